@@ -18,9 +18,19 @@ names 1024^3 at 1/2/4/8 GPUs); N>1 = Z-slab chain with a one-plane exchange per 
     arrangement (gpu_engine.h:680-682).  On a box with fewer than N devices the slabs share devices ("virtual slabs").
 
 Prints ONE JSON line on rank 0: metric Gvoxel-updates/s = Nx*Ny*Nz*K / t / 1e9 (the reference's own formula,
-cpu_engine.h:357 / gpu_engine.h:1253), plus `roofline` (dominant kernel, HIP-event timed in a region of its own --
-the headline regions run without per-launch events --, algorithmic bytes = 12.125 B/voxel fp32) and `cpu_baseline`
-(the CPU oracle on this box's host cores, bounded sample).
+cpu_engine.h:357 / gpu_engine.h:1253) and ms_per_step.  A plain run sets up, warms up, times ONE region of K steps
+(--repeats R: R regions, the median reported), writes its outputs if --dump-outputs is given, and prints that line.
+
+--full adds everything else, as one run: the headline timed over 7 regions by default, `roofline` (dominant kernel,
+HIP-event timed in a region of its own -- the headline regions run without per-launch events --, algorithmic bytes =
+12.125 B/voxel fp32, HBM traffic from rocprofv3 --pmc child passes), the kernel-family `selfcheck`, the `rigid_walls`
+run, the exchange checksums of N > 1 and `cpu_baseline` (the reference's CPU engine on this box's host cores, bounded
+sample).  The --no-* switches turn single legs of a --full run off.
+
+--dump-outputs DIR writes what the timed path computed, after its last timed step, as .npy files: u_out.npy = every
+receiver's samples of the steps run so far (float64, the rows in the scene's order); for one domain on one GPU also
+u_n_sample.npy / u_nm1_sample.npy = the state grids u^n and u^{n-1} at a fixed, seeded sample of 2^20 interior cells
+(the grid's precision).  The inputs (scene, seeded initial fields) depend on the arguments only.
 """
 import argparse
 import json
@@ -146,6 +156,40 @@ def fill_engine_grids(torch, eng_view, nplanes, plane_elems, real_bytes, device,
         torch.cuda.synchronize()
 
 
+DUMP_SAMPLES = 1 << 20  # interior cells of each state grid written by --dump-outputs
+DUMP_SEED = 20240917
+
+
+def dump_outputs(out_dir, u_out, eng=None, loc=None, device=0):
+    """--dump-outputs: u_out.npy = the receivers' samples so far; with `eng` (one domain) the state grids u^n / u^{n-1} at
+    DUMP_SAMPLES interior cells drawn by a fixed seed in the file's (x, y, z), read from the grids as the engine stores them."""
+    import torch
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "u_out.npy", np.ascontiguousarray(u_out, dtype=np.float64))
+    if eng is None:
+        return
+    (planes, rows, cols), pitch, exchanged = eng.layout()
+    nx, ny, nz = loc.Nx, loc.Ny, loc.Nz
+    if (planes, rows, cols) != ((nz, ny, nx) if exchanged else (nx, ny, nz)):
+        raise SystemExit(f"bench: --dump-outputs: stored grid {planes}x{rows}x{cols} is not the file's {nx}x{ny}x{nz}")
+    rng = np.random.default_rng(DUMP_SEED)
+    x, y, z = (rng.integers(1, n - 1, DUMP_SAMPLES) for n in (nx, ny, nz))
+    p, c = (z, x) if exchanged else (x, z)
+    flat = (p * rows + y) * pitch + c
+    assert 0 <= flat.min() and flat.max() < planes * rows * pitch
+    ts, dt = ("<f4", np.float32) if loc.real_bytes == 4 else ("<f8", np.float64)
+    u_prev, u_cur = eng.state_grids()
+    with torch.cuda.device(device):
+        idx = torch.as_tensor(flat, dtype=torch.int64, device=f"cuda:{device}")
+        for name, ptr in (("u_nm1_sample", u_prev), ("u_n_sample", u_cur)):
+            g = torch.as_tensor(_DevMem(ptr, (planes * rows * pitch,), ts), device=f"cuda:{device}")
+            assert g.data_ptr() == ptr
+            np.save(out / f"{name}.npy", g[idx].cpu().numpy().astype(dt, copy=False))
+            del g
+        torch.cuda.synchronize()
+
+
 def roofline_block(args, sd, tm, K, real_bytes, interior_planes, interior_per_plane=None):
     """`roofline` of the bench line from an engine's timing record (collected in a region with per-launch events on).
     interior_per_plane: interior cells of one stored plane (default: the file's (Ny-2)(Nz-2); a chain cut along file z
@@ -230,7 +274,7 @@ def measure_traffic_live(args, inst):
     except Exception:  # noqa: BLE001
         arch = ""
     rd_scale = 2 if arch == "gfx950" else 1  # gfx950 tallies 128-B read requests as 64 B (guides/MI355X_MICROARCH.md)
-    child = [sys.executable, str(ROOT / "bench.py"), "--steps", "6", "--warmup", "2", "--repeats", "1", "--no-rigid-run", "--no-cpu-baseline",
+    child = [sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "6", "--warmup", "2", "--repeats", "1", "--no-rigid-run", "--no-cpu-baseline",
              "--no-selfcheck", "--no-pmc", "--size", str(args.size), "--precision", args.precision, "--mb", str(args.mb),
              "--variant", str(args.variant), "--chunk", str(args.chunk), "--numerics", str(args.numerics), "--debug", hex(args.debug | 0x8000)]
     child += ["--split-phase"] if args.split_phase else []
@@ -375,13 +419,13 @@ def run_chain(args, only=None):
     devices = [0] * N if only else (list(range(N)) if ndev >= N else [i % ndev for i in range(N)])
     lossy = not args.rigid
     real_bytes = 4 if args.precision == "single" else 8
-    sd = build_scene(args.size, (R + 1) * K + W, args.precision, args.fcc, lossy, args.mb, args.nx, args.ny)
+    sd = build_scene(args.size, W + R * K + (K if args.full else 0), args.precision, args.fcc, lossy, args.mb, args.nx, args.ny)
     transport = {"auto": engine.PF_TRANSPORT_AUTO, "peer": engine.PF_TRANSPORT_PEER, "rccl": engine.PF_TRANSPORT_RCCL,
                  "host": engine.PF_TRANSPORT_HOST}[args.transport]
     if only:
         transport = engine.PF_TRANSPORT_RCCL if args.emulate_transport == "rccl" else engine.PF_TRANSPORT_PEER
     m = engine.HipMulti(sd, devices, numerics=args.numerics, air_variant=args.variant, air_chunk=args.chunk, debug=args.debug,
-                        transport=transport, verify_exchange=0 if only else min(max(W, 2), 6), only_slab=(only[0] + 1) if only else 0, wall_scale=args.wall_scale,
+                        transport=transport, verify_exchange=0 if only or not args.full else min(max(W, 2), 6), only_slab=(only[0] + 1) if only else 0, wall_scale=args.wall_scale,
                         multi_flags=0 if args.wall_scale > 0 else engine.PF_MULTI_MEASURE_WEIGHTS)  # (first contact: the first exchanges of every chain -- up to six: two whole triples' worth of split-phase steps -- are checksummed, inside the warm-up)
     live = [only[0]] if only else list(range(N))
     slabs = [m.slab(g) for g in live]
@@ -405,6 +449,20 @@ def run_chain(args, only=None):
     regions = [timed_region(W + r * K) for r in range(R)]
     el = sorted(regions)[len(regions) // 2]
     info = m.info()
+    if args.dump_outputs:  # (the chain writes every slab's receiver rows into sd.u_out; an emulated rank: its own)
+        dump_outputs(args.dump_outputs, sd.u_out[:, :W + R * K])
+    virt = ndev < N
+    parallelism = (f"z-slab x{N}, ONE process, one host thread per slab (pf_multi_create), ghost planes by {info['transport_name']} "
+                   "on the edge stream while the interior planes run"
+                   + (f"; VIRTUAL: the {N} slabs share {ndev} device(s) -- control-flow run, not a scaling figure" if virt else ""))
+    if only:
+        parallelism = (f"COST MODEL of rank {only[0]} of a z-slab x{N} chain on one device: slab {only[0]} alone exists (pf_opts.only_slab) and "
+                       f"exchanges its own edge planes with itself by {info['transport_name']}; value = what an {N}-rank chain of such ranks would do")
+    res = base_result(args, sd, N, K, W, R, regions, el, real_bytes, lossy, parallelism)
+    if not args.full:
+        m.close()
+        print(json.dumps(res), flush=True)
+        return
     if not only and not np.isfinite(sd.u_out[:, :W + R * K]).all():
         raise SystemExit("bench: non-finite receiver samples")
     # kernel durations: one more region with per-launch events on
@@ -413,15 +471,7 @@ def run_chain(args, only=None):
         sl["engine"].timing(reset=True)
     m.run(W + R * K, K)
     tms = [sl["engine"].timing() for sl in slabs]
-    virt = ndev < N
-    parallelism = (f"z-slab x{N}, ONE process, one host thread per slab (pf_multi_create), ghost planes by {info['transport_name']} "
-                   "on the edge stream while the interior planes run"
-                   + (f"; VIRTUAL: the {N} slabs share {ndev} device(s) -- control-flow run, not a scaling figure" if virt else ""))
-    res = base_result(args, sd, N, K, W, R, regions, el, real_bytes, lossy, parallelism)
     if only:
-        parallelism = (f"COST MODEL of rank {only[0]} of a z-slab x{N} chain on one device: slab {only[0]} alone exists (pf_opts.only_slab) and "
-                       f"exchanges its own edge planes with itself by {info['transport_name']}; value = what an {N}-rank chain of such ranks would do")
-        res = base_result(args, sd, N, K, W, R, regions, el, real_bytes, lossy, parallelism)
         res["emulated_slab"] = {"rank": only[0], "of": N, "planes": [slabs[0]["x0"], slabs[0]["x1"]], "pairs": slabs[0]["paired"], "steps_per_pass": slabs[0]["steps_per_pass"],
                                 "ms_per_step": round(el / K * 1e3, 4), "ideal_ms_per_step_note": "single-domain ms/step / N"}
     g0 = max(range(len(slabs)), key=lambda g: slabs[g]["x1"] - slabs[g]["x0"])
@@ -453,7 +503,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=7, help="the K-step region is timed this many times; value = the MEDIAN region")
+    ap.add_argument("--repeats", type=int, default=None, help="the K-step region is timed this many times; value = the MEDIAN region "
+                    "(default: 1, with --full 7)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline as well: roofline, HBM traffic, self-check, "
+                    "rigid-wall run, exchange checksums, CPU baseline (the --no-* switches turn single legs off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the timed path computed after its last timed step "
+                    "as DIR/<name>.npy")
     ap.add_argument("--no-rigid-run", action="store_true", help="skip the second, rigid-wall run (SURVEY 8d asks for both)")
     ap.add_argument("--no-selfcheck", action="store_true", help="skip the family-agreement check of the timed run")
     ap.add_argument("--size", type=int, default=1024)
@@ -480,6 +535,8 @@ def main():
     ap.add_argument("--emulate-via", default="chain", choices=["chain", "torch"],
                     help="with --emulate-slab: through the C chain object (pf_opts.only_slab; default) or the torch.distributed runner")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
     if args.emulate_slab and args.emulate_via == "chain":
         return run_chain(args, only=tuple(int(v) for v in args.emulate_slab.split("/")))
 
@@ -524,7 +581,7 @@ def main():
     K, W, R = args.steps, args.warmup, max(args.repeats, 1)
     n = args.size
     lossy = not args.rigid
-    nt_total = (R + 1) * K + W  # warm-up, R headline regions, one region with per-launch events
+    nt_total = W + R * K + (K if args.full else 0)  # warm-up, R headline regions (--full: one region with per-launch events)
     sd = build_scene(n, nt_total, args.precision, args.fcc, lossy, args.mb, args.nx, args.ny)
     real_bytes = 4 if args.precision == "single" else 8
     ekw = dict(numerics=args.numerics, air_variant=args.variant, air_chunk=args.chunk, timing=False, debug=args.debug)
@@ -589,7 +646,7 @@ def main():
             import torch.distributed as dist
             dist.barrier()
 
-    runner.verify_steps = min(W, 6) if world > 1 else 0  # N>1: checksum the first exchanges against the senders' planes
+    runner.verify_steps = min(W, 6) if world > 1 and args.full else 0  # N>1: checksum the first exchanges against the senders' planes
     run(0, W)
     sync()
 
@@ -612,6 +669,27 @@ def main():
 
     regions = [timed_region(W + r * K) for r in range(R)]
     el = sorted(regions)[len(regions) // 2]  # the median region is the one reported
+    if args.dump_outputs:
+        runner.finish()  # (receiver samples still on the device: a split-phase loop leaves them there)
+        if world > 1:
+            u_out = pdist.gather_outputs(sd, loc, info, group)[:, :W + R * K]
+        elif info.G == 1:
+            u_out = pdist.gather_outputs(sd, loc, info)[:, :W + R * K]
+        else:  # an emulated slab: its own receivers
+            u_out = loc.u_out[:, :W + R * K]
+        if rank == 0:
+            dump_outputs(args.dump_outputs, u_out, eng if info.G == 1 else None, loc, local_rank)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(base_result(args, sd, world, K, W, R, regions, el, real_bytes, lossy, parallelism)), flush=True)
+        if world > 1:
+            import torch.distributed as dist
+            dist.barrier()
+            runner.close_comm()
+            dist.destroy_process_group()
+        else:
+            runner.st.close()
+        return
     # kernel durations: one more K-step region with HIP events around every launch (not part of `value`)
     eng.set_timing(True)
     eng.timing(reset=True)

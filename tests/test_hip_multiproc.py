@@ -79,7 +79,7 @@ def test_bench_two_ranks_control_flow():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29617", str(root / "bench.py"), "--gpus", "2", "--size", "320", "--steps", "6", "--warmup", "3",
+           "--master-port", "29617", str(root / "bench.py"), "--full", "--gpus", "2", "--size", "320", "--steps", "6", "--warmup", "3",
            "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(root))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
