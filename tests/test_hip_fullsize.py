@@ -1,4 +1,6 @@
-"""GPU, large grids (the oracle is too slow there): size-independent properties instead of point-wise oracle parity.
+"""GPU, large grids: size-independent properties and agreement between the kernel families.  (Point-wise oracle parity of the default path at
+1024^3 ... 1536^3 is tests/test_hip_fullsize_oracle.py's; what this module adds is the agreement of ALL families with each other, also
+beyond 2^32 CELLS -- 4224 x 1024 x 1024 -- which the oracle cases do not reach, linearity and causality.)
   * three independent interior-kernel families (lean fused / barrier-free marching / naive one-thread-per-cell) must
     produce identical bits on a 512^3 lossy room;
   * linearity: doubling the input doubles every receiver sample exactly (power-of-two scaling is exact in fp);

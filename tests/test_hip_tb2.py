@@ -494,6 +494,39 @@ def test_three_steps_per_pass_give_the_oracles_bits(prec, numerics):
 
 
 @pytest.mark.parametrize("prec", ["single", "double"])
+@pytest.mark.parametrize("numerics", [engine.PF_NUM_CPU_EXACT, engine.PF_NUM_GPU_SAFEGUARDED], ids=["exact", "safeguarded"])
+def test_three_steps_per_pass_across_run_boundaries_give_the_oracles_bits(prec, numerics):
+    """The scene of test_three_steps_per_pass_give_the_oracles_bits stepped as run(0, 7); run(7, 13); run(20, Nt - 20) on ONE engine: a triple
+    does not survive a run() boundary (Engine::run), so the runs end in a single step, in a single step after four triples, and in a pair --
+    and the next run's first triple starts from what those left behind (u^{n+1} of the triples' tiles, the regions' double-buffered branch
+    state, the receivers' ring).  The same oracle receivers and final field as the run in one piece (tests/test_hip_fullsize_oracle.py, A3,
+    does this at 1024^3)."""
+    sim = triple_scene(Nt=100, n=(48, 100, 280 if prec == "single" else 264))
+    sd = sim_data.SimData.from_sim(sim, prec)
+    sd.scale_input()
+    e = oracle.Engine(sd, safeguarded=numerics == engine.PF_NUM_GPU_SAFEGUARDED)
+    for k in range(sd.Nt):
+        e.step(k)
+    ref_out, ref_u0, ref_u1 = sd.u_out.copy(), e.grid(0).copy(), e.grid(1).copy()
+    e.close()
+    assert (np.abs(ref_out[:-8]).max(axis=1) > 0).all()
+    for chunk in (0, 7):
+        hip = sim_data.SimData.from_sim(sim, prec, build_mask=False)
+        hip.scale_input()
+        eng = engine.HipEngine(hip, air_variant=40, timing=True, numerics=numerics, readout_chunk=chunk)
+        for n0, n in ((0, 7), (7, 13), (20, hip.Nt - 20)):
+            eng.run(n0, n)
+        tm = eng.timing()
+        g = [eng.get_grid(0).copy(), eng.get_grid(1).copy()]
+        eng.close()
+        assert tm["tb_steps_per_pass"] == 3 and tm["tb2_launches"] > 0 and sum(tm["wall_blocks"]) > 0 and tm["steps"] == 100, tm
+        assert tm["wall_three_steps"] == (0 if prec == "double" else 9) and tm["tb2_dirty_tiles"] == 0, tm
+        assert np.array_equal(hip.u_out, ref_out), chunk
+        assert np.array_equal(g[0][1:-1, 1:-1, 1:-1], ref_u0[1:-1, 1:-1, 1:-1]), chunk
+        assert np.array_equal(g[1][1:-1, 1:-1, 1:-1], ref_u1[1:-1, 1:-1, 1:-1]), chunk
+
+
+@pytest.mark.parametrize("prec", ["single", "double"])
 @pytest.mark.parametrize("sx,sy,sz", [(24, 24, 140), (24, 25, 140), (24, 26, 140), (24, 27, 140), (18, 50, 140), (19, 50, 140), (20, 50, 140),
                                       (31, 44, 251), (32, 45, 254), (33, 46, 257), (24, 86, 20)])
 def test_sources_added_inside_k_tb3_at_tile_borders(sx, sy, sz, prec):

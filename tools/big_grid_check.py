@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Grids beyond 2^32 cells: the interior-kernel families (blocked pairs, lean single steps, barrier-free, unfused) must
-agree bit for bit on EVERY cell and on the receivers (the oracle is too slow there).  The fields start from seeded random
+agree bit for bit on EVERY cell and on the receivers (the oracle pins the default path up to 1536^3, tests/test_hip_fullsize_oracle.py;
+this check adds every other family, and grids beyond 2^32 cells, which those cases do not reach).  The fields start from seeded random
 data, so every cell is live from step 0.   usage: tools/big_grid_check.py [--fcc] [--double] [Nx Ny Nz] [Nt]"""
 import sys
 import time

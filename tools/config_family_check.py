@@ -2,8 +2,9 @@
 """The reference's test-script configurations at FULL size (BASELINE configs[1] CTK 894x579x309 7-point, configs[2]
 Musikverein 2852x552x850 folded 13-point): the scene is voxelised and GPU-prepared on this box (sim_setup), then several
 independent interior-kernel families step it from the same seeded random fields and must leave identical bits in every
-cell and at every receiver (the CPU oracle is too slow at these sizes; tests/test_sim_setup.py pins the same geometries
-against the oracle at coarse resolution).   usage: tools/config_family_check.py ctk_cart_gpu|mv_fcc_gpu [steps]"""
+cell and at every receiver (the default path on these rooms is pinned to the CPU oracle at full size by tests/test_hip_fullsize_oracle.py,
+case D; this check adds the other families and caller-owned grids; tests/test_sim_setup.py pins the same geometries against the oracle at
+coarse resolution).   usage: tools/config_family_check.py ctk_cart_gpu|mv_fcc_gpu [steps]"""
 import sys
 import tempfile
 import time
