@@ -167,6 +167,8 @@ typedef struct pf_timing {
    int64_t wall_three_steps;/* triples: which wall regions take all three steps in ONE pass (k_wall2<..., NS = 3>): bit 0 the x / y regions, bit 3 the
                                column strips; 0: two steps + one.  Slabs of a chain: bits 4 / 5 -- the slab's low / high x side is the grid's own wall
                                and a region's and the bricks' too (no single steps of its planes) */
+   int64_t wall_profile;    /* of the regions in wall_three_steps, which run with the node layout of a plain box wall compiled in (pf_wall.h: wall profiles):
+                               bit 0 the x / y regions, bit 3 the column strips; 0: the node words are read from the blocks */
 } pf_timing;
 
 typedef struct pf_engine pf_engine;

@@ -266,6 +266,7 @@ template <typename Real> struct Engine : EngineBase {
    bool wl_ns3 = false, wl_ns3z = false, wl_no_ns3 = false;                // the x / y regions take three steps per pass (k_wall2<..., NS = 3>); ... found impossible for this scene
    Real *ubx[2] = {nullptr, nullptr};                     // single domains with wall regions: two more node-value buffers beside ub[0..2]
    int wl_geo[4] = {0, 0, 0, 0};                          // per launch group: the box margin all its regions' pencils share (standard geometry, pf_wall.h GD), else 0
+   int wl_prof[4] = {0, 0, 0, 0};                         // per launch group: the wall profile all its alike blocks' node words match (pf_wall.h PR), else 0
    int wl_chunk_want[2] = {0, 0};                         // march steps per block the x / y regions' and the column strips' launches aim for (init_walls)
    size_t wl_brk_lds = 0;                                 // dynamic LDS of a brick launch (the largest brick)
    Real *vh1b = nullptr, *gh1b = nullptr;                 // the other half of the double-buffered branch state
@@ -910,6 +911,7 @@ template <typename Real> struct Engine : EngineBase {
          for (const WlGroup &g : wl_grp) { tm.wall_blocks[0] += g.nblk[0] + g.nblk[2]; tm.wall_blocks[1] += g.nblk[1]; }
       tm.wall_bricks = wl_on ? wl_nbrk : 0;
       tm.wall_three_steps = (wl_on && (tb3 || (tb3_slab && ws_all3))) ? ((wl_ns3 ? 1 : 0) | (wl_ns3z ? 8 : 0) | (wl_xw[0] ? 0x10 : 0) | (wl_xw[1] ? 0x20 : 0)) : 0;
+      tm.wall_profile = (((tm.wall_three_steps & 1) && wl_geo[0] == 6 && wl_prof[0]) ? 1 : 0) | (((tm.wall_three_steps & 8) && wl_geo[3] == 16 && wl_prof[3]) ? 8 : 0);
       if (t) *t = tm;
       if (reset) tm = pf_timing{};
       return PF_OK;

@@ -31,6 +31,7 @@
       auto F = [](auto *&p) { if (p) hipFree((void *)p); p = nullptr; };
       F(wl_pen); F(wl_rec); F(wl_rest); F(wl_blk); F(wl_brk); F(wl_binfo); F(wl_blos); F(vh1b); F(gh1b); F(ubx[0]); F(ubx[1]);
       wl_nbrk = 0; wl_brk_lds = 0; wl_ns3 = wl_ns3z = false;
+      for (int &p : wl_prof) p = 0;
       wl_xw[0] = wl_xw[1] = false;
       wl_on = false;
       for (auto &g : wl_grp) g = WlGroup{};
@@ -483,6 +484,24 @@
          wl_grp[0].blk0b = (uint32_t)all.size(); wl_grp[0].nblkb = (uint32_t)lists2.size(); all.insert(all.end(), lists2.begin(), lists2.end());
          if ((rc = upload(&wl_blk, all.data(), (int64_t)all.size()))) return no_room(); // (the lossy arrays are re-ordered by now: consistently, which any path accepts)
       }
+      // Does every alike block of a three-step launch group carry the node words of a wall profile (pf_wall.h: wall_profile_words -- the two node
+      // layers of a plain box wall)?  Then the bodies with those words compiled in run (fp32: fp64 takes no three steps per pass); one block that
+      // differs -- a room that is no plain box, other wall depths, mixed materials -- keeps the bodies that read the words from the block.
+      for (int gi = 0; gi < 4; gi++) {
+         wl_prof[gi] = 0;
+         const std::vector<uint4> &bl = lists[3 * gi];
+         if (sizeof(Real) != 4 || (gi != 0 && gi != 3) || wl_geo[gi] <= 0 || bl.empty() || !lists[3 * gi + 2].empty() || (op.debug & PF_DBG_RUNTIME_NODES)) continue;
+         const int dp = gi == 0 ? DPX : 20;
+         for (int pr = 1; pr <= pf::WALL_NPROF && !wl_prof[gi]; pr++) {
+            bool all = true;
+            for (const uint4 &b : bl) {
+               const pf::WallRegion &R = wl_grp[gi].reg[b.x & 7u];
+               const pf::WallNodes n = pf::wall_profile_words(R.mode, R.kg != 0, dp, pr);
+               if (b.y != n.x || b.z != n.z || b.w != n.w) { all = false; break; }
+            }
+            if (all) wl_prof[gi] = pr;
+         }
+      }
       wl_ns3 = ns3; wl_ns3z = ns3z;
       if ((ns3 && wl_grp[0].nblk[1] > 0) || (ns3z && wl_grp[3].nblk[1] > 0)) { // some x / y block is not alike (a room that is no plain box): those regions keep two steps + one
          wl_no_ns3 = true;
@@ -539,21 +558,36 @@
 #define PF_WALL_S(DP, VEC, S) do { if (ns == 1) PF_WALL_N(DP, VEC, S, 1); else PF_WALL_N(DP, VEC, S, 2); } while (0)
 #define PF_WALL(DP, VEC) do { if (sg) PF_WALL_S(DP, VEC, true); else PF_WALL_S(DP, VEC, false); } while (0)
             // x / y regions with three-step tables (10-cell pencils, alike blocks only: init_walls): three steps, or the two of a run's last pair
-#define PF_WALL3_N(S, NSV, GDV) do { if (q != 0) break; \
-                              if (mb_max <= 4) hipLaunchKernelGGL((pf::k_wall2<Real, 10, false, true, true, 4, S, NSV, GDV>), gd, b, 0, st, wp, a1, a2); \
-                              else hipLaunchKernelGGL((pf::k_wall2<Real, 10, false, true, true, 12, S, NSV, GDV>), gd, b, 0, st, wp, a1, a2); } while (0)
-#define PF_WALL3(NSV, GDV) do { if (sg) PF_WALL3_N(true, NSV, GDV); else PF_WALL3_N(false, NSV, GDV); } while (0)
-            // (wl_geo: every region of the group has the standard pencil geometry of a box with that margin -- the kernel with it compiled in)
-            if (gi == 0 && wl_ns3) { if (ns == 3) { if (wl_geo[0] == 6) PF_WALL3(3, 6); else PF_WALL3(3, 0); } else if (ns == 2) PF_WALL3(2, 0); }
+#define PF_WALL3_N(S, NSV, GDV, PRV, MCLO) do { if (q != 0) break; \
+                              if (mb_max <= 4 || MCLO) hipLaunchKernelGGL((pf::k_wall2<Real, 10, false, true, true, 4, S, NSV, GDV, PRV>), gd, b, 0, st, wp, a1, a2); \
+                              else hipLaunchKernelGGL((pf::k_wall2<Real, 10, false, true, true, MCLO ? 4 : 12, S, NSV, GDV, PRV>), gd, b, 0, st, wp, a1, a2); } while (0)
+#define PF_WALL3P(NSV, GDV, PRV, MCLO) do { if (sg) PF_WALL3_N(true, NSV, GDV, PRV, MCLO); else PF_WALL3_N(false, NSV, GDV, PRV, MCLO); } while (0)
+#define PF_WALL3(NSV, GDV) PF_WALL3P(NSV, GDV, 0, false)
+            // (wl_geo: every region of the group has the standard pencil geometry of a box with that margin -- the kernel with it compiled in;
+            // wl_prof: every alike block of the group has the node words of that wall profile -- the kernel with them compiled in too.  Profile 2 holds
+            // no frequency-dependent node, so no branch state moves whatever the scene's branch count: one instantiation, MC = 4)
+            bool profiled = false;
+            if constexpr (sizeof(Real) == 4) {
+               if (gi == 0 && wl_ns3 && ns == 3 && wl_geo[0] == 6 && wl_prof[0] > 0) {
+                  if (wl_prof[0] == 1) PF_WALL3P(3, 6, 1, false); else PF_WALL3P(3, 6, 2, true);
+                  profiled = true;
+               }
+            }
+            if (profiled) {}
+            else if (gi == 0 && wl_ns3) { if (ns == 3) { if (wl_geo[0] == 6) PF_WALL3(3, 6); else PF_WALL3(3, 0); } else if (ns == 2) PF_WALL3(2, 0); }
             else if (gi == 3 && ns == 3) { // column strips with three-step tables (wl_ns3z; fp32 only)
                if constexpr (sizeof(Real) == 4) {
                   if (q == 0) {
-#define PF_WALLZ3(GDV) do { \
-                     if (mb_max <= 4) { if (sg) hipLaunchKernelGGL((pf::k_wall2<Real, 20, true, true, true, 4, true, 3, GDV>), gd, b, 0, st, wp, a1, a2); \
-                                        else hipLaunchKernelGGL((pf::k_wall2<Real, 20, true, true, true, 4, false, 3, GDV>), gd, b, 0, st, wp, a1, a2); } \
-                     else { if (sg) hipLaunchKernelGGL((pf::k_wall2<Real, 20, true, true, true, 12, true, 3, GDV>), gd, b, 0, st, wp, a1, a2); \
-                            else hipLaunchKernelGGL((pf::k_wall2<Real, 20, true, true, true, 12, false, 3, GDV>), gd, b, 0, st, wp, a1, a2); } } while (0)
-                     if (wl_geo[3] == 16) PF_WALLZ3(16); else PF_WALLZ3(0);
+#define PF_WALLZ3P(GDV, PRV, MCLO) do { \
+                     if (mb_max <= 4 || MCLO) { if (sg) hipLaunchKernelGGL((pf::k_wall2<Real, 20, true, true, true, 4, true, 3, GDV, PRV>), gd, b, 0, st, wp, a1, a2); \
+                                        else hipLaunchKernelGGL((pf::k_wall2<Real, 20, true, true, true, 4, false, 3, GDV, PRV>), gd, b, 0, st, wp, a1, a2); } \
+                     else { if (sg) hipLaunchKernelGGL((pf::k_wall2<Real, 20, true, true, true, MCLO ? 4 : 12, true, 3, GDV, PRV>), gd, b, 0, st, wp, a1, a2); \
+                            else hipLaunchKernelGGL((pf::k_wall2<Real, 20, true, true, true, MCLO ? 4 : 12, false, 3, GDV, PRV>), gd, b, 0, st, wp, a1, a2); } } while (0)
+#define PF_WALLZ3(GDV) PF_WALLZ3P(GDV, 0, false)
+                     if (wl_geo[3] == 16 && wl_prof[3] == 1) PF_WALLZ3P(16, 1, false);
+                     else if (wl_geo[3] == 16 && wl_prof[3] == 2) PF_WALLZ3P(16, 2, true);
+                     else if (wl_geo[3] == 16) PF_WALLZ3(16); else PF_WALLZ3(0);
+#undef PF_WALLZ3P
 #undef PF_WALLZ3
                   }
                }
@@ -563,6 +597,7 @@
             else if (gi == 2) PF_WALL(16, true);
             else if constexpr (sizeof(Real) == 4) PF_WALL(20, true);
 #undef PF_WALL3
+#undef PF_WALL3P
 #undef PF_WALL3_N
 #undef PF_WALL
 #undef PF_WALL_S

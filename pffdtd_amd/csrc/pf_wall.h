@@ -157,6 +157,29 @@ __device__ __forceinline__ Real fd_regs(Real p, Real u2, Real sf, int32_t k, con
    return u;
 }
 
+// Wall profiles (PR > 0; alike blocks of three-step launches with constant pencil geometry, GD > 0): the NODE structure of the block's pencils
+// compiled in as well.  For the walls of a plain box the three words a block carries (WallParams::blk .y / .z / .w) are a pure function of
+// (mode, side, wall depth): two node cells at pencil depths 2 and 3 from the ghost cell -- the outer one rigid, the inner one frequency-dependent
+// (PR = 1) or rigid too (PR = 2: a room without lossy materials) --, each with every neighbour but the one across the wall surface.  In pencil
+// order the first node lacks its neighbour on the +normal side and the second the one on the -normal side, on either side of the grid.  The host
+// launches these bodies only when every block of every region of the launch carries exactly wall_profile_words() (Engine::launch_walls_x).
+struct WallNodes { uint32_t x, z, w; }; // node cells; adjacency of the nodes in pencil order, 6 bits each (file order +x -x +y -y +z -z); lossy flags | cell of the frequency-dependent node << 8
+struct WallProfileRow { int outer, inner; bool fd; }; // depths of the two node layers from the ghost cell; is the inner one frequency-dependent?
+constexpr int WALL_NPROF = 2;
+constexpr WallProfileRow WALL_PROFILES[WALL_NPROF] = {{2, 3, true}, {2, 3, false}};
+constexpr WallNodes wall_profile_words(int MODE, bool HI, int DP, int PR) {
+   if (PR < 1 || PR > WALL_NPROF) return WallNodes{0u, 0u, 0u};
+   const WallProfileRow r = WALL_PROFILES[PR - 1];
+   const int ko = HI ? DP - 1 - r.outer : r.outer, ki = HI ? DP - 1 - r.inner : r.inner; // (the ghost cell: 0 / DP - 1)
+   const uint32_t all = 63u, no_p = all & ~(1u << (2 * MODE)), no_m = all & ~(2u << (2 * MODE));
+   WallNodes n{(1u << ko) | (1u << ki), no_p | (no_m << 6), 0u};
+   if (r.fd) n.w = (HI ? 1u : 2u) | ((uint32_t)ki << 8); // (the inner node is the second of a low-side pencil, the first of a high-side one)
+   return n;
+}
+template <int B, int E, typename F> __device__ __forceinline__ void wall_static_for(F &&f) {
+   if constexpr (B < E) { f(std::integral_constant<int, B>()); wall_static_for<B + 1, E>(f); }
+}
+
 // FAST: the host found every pencil the block evaluates (all lanes, all march steps) to have the SAME structure -- the same node
 // cells with the same adjacency, at most one frequency-dependent node -- and no ghost or ABC cell along the lane and march
 // axes: walls away from edges and corners, the bulk of the work.  The structure then arrives with the block (ds*) and the
@@ -174,7 +197,10 @@ __device__ __forceinline__ Real fd_regs(Real p, Real u2, Real sf, int32_t k, con
 // DP-GD .. DP-2, pencil from N - DP -- and a compile-time constant: the ghost mirror, the owned range of every store, the ABC cell and the load
 // clamps cost no scalar compares and selects per cell and stage any more (x / y regions: -12 % vector, -29 % scalar instructions per march
 // step).  The host launches these bodies only when every region of the launch has that geometry (Engine::launch_walls_x), else GD = 0.
-template <typename Real, int DP, int MODE, bool FAST, bool NODES, int MC, bool SG, int NS = 2, int GD = 0, bool HI = false>
+// PR > 0 (with GD > 0 only): a wall profile, above -- the per-cell node test is decided at compile time, node cells skip the air update, the rigid
+// update runs in line with constant adjacency (the same upd_rigid call, the same operand order: the same bits), the frequency-dependent node's
+// value goes back with one assignment, and the three words are never made opaque.
+template <typename Real, int DP, int MODE, bool FAST, bool NODES, int MC, bool SG, int NS = 2, int GD = 0, bool HI = false, int PR = 0>
 __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const WallRegion &R, const int j, const int c, const Real a1, const Real a2,
                                           const WallLds<Real> *ldsp, const uint32_t dsx, const uint32_t dsz, const uint32_t dsw, WallJobs<Real> *jobs = nullptr) {
    constexpr bool VEC = MODE == 2;
@@ -211,6 +237,9 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
    int rkg = CG ? (HI ? DP - 1 : 0) : R.kg, rko0 = CG ? (HI ? DP - GD : 1) : R.ko0, rko1 = CG ? (HI ? DP - 1 : GD) : R.ko1;
    int rkb0 = CG ? (HI ? DP - GD - 3 : 0) : R.kb0, rkb1 = CG ? (HI ? DP : GD + 3) : R.kb1, rnbase = CG ? (HI ? NN - DP : 0) : R.nbase;
    uint32_t usx = dsx, usz = dsz, usw = dsw;
+   constexpr bool PN = PR > 0; // constant node structure
+   static_assert(!PN || (CG && NODES), "wall profiles: bodies with constant pencil geometry");
+   constexpr WallNodes WN = wall_profile_words(MODE, HI, DP, PR);
    auto msrc = [&](int m) __attribute__((always_inline)) {
       m = min(max(m, 0), NM - 1);
       if (FAST) return m;
@@ -248,7 +277,7 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
    };
    auto load_ent = [&](int m) __attribute__((always_inline)) { // march steps R.m0 - hm .. R.m1 + hm - 1 have entries
       const uint4 *e = wp.pen + (R.pen_off + (int64_t)(min(m, R.m1 + R.hm - 1) - (R.m0 - R.hm)) * R.nlp + (lt * j + lane));
-      if (FAST && !NODES) return make_uint4(0u, 0u, 0u, 0u);
+      if (FAST && (!NODES || (PN && (WN.w & 31u) == 0u))) return make_uint4(0u, 0u, 0u, 0u);
       if (FAST) return make_uint4(0u, 0u, 0u, e->w); // (only the place of the frequency-dependent node differs from lane to lane)
       return *e;
    };
@@ -318,6 +347,39 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
          // wherever the aligned pencil puts it: applied after the loop through selects -- one copy of the double-precision
          // division instead of one per pencil cell)
          st = false;
+         if constexpr (PN) { // the node structure is a compile-time constant (wall_profile_words)
+            constexpr uint32_t sx = WN.x, sw5 = WN.w & 31u;
+            constexpr int sk0 = (int)(WN.w >> 8);
+            Real pfd = Real(0);
+            wall_static_for<1, DP - 1>([&](auto kc) __attribute__((always_inline)) {
+               constexpr int k = decltype(kc)::value;
+               const Real cc = Cur[k];
+               const Real lm = lane_from_lower<true>(cc), lp = lane_from_upper<true>(cc);
+               Real p;
+               if constexpr (((sx >> k) & 1u) != 0u) {
+                  constexpr uint32_t jn = k == 0 ? 0u : (uint32_t)__builtin_popcount(sx & ((1u << k) - 1u));
+                  p = rigid((WN.z >> (6 * jn)) & 63u, cc, Old[k], Cur[k + 1], Cur[k - 1], Nxt[k], Prv[k], lp, lm);
+                  if constexpr (sw5 != 0u && k == sk0) pfd = p;
+               } else {
+                  p = air(cc, Old[k], Cur[k + 1], Cur[k - 1], Nxt[k], Prv[k], lp, lm);
+                  if constexpr (k == 1) { if (__builtin_expect(!HI && ng_lo, 0)) p = abc_loss<SG>(p, Old[k], wp.l); } // (cpu_engine.h:225-229)
+               }
+               Out[k] = p;
+            });
+            static_assert(((sx >> 1) & 1u) == 0u && ((sx >> (DP - 2)) & 1u) == 0u, "wall profiles: no node on the ABC cell");
+            if (HI && ng_hi) Out[DP - 2] = abc_loss<SG>(Out[DP - 2], Old[DP - 2], wp.l);
+            if constexpr (sw5 != 0u) { // (cpu_engine.h:290-301, 363-405) the pencils' frequency-dependent node: state in registers
+               const bool owner = own_m && own_lane && sk0 >= rko0 && sk0 < rko1;
+               if (eval_lane && (STAGE < NS || STAGE == 1 || owner)) {
+                  pfd = fd_regs<Real, MC>(pfd, Fu2, Fsf, Fk, Fv, Fg, Fvo, Fgo, lds, wp.lo2);
+                  st = owner;
+                  nval = pfd;
+               }
+               Out[sk0] = pfd;
+            }
+            mirror(Out);
+            return;
+         }
          const uint32_t sx = NODES ? usx : 0u, sw5 = NODES ? (usw & 31u) : 0u, sk0 = usw >> 8;
          Real pfd = Real(0);
 #pragma unroll
@@ -529,7 +591,8 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
    fd_fetch(En, Fqv, Fqg, Fqsf, Fqu2, Fqx1, Fqk);
    for (int m = mf; m <= ml; m++) {
       usx = dsx; usz = dsz; usw = dsw;
-      if constexpr (CG) asm volatile("" : "+s"(usx), "+s"(usz), "+s"(usw));
+      if constexpr (PN) {} // (nothing to hide: the words are constants)
+      else if constexpr (CG) asm volatile("" : "+s"(usx), "+s"(usz), "+s"(usw));
       else {
          rkg = R.kg; rko0 = R.ko0; rko1 = R.ko1; rkb0 = R.kb0; rkb1 = R.kb1; rnbase = R.nbase;
          asm volatile("" : "+s"(rkg), "+s"(rko0), "+s"(rko1), "+s"(rkb0), "+s"(rkb1), "+s"(rnbase), "+s"(usx), "+s"(usz), "+s"(usw));
@@ -542,7 +605,8 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
       // stage 2: u^{n+2}(m-1) from u^{n+1}(m-2 .. m); a ghost plane of the march axis is the plane two further in
       // (opaque again: otherwise every per-cell predicate of stage 1 is kept for stage 2 -- in vector-register lanes, two
       // v_writelane per cell -- instead of being tested again with one scalar instruction)
-      if constexpr (CG) asm volatile("" : "+s"(usx), "+s"(usz), "+s"(usw));
+      if constexpr (PN) {}
+      else if constexpr (CG) asm volatile("" : "+s"(usx), "+s"(usz), "+s"(usw));
       else asm volatile("" : "+s"(rkg), "+s"(rko0), "+s"(rko1), "+s"(rnbase), "+s"(usx), "+s"(usz), "+s"(usw));
       const bool do2 = NS >= 2 && m - 1 >= ms - (NS - 2);
       const bool own_m2 = m - 1 >= ms && m - 1 < me;
@@ -558,7 +622,8 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
       // stage 3 (NS = 3): u^{n+3}(m-2) from u^{n+2}(m-3 .. m-1) -- the last of them stage 2's output just now --, old value u^{n+1}(m-2)
       const bool do3 = NS == 3 && m - 2 >= ms;
       if constexpr (NS == 3) {
-         if constexpr (CG) asm volatile("" : "+s"(usx), "+s"(usz), "+s"(usw));
+         if constexpr (PN) {}
+         else if constexpr (CG) asm volatile("" : "+s"(usx), "+s"(usz), "+s"(usw));
          else asm volatile("" : "+s"(rkg), "+s"(rko0), "+s"(rko1), "+s"(rnbase), "+s"(usx), "+s"(usz), "+s"(usw));
          if (do3) update(std::integral_constant<int, 3>(), m - 2, Xm, Xc, W, Vm, Epp, Y, true, F3v, F3g, F3v, F3g, F3sf, F3u2, F3k, nv3, st3);
       }
@@ -633,7 +698,8 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
 // bound every branch m sat in a block of its own -- compare, jump, reload of the array pointers, wait -- 12 times per fetch, per
 // evaluation and per store.  Slots between the scene's count and MC are loaded and stored back unchanged.
 // SG: the reference GPU engine's safeguarded arithmetic (pf_kernels.h: upd7 / upd_rigid / abc_loss<true>) instead of the C CPU engine's.
-template <typename Real, int DP, bool VEC, bool FAST, bool NODES = true, int MC = 12, bool SG = false, int NS = 2, int GD = 0>
+// PR: the wall profile of the launch's blocks (with GD > 0; 0: their node structure arrives with the block).
+template <typename Real, int DP, bool VEC, bool FAST, bool NODES = true, int MC = 12, bool SG = false, int NS = 2, int GD = 0, int PR = 0>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FAST && !VEC && NS != 3 && sizeof(Real) == 4) ? 2 : 1))) void k_wall2(WallParams<Real> wp, Real a1, Real a2) {
    static_assert(FAST || NODES, "generic blocks have everything");
    const uint4 bd = wp.blk[blockIdx.x];
@@ -651,14 +717,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FAST && !VE
       for (int i = threadIdx.x; i < wp.nmat; i += 64) { lds.beta[i] = wp.beta[i]; lds.M[i] = wp.Mb[i]; }
       __syncthreads();
    }
+   static_assert(PR == 0 || GD > 0, "wall profiles: with constant pencil geometry");
    if constexpr (GD > 0) { // constant pencil geometry: a low-side and a high-side body
       const bool hi = R.kg != 0;
-      if constexpr (VEC) { if (hi) wall_body<Real, DP, 2, FAST, NODES, MC, SG, NS, GD, true>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
-                           else wall_body<Real, DP, 2, FAST, NODES, MC, SG, NS, GD, false>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs); }
-      else if (R.mode == 1) { if (hi) wall_body<Real, DP, 1, FAST, NODES, MC, SG, NS, GD, true>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
-                              else wall_body<Real, DP, 1, FAST, NODES, MC, SG, NS, GD, false>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs); }
-      else { if (hi) wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS, GD, true>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
-             else wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS, GD, false>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs); }
+      if constexpr (VEC) { if (hi) wall_body<Real, DP, 2, FAST, NODES, MC, SG, NS, GD, true, PR>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
+                           else wall_body<Real, DP, 2, FAST, NODES, MC, SG, NS, GD, false, PR>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs); }
+      else if (R.mode == 1) { if (hi) wall_body<Real, DP, 1, FAST, NODES, MC, SG, NS, GD, true, PR>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
+                              else wall_body<Real, DP, 1, FAST, NODES, MC, SG, NS, GD, false, PR>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs); }
+      else { if (hi) wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS, GD, true, PR>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
+             else wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS, GD, false, PR>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs); }
    } else if constexpr (VEC) wall_body<Real, DP, 2, FAST, NODES, MC, SG, NS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
    else if (R.mode == 1) wall_body<Real, DP, 1, FAST, NODES, MC, SG, NS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
    else wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
