@@ -169,6 +169,11 @@ typedef struct pf_timing {
                                and a region's and the bricks' too (no single steps of its planes) */
    int64_t wall_profile;    /* of the regions in wall_three_steps, which run with the node layout of a plain box wall compiled in (pf_wall.h: wall profiles):
                                bit 0 the x / y regions, bit 3 the column strips; 0: the node words are read from the blocks */
+   int64_t wall_uniform_branches; /* of the regions in wall_profile with a frequency-dependent node layer: the branch count their kernels evaluate for every
+                               node alike, without a per-node guard (every material of the scene has that many branches: 1 .. 4, 11 or 12);
+                               0: the guarded form ran (mixed counts, other counts) or no such region */
+   int64_t wall_unread_skipped; /* triples: wall regions (bits as in wall_three_steps) that do not store u^{n+1} of their cells because nothing reads it:
+                               no receiver in their cells, no tile or node that steps singly */
 } pf_timing;
 
 typedef struct pf_engine pf_engine;

@@ -267,6 +267,16 @@ template <typename Real> struct Engine : EngineBase {
    Real *ubx[2] = {nullptr, nullptr};                     // single domains with wall regions: two more node-value buffers beside ub[0..2]
    int wl_geo[4] = {0, 0, 0, 0};                          // per launch group: the box margin all its regions' pencils share (standard geometry, pf_wall.h GD), else 0
    int wl_prof[4] = {0, 0, 0, 0};                         // per launch group: the wall profile all its alike blocks' node words match (pf_wall.h PR), else 0
+   int wl_uni = 0;                                        // the branch count every material of the scene has, where the profiled kernels have a uniform form for it (pf_wall.h UB), else 0
+   unsigned wl_rcv = 0;                                   // launch groups whose regions own a cell that holds a receiver (k_io of step n + 1 reads its u^{n+1})
+   // does launch group gi run the uniform-branch-count bodies in a triple?  ... and leave u^{n+1} of its cells unstored (nothing reads it)?
+   bool wl_uni_group(int gi) const {
+      return sizeof(Real) == 4 && wl_uni > 0 && wl_prof[gi] == 1 && ((gi == 0 && wl_ns3 && wl_geo[0] == 6) || (gi == 3 && wl_ns3z && wl_geo[3] == 16));
+   }
+   bool wl_skip_c(int gi) const {
+      return wl_uni_group(gi) && op.slab_first && op.slab_last && tb_ndirty == 0 && wl_nrest == 0 && !((wl_rcv >> gi) & 1u) &&
+             !(op.debug & (PF_DBG_STORE_UNREAD | PF_DBG_THIRD_STEP_LISTS));
+   }
    int wl_chunk_want[2] = {0, 0};                         // march steps per block the x / y regions' and the column strips' launches aim for (init_walls)
    size_t wl_brk_lds = 0;                                 // dynamic LDS of a brick launch (the largest brick)
    Real *vh1b = nullptr, *gh1b = nullptr;                 // the other half of the double-buffered branch state
@@ -912,6 +922,9 @@ template <typename Real> struct Engine : EngineBase {
       tm.wall_bricks = wl_on ? wl_nbrk : 0;
       tm.wall_three_steps = (wl_on && (tb3 || (tb3_slab && ws_all3))) ? ((wl_ns3 ? 1 : 0) | (wl_ns3z ? 8 : 0) | (wl_xw[0] ? 0x10 : 0) | (wl_xw[1] ? 0x20 : 0)) : 0;
       tm.wall_profile = (((tm.wall_three_steps & 1) && wl_geo[0] == 6 && wl_prof[0]) ? 1 : 0) | (((tm.wall_three_steps & 8) && wl_geo[3] == 16 && wl_prof[3]) ? 8 : 0);
+      tm.wall_uniform_branches = 0; tm.wall_unread_skipped = 0;
+      for (int gi : {0, 3})
+         if (((tm.wall_profile >> gi) & 1) && wl_uni_group(gi)) { tm.wall_uniform_branches = wl_uni; if (wl_skip_c(gi)) tm.wall_unread_skipped |= (int64_t)1 << gi; }
       if (t) *t = tm;
       if (reset) tm = pf_timing{};
       return PF_OK;

@@ -30,7 +30,7 @@
    void free_walls() {
       auto F = [](auto *&p) { if (p) hipFree((void *)p); p = nullptr; };
       F(wl_pen); F(wl_rec); F(wl_rest); F(wl_blk); F(wl_brk); F(wl_binfo); F(wl_blos); F(vh1b); F(gh1b); F(ubx[0]); F(ubx[1]);
-      wl_nbrk = 0; wl_brk_lds = 0; wl_ns3 = wl_ns3z = false;
+      wl_nbrk = 0; wl_brk_lds = 0; wl_ns3 = wl_ns3z = false; wl_uni = 0; wl_rcv = 0;
       for (int &p : wl_prof) p = 0;
       wl_xw[0] = wl_xw[1] = false;
       wl_on = false;
@@ -502,6 +502,25 @@
             if (all) wl_prof[gi] = pr;
          }
       }
+      // Do all materials have the same branch count, one the profiled kernels have a uniform form for (pf_wall.h: fd_regs<..., UNI>: 11 and 12 as
+      // they are, 1 .. 4 through the four-branch kernel; other counts keep the guarded form)?  debug PF_DBG_BRANCH_SELECTS: never
+      wl_uni = 0;
+      {
+         bool uni = sd.Nm > 0 && !(op.debug & PF_DBG_BRANCH_SELECTS);
+         for (int k = 0; k < sd.Nm; k++) uni = uni && sd.Mb[k] == mb_max;
+         if (uni && (mb_max == 11 || mb_max == 12 || (mb_max >= 1 && mb_max <= 4))) wl_uni = mb_max;
+      }
+      // which launch groups own a cell with a receiver in it?  (the others' u^{n+1} need not reach the scratch grid: launch_walls_x)
+      wl_rcv = 0;
+      for (int64_t i = 0; i < Nr; i++) {
+         int64_t ix, iy, iz;
+         decode(sd.out_ixyz[i], ix, iy, iz);
+         for (int r = 0; r < nregs; r++) {
+            int k, lc, m;
+            frame(reg[r], ix, iy, iz, k, lc, m);
+            if (k >= reg[r].ko0 && k < reg[r].ko1 && lc >= reg[r].l0 && lc < reg[r].l1 && m >= reg[r].m0 && m < reg[r].m1) wl_rcv |= 1u << grp[r];
+         }
+      }
       wl_ns3 = ns3; wl_ns3z = ns3z;
       if ((ns3 && wl_grp[0].nblk[1] > 0) || (ns3z && wl_grp[3].nblk[1] > 0)) { // some x / y block is not alike (a room that is no plain box): those regions keep two steps + one
          wl_no_ns3 = true;
@@ -539,6 +558,10 @@
          const WlGroup &g = wl_grp[gi];
          wp.nreg = g.nreg;
          for (int i = 0; i < g.nreg; i++) wp.reg[i] = g.reg[i];
+         // (a triple of a single domain in which nothing steps singly and no receiver sits in the group's cells: nobody reads their u^{n+1}; the
+         // uniform-branch-count bodies test the pointer, the others store always)
+         const bool uni = ns == 3 && wl_uni_group(gi);
+         wp.C = (uni && wl_skip_c(gi)) ? nullptr : C;
          for (int q = 0; q < 3; q++) { // alike blocks, generic blocks, alike blocks without nodes (column strips only)
             if (!g.nblk[q]) continue;
             wp.blk = wl_blk + g.blk0[q];
@@ -566,10 +589,17 @@
             // (wl_geo: every region of the group has the standard pencil geometry of a box with that margin -- the kernel with it compiled in;
             // wl_prof: every alike block of the group has the node words of that wall profile -- the kernel with them compiled in too.  Profile 2 holds
             // no frequency-dependent node, so no branch state moves whatever the scene's branch count: one instantiation, MC = 4)
+            // (wl_uni: every material has that many branches -- the profiled bodies with fd_regs' uniform form; MC = 4 serves the counts 1 .. 4)
+#define PF_WALLU(DPV, VECV, GDV, MCV, UBV, USKV) do { if (q != 0) break; \
+                              if (sg) hipLaunchKernelGGL((pf::k_wall2<Real, DPV, VECV, true, true, MCV, true, 3, GDV, 1, UBV, USKV>), gd, b, 0, st, wp, a1, a2); \
+                              else hipLaunchKernelGGL((pf::k_wall2<Real, DPV, VECV, true, true, MCV, false, 3, GDV, 1, UBV, USKV>), gd, b, 0, st, wp, a1, a2); } while (0)
+#define PF_WALLU_ANY(DPV, VECV, GDV) do { if (wl_uni == 11) PF_WALLU(DPV, VECV, GDV, 12, 11, false); else if (wl_uni == 12) PF_WALLU(DPV, VECV, GDV, 12, 12, false); \
+                              else PF_WALLU(DPV, VECV, GDV, 4, 4, true); } while (0)
             bool profiled = false;
             if constexpr (sizeof(Real) == 4) {
                if (gi == 0 && wl_ns3 && ns == 3 && wl_geo[0] == 6 && wl_prof[0] > 0) {
-                  if (wl_prof[0] == 1) PF_WALL3P(3, 6, 1, false); else PF_WALL3P(3, 6, 2, true);
+                  if (uni) PF_WALLU_ANY(10, false, 6);
+                  else if (wl_prof[0] == 1) PF_WALL3P(3, 6, 1, false); else PF_WALL3P(3, 6, 2, true);
                   profiled = true;
                }
             }
@@ -584,7 +614,8 @@
                      else { if (sg) hipLaunchKernelGGL((pf::k_wall2<Real, 20, true, true, true, MCLO ? 4 : 12, true, 3, GDV, PRV>), gd, b, 0, st, wp, a1, a2); \
                             else hipLaunchKernelGGL((pf::k_wall2<Real, 20, true, true, true, MCLO ? 4 : 12, false, 3, GDV, PRV>), gd, b, 0, st, wp, a1, a2); } } while (0)
 #define PF_WALLZ3(GDV) PF_WALLZ3P(GDV, 0, false)
-                     if (wl_geo[3] == 16 && wl_prof[3] == 1) PF_WALLZ3P(16, 1, false);
+                     if (uni) PF_WALLU_ANY(20, true, 16);
+                     else if (wl_geo[3] == 16 && wl_prof[3] == 1) PF_WALLZ3P(16, 1, false);
                      else if (wl_geo[3] == 16 && wl_prof[3] == 2) PF_WALLZ3P(16, 2, true);
                      else if (wl_geo[3] == 16) PF_WALLZ3(16); else PF_WALLZ3(0);
 #undef PF_WALLZ3P
@@ -596,6 +627,8 @@
             else if (gi == 1) PF_WALL(12, true);
             else if (gi == 2) PF_WALL(16, true);
             else if constexpr (sizeof(Real) == 4) PF_WALL(20, true);
+#undef PF_WALLU_ANY
+#undef PF_WALLU
 #undef PF_WALL3
 #undef PF_WALL3P
 #undef PF_WALL3_N

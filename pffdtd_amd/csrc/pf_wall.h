@@ -121,40 +121,100 @@ template <typename Real> struct WallJobs {
    int32_t li[64 * 8]; // position in the lossy arrays | owner << 30
    uint32_t mask[64];  // pencil cells with a job, per lane
 };
-template <typename Real, int mmax, typename LDS = WallLds<Real>> // (LDS: anything with mq[], beta[], M[] -- pf_brick.h carves its own)
+// UNI bodies (below): every material of the scene has the same branch count, so a node's own count is no per-lane value and the table holds
+// what fd_regs multiplies by, prepared once per block -- per material five rows of 12 branches: 2 bDh, bFh, b, bd, 2 bFh (rows start on 16
+// bytes: whole vectors per LDS read).  2 bDh and 2 bFh are the products fd_regs' expressions form first (`two * q.bDh * v1` parses as
+// (two * q.bDh) * v1), rounded in Real like there: the same bits, subnormals included.
+constexpr int WALL_UROWS = 5, WALL_UROW = 12;
+template <typename Real> struct WallLdsU {
+   alignas(16) Real c[PF_WALL_MAXMAT][WALL_UROWS * WALL_UROW];
+   Real beta[PF_WALL_MAXMAT];
+   template <typename Q> __device__ __forceinline__ void put(int i, const Q &q) { // entry i = material * 12 + branch of the device table
+      const Real two = 2.0;
+      Real *r = c[i / 12] + i % 12;
+      r[0] = two * q.bDh; r[WALL_UROW] = q.bFh; r[2 * WALL_UROW] = q.b; r[3 * WALL_UROW] = q.bd; r[4 * WALL_UROW] = two * q.bFh;
+   }
+};
+// UNI: the scene's materials all have the same number of branches and MB bounds it, so no branch is guarded per lane -- no L.M[k], no
+// compare and three selects per branch --, slots >= MB of the state arrays are neither read nor written, and the coefficients come prepared
+// (WallLdsU).  SKIP: the count is the wave-uniform `nb` <= MB and branches beyond it are skipped by a scalar test (the kernels that move four
+// branch states per node: counts 1 .. 4, one instantiation); else it IS MB.  Same operands in the same order as the select form: the same bits.
+template <typename Real, int mmax, typename LDS = WallLds<Real>, int MB = mmax, bool UNI = false, bool SKIP = false> // (LDS: anything with mq[], beta[], M[] -- pf_brick.h carves its own)
 __device__ __forceinline__ Real fd_regs(Real p, Real u2, Real sf, int32_t k, const Real (&v1)[12], const Real (&g1)[12], Real (&v1o)[12], Real (&g1o)[12],
-                                        const LDS &L, Real lo2) {
-   // mmax = the largest branch count of the scene (uniform).  Branches m >= the node's own count M are computed and thrown away
-   // (selects): a per-lane branch around every m put each LDS read of a coefficient and its wait into a block of its own --
-   // two dozen dependent LDS round trips per node, with one wave per SIMD nothing to hide them.
-   const int M = L.M[k];
-   const Real two = 2.0, one = 1.0;
-   const Real g = lo2 * sf * L.beta[k];
-   MatQuadT<Real> q[12];
+                                        const LDS &L, Real lo2, int nb = MB) {
+   if constexpr (UNI) {
+      static_assert(MB >= 1 && MB <= mmax && mmax <= WALL_UROW, "uniform branch count within the state the kernel moves");
+      typedef typename VecOf<Real>::type vec;
+      constexpr int V = VecOf<Real>::V, NV = (MB + V - 1) / V;
+      const Real two = 2.0, one = 1.0;
+      const Real g = lo2 * sf * L.beta[k];
+      Real cf[WALL_UROWS][NV * V];
+      auto rows = [&](int32_t kk, int r0, int r1) __attribute__((always_inline)) {
+         const vec *cp = (const vec *)L.c[kk];
 #pragma unroll
-   for (int m = 0; m < 12; m++)
-      if (m < mmax) q[m] = L.mq[k * 12 + m];
-   const Real fac = two * lo2 * sf / (one + g);
-   Real u = p;
-   u = (u + g * u2) / (one + g);
+         for (int r = r0; r < r1; r++)
 #pragma unroll
-   for (int m = 0; m < 12; m++) {
-      if (m < mmax) {
-         const Real t = u - fac * (two * q[m].bDh * v1[m] - q[m].bFh * g1[m]);
-         u = (m < M) ? t : u;
+            for (int v = 0; v < NV; v++) {
+               const vec t = cp[r * (WALL_UROW / V) + v];
+#pragma unroll
+               for (int i = 0; i < V; i++) cf[r][v * V + i] = t[i];
+            }
+      };
+      rows(k, 0, 2);
+      const Real fac = two * lo2 * sf / (one + g);
+      Real u = p;
+      u = (u + g * u2) / (one + g);
+#pragma unroll
+      for (int m = 0; m < MB; m++)
+         if (!SKIP || m < nb) u = u - fac * (cf[0][m] * v1[m] - cf[1][m] * g1[m]);
+      const Real du = u - u2;
+      // (the rows of the state update are read HERE: their address is made to wait for du, else all sixty coefficients are fetched up front and
+      // the kernel, one wave per SIMD at the register limit, parks that many more values in the accumulation registers)
+      int32_t k2 = k;
+      asm("" : "+v"(k2) : "v"(du));
+      rows(k2, 2, WALL_UROWS);
+#pragma unroll
+      for (int m = 0; m < MB; m++) {
+         if (!SKIP || m < nb) {
+            const Real v0 = cf[2][m] * du + cf[3][m] * v1[m] - cf[4][m] * g1[m];
+            g1o[m] = g1[m] + (v0 + v1[m]) / two;
+            v1o[m] = v0;
+         } else { g1o[m] = g1[m]; v1o[m] = v1[m]; }
       }
-   }
-   const Real du = u - u2;
+      return u;
+   } else {
+      // mmax = the largest branch count of the scene (uniform).  Branches m >= the node's own count M are computed and thrown away
+      // (selects): a per-lane branch around every m put each LDS read of a coefficient and its wait into a block of its own --
+      // two dozen dependent LDS round trips per node, with one wave per SIMD nothing to hide them.
+      const int M = L.M[k];
+      const Real two = 2.0, one = 1.0;
+      const Real g = lo2 * sf * L.beta[k];
+      MatQuadT<Real> q[12];
 #pragma unroll
-   for (int m = 0; m < 12; m++) {
-      if (m < mmax) {
-         const Real v0 = q[m].b * du + q[m].bd * v1[m] - two * q[m].bFh * g1[m];
-         const Real gn = g1[m] + (v0 + v1[m]) / two;
-         g1o[m] = (m < M) ? gn : g1[m];
-         v1o[m] = (m < M) ? v0 : v1[m];
-      } else { g1o[m] = g1[m]; v1o[m] = v1[m]; }
+      for (int m = 0; m < 12; m++)
+         if (m < mmax) q[m] = L.mq[k * 12 + m];
+      const Real fac = two * lo2 * sf / (one + g);
+      Real u = p;
+      u = (u + g * u2) / (one + g);
+#pragma unroll
+      for (int m = 0; m < 12; m++) {
+         if (m < mmax) {
+            const Real t = u - fac * (two * q[m].bDh * v1[m] - q[m].bFh * g1[m]);
+            u = (m < M) ? t : u;
+         }
+      }
+      const Real du = u - u2;
+#pragma unroll
+      for (int m = 0; m < 12; m++) {
+         if (m < mmax) {
+            const Real v0 = q[m].b * du + q[m].bd * v1[m] - two * q[m].bFh * g1[m];
+            const Real gn = g1[m] + (v0 + v1[m]) / two;
+            g1o[m] = (m < M) ? gn : g1[m];
+            v1o[m] = (m < M) ? v0 : v1[m];
+         } else { g1o[m] = g1[m]; v1o[m] = v1[m]; }
+      }
+      return u;
    }
-   return u;
 }
 
 // Wall profiles (PR > 0; alike blocks of three-step launches with constant pencil geometry, GD > 0): the NODE structure of the block's pencils
@@ -200,9 +260,13 @@ template <int B, int E, typename F> __device__ __forceinline__ void wall_static_
 // PR > 0 (with GD > 0 only): a wall profile, above -- the per-cell node test is decided at compile time, node cells skip the air update, the rigid
 // update runs in line with constant adjacency (the same upd_rigid call, the same operand order: the same bits), the frequency-dependent node's
 // value goes back with one assignment, and the three words are never made opaque.
-template <typename Real, int DP, int MODE, bool FAST, bool NODES, int MC, bool SG, int NS = 2, int GD = 0, bool HI = false, int PR = 0>
+// UB > 0 (bodies with a frequency-dependent wall profile only): the scene's materials all have the same number of branches -- UB of them,
+// or (USK) wp.mmax <= UB of them -- : fd_regs' uniform form, UB slots of branch state per node fetched, rotated and stored, and u^{n+1} of the owned
+// cells is stored only where the host passes a grid for it (wp.C: null when nobody reads it, Engine::launch_walls_x).
+template <typename Real, int DP, int MODE, bool FAST, bool NODES, int MC, bool SG, int NS = 2, int GD = 0, bool HI = false, int PR = 0, int UB = 0, bool USK = false,
+          typename LDS = WallLds<Real>>
 __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const WallRegion &R, const int j, const int c, const Real a1, const Real a2,
-                                          const WallLds<Real> *ldsp, const uint32_t dsx, const uint32_t dsz, const uint32_t dsw, WallJobs<Real> *jobs = nullptr) {
+                                          const LDS *ldsp, const uint32_t dsx, const uint32_t dsz, const uint32_t dsw, WallJobs<Real> *jobs = nullptr) {
    constexpr bool VEC = MODE == 2;
    typedef typename VecOf<Real>::type vec;
    constexpr int V = VecOf<Real>::V;
@@ -228,7 +292,9 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
    const bool eval_lane = lane >= 1 && lane <= 62 && lc <= R.l1 + (NS == 3 ? 1 : 0); // stage 1 is valid (and needed) here
    const int ms = R.m0 + c * R.mchunk, me = min(ms + R.mchunk, R.m1);
    if (ms >= me) return;
-   const WallLds<Real> &lds = *ldsp;
+   const LDS &lds = *ldsp;
+   constexpr int NB = UB > 0 ? UB : MC, NQ = UB > 0 ? UB : 12; // branch-state slots fetched and stored; ... rotated
+   static_assert(UB == 0 || (PR > 0 && NS == 3 && UB <= MC), "uniform branch counts: profiled three-step bodies");
    // Wave-uniform values the loop body branches on.  They are made opaque once per march step (below): left alone, the compiler
    // hoists every uniform predicate derived from them out of the march loop, runs out of scalar registers and spills them into
    // vector-register lanes -- 300-500 v_readlane / v_writelane per step, a fifth of the vector instructions.
@@ -310,7 +376,7 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
          const int32_t li = (int32_t)(E.w >> 8);
 #pragma unroll
          for (int m = 0; m < 12; m++)
-            if (m < MC) { v[m] = wp.sv_in[st_idx(m, li)]; g[m] = wp.sg_in[st_idx(m, li)]; }
+            if (m < NB) { v[m] = wp.sv_in[st_idx(m, li)]; g[m] = wp.sg_in[st_idx(m, li)]; }
          sf = wp.ssaf[li];
          k = wp.mat[li];
          u2 = wp.x2[li];
@@ -371,7 +437,8 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
             if constexpr (sw5 != 0u) { // (cpu_engine.h:290-301, 363-405) the pencils' frequency-dependent node: state in registers
                const bool owner = own_m && own_lane && sk0 >= rko0 && sk0 < rko1;
                if (eval_lane && (STAGE < NS || STAGE == 1 || owner)) {
-                  pfd = fd_regs<Real, MC>(pfd, Fu2, Fsf, Fk, Fv, Fg, Fvo, Fgo, lds, wp.lo2);
+                  if constexpr (UB > 0) pfd = fd_regs<Real, MC, LDS, UB, true, USK>(pfd, Fu2, Fsf, Fk, Fv, Fg, Fvo, Fgo, lds, wp.lo2, USK ? wp.mmax : UB);
+                  else pfd = fd_regs<Real, MC>(pfd, Fu2, Fsf, Fk, Fv, Fg, Fvo, Fgo, lds, wp.lo2);
                   st = owner;
                   nval = pfd;
                }
@@ -415,7 +482,7 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
          if (NODES && sw5 != 0u) { // (cpu_engine.h:290-301, 363-405) the pencils' frequency-dependent node: state in registers
             const bool owner = own_m && own_lane && (int)sk0 >= rko0 && (int)sk0 < rko1;
             if (eval_lane && (STAGE < NS || STAGE == 1 || owner)) { // (all but the last stage: the halo's nodes too, their state private)
-               pfd = fd_regs<Real, MC>(pfd, Fu2, Fsf, Fk, Fv, Fg, Fvo, Fgo, lds, wp.lo2);
+               if constexpr (UB == 0) pfd = fd_regs<Real, MC>(pfd, Fu2, Fsf, Fk, Fv, Fg, Fvo, Fgo, lds, wp.lo2);
                st = owner;
                nval = pfd;
             }
@@ -463,7 +530,7 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
          if (sw5 != 0u) { // (cpu_engine.h:290-301, 363-405) the pencils' frequency-dependent node: state in registers
             const bool owner = own_m && own_lane && (int)sk0 >= rko0 && (int)sk0 < rko1;
             if (eval_lane && (STAGE == 1 || owner)) {
-               pfd = fd_regs<Real, MC>(pfd, Fu2, Fsf, Fk, Fv, Fg, Fvo, Fgo, lds, wp.lo2);
+               if constexpr (UB == 0) pfd = fd_regs<Real, MC>(pfd, Fu2, Fsf, Fk, Fv, Fg, Fvo, Fgo, lds, wp.lo2);
                st = owner;
                nval = pfd;
             }
@@ -500,7 +567,7 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
             Real p = rigid(adj, cc, old, np_, nm, mp, mm, lp, lm);
             const bool owner = own_m && own_lane && k >= rko0 && k < rko1;
             if (prim && (STAGE == 1 || owner)) {
-               p = fd_regs<Real, MC>(p, Fu2, Fsf, Fk, Fv, Fg, Fvo, Fgo, lds, wp.lo2);
+               if constexpr (UB == 0) p = fd_regs<Real, MC>(p, Fu2, Fsf, Fk, Fv, Fg, Fvo, Fgo, lds, wp.lo2);
                st = owner;
                nval = p;
             }
@@ -636,11 +703,12 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
 #pragma unroll
       for (int k = 0; k < DP; k++) { asm volatile("" : "+v"(Bn[k])); asm volatile("" : "+v"(Ac[k])); }
 #pragma unroll
-      for (int q = 0; q < 12; q++) { asm volatile("" : "+v"(Fqv[q])); asm volatile("" : "+v"(Fqg[q])); }
+      for (int q = 0; q < NQ; q++) { asm volatile("" : "+v"(Fqv[q])); asm volatile("" : "+v"(Fqg[q])); }
       asm volatile("" : "+v"(Fqsf), "+v"(Fqu2), "+v"(Fqx1), "+v"(Fqk), "+v"(Eq.x), "+v"(Eq.y), "+v"(Eq.z), "+v"(Eq.w) : : "memory");
       mirror(Bn);
       // the stores of this march step ...
-      if (own_m) store_pencil(wp.C, m, Vc);
+      if constexpr (UB > 0) { if (own_m && wp.C) store_pencil(wp.C, m, Vc); } // (u^{n+1} of the region: only where somebody reads it)
+      else if (own_m) store_pencil(wp.C, m, Vc);
       if (do2 && own_m2) store_pencil(wp.D, m - 1, W);
       if constexpr (NS == 3) { if (do3) store_pencil(wp.E, m - 2, Y); }
       if (st1) wp.o1[li1] = nv1;
@@ -662,7 +730,7 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
             wp.o3[li3] = nv3;
 #pragma unroll
             for (int q = 0; q < 12; q++)
-               if (q < MC) { wp.sv_out[st_idx(q, li3)] = F3v[q]; wp.sg_out[st_idx(q, li3)] = F3g[q]; }
+               if (q < NB) { wp.sv_out[st_idx(q, li3)] = F3v[q]; wp.sg_out[st_idx(q, li3)] = F3g[q]; }
          }
       }
       asm volatile("" : : : "memory");
@@ -670,12 +738,12 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
 #pragma unroll
          for (int k = 0; k < DP; k++) { Xm[k] = Xc[k]; Xc[k] = W[k]; }
 #pragma unroll
-         for (int q = 0; q < 12; q++) { F3v[q] = F2v[q]; F3g[q] = F2g[q]; }
+         for (int q = 0; q < NQ; q++) { F3v[q] = F2v[q]; F3g[q] = F2g[q]; }
          F3sf = F2sf; F3k = F2k; F3u2 = F2n1; // (stage 3's u2b: the node's own u^{n+1}, from its stage 1 two march steps ago)
          F2n1 = nv1;
       }
 #pragma unroll
-      for (int q = 0; q < 12; q++) { F2v[q] = F1v[q]; F2g[q] = F1g[q]; F1v[q] = Fqv[q]; F1g[q] = Fqg[q]; }
+      for (int q = 0; q < NQ; q++) { F2v[q] = F1v[q]; F2g[q] = F1g[q]; F1v[q] = Fqv[q]; F1g[q] = Fqg[q]; }
       F2sf = F1sf; F2u2 = F1x1; F2k = F1k;
       F1sf = Fqsf; F1u2 = Fqu2; F1x1 = Fqx1; F1k = Fqk;
       Epp = Ep; Ep = Ec; Ec = En; En = mask_ent(Eq, m + 2);
@@ -699,20 +767,26 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
 // evaluation and per store.  Slots between the scene's count and MC are loaded and stored back unchanged.
 // SG: the reference GPU engine's safeguarded arithmetic (pf_kernels.h: upd7 / upd_rigid / abc_loss<true>) instead of the C CPU engine's.
 // PR: the wall profile of the launch's blocks (with GD > 0; 0: their node structure arrives with the block).
-template <typename Real, int DP, bool VEC, bool FAST, bool NODES = true, int MC = 12, bool SG = false, int NS = 2, int GD = 0, int PR = 0>
+// UB / USK: the uniform-branch-count bodies (wall_body; PR = 1 only), their coefficient table in LDS prepared here.
+template <typename Real, int DP, bool VEC, bool FAST, bool NODES = true, int MC = 12, bool SG = false, int NS = 2, int GD = 0, int PR = 0, int UB = 0, bool USK = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FAST && !VEC && NS != 3 && sizeof(Real) == 4) ? 2 : 1))) void k_wall2(WallParams<Real> wp, Real a1, Real a2) {
    static_assert(FAST || NODES, "generic blocks have everything");
    const uint4 bd = wp.blk[blockIdx.x];
    const WallRegion R = wp.reg[bd.x & 7u];
    const int j = (int)((bd.x >> 3) & 0x1fffu), c = (int)(bd.x >> 16);
-   __shared__ WallLds<Real> lds;
+   typedef typename std::conditional<(UB > 0), WallLdsU<Real>, WallLds<Real>>::type LDS;
+   __shared__ LDS lds;
    __shared__ typename std::conditional<FAST, int, WallJobs<Real>>::type jobs_mem; // (generic blocks only)
    WallJobs<Real> *jobs = nullptr;
    if constexpr (!FAST) {
       jobs = &jobs_mem;
       jobs->mask[threadIdx.x] = 0u;
    }
-   if (NODES) {
+   if constexpr (UB > 0) {
+      for (int i = threadIdx.x; i < wp.nmat * 12; i += 64) lds.put(i, wp.mq[i]);
+      for (int i = threadIdx.x; i < wp.nmat; i += 64) lds.beta[i] = wp.beta[i];
+      __syncthreads();
+   } else if (NODES) {
       for (int i = threadIdx.x; i < wp.nmat * 12; i += 64) lds.mq[i] = wp.mq[i];
       for (int i = threadIdx.x; i < wp.nmat; i += 64) { lds.beta[i] = wp.beta[i]; lds.M[i] = wp.Mb[i]; }
       __syncthreads();
@@ -720,12 +794,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FAST && !VE
    static_assert(PR == 0 || GD > 0, "wall profiles: with constant pencil geometry");
    if constexpr (GD > 0) { // constant pencil geometry: a low-side and a high-side body
       const bool hi = R.kg != 0;
-      if constexpr (VEC) { if (hi) wall_body<Real, DP, 2, FAST, NODES, MC, SG, NS, GD, true, PR>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
-                           else wall_body<Real, DP, 2, FAST, NODES, MC, SG, NS, GD, false, PR>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs); }
-      else if (R.mode == 1) { if (hi) wall_body<Real, DP, 1, FAST, NODES, MC, SG, NS, GD, true, PR>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
-                              else wall_body<Real, DP, 1, FAST, NODES, MC, SG, NS, GD, false, PR>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs); }
-      else { if (hi) wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS, GD, true, PR>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
-             else wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS, GD, false, PR>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs); }
+      if constexpr (VEC) { if (hi) wall_body<Real, DP, 2, FAST, NODES, MC, SG, NS, GD, true, PR, UB, USK, LDS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
+                           else wall_body<Real, DP, 2, FAST, NODES, MC, SG, NS, GD, false, PR, UB, USK, LDS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs); }
+      else if (R.mode == 1) { if (hi) wall_body<Real, DP, 1, FAST, NODES, MC, SG, NS, GD, true, PR, UB, USK, LDS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
+                              else wall_body<Real, DP, 1, FAST, NODES, MC, SG, NS, GD, false, PR, UB, USK, LDS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs); }
+      else { if (hi) wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS, GD, true, PR, UB, USK, LDS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
+             else wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS, GD, false, PR, UB, USK, LDS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs); }
    } else if constexpr (VEC) wall_body<Real, DP, 2, FAST, NODES, MC, SG, NS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
    else if (R.mode == 1) wall_body<Real, DP, 1, FAST, NODES, MC, SG, NS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
    else wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);

@@ -3,7 +3,9 @@
 
 Cross-compiles a small translation unit that instantiates the kernels (no GPU needed) and prints, per kernel, registers and scratch and,
 per body (one march loop each: x / y regions four -- mode x side --, column strips two), the instructions between the loop's header and
-its back edge.  The count is STATIC: out-of-line paths inside the loop count whether a step runs them or not.
+its back edge.  The count is STATIC: out-of-line paths inside the loop count whether a step runs them or not.  Where the header has them, the
+uniform-branch-count bodies (UB = 11, 12, and 4 with the count as a wave-uniform bound) are listed after the guarded ones; the columns after
+`s_cmp` count what those bodies are about: vector compares (the integer `m < M` guards apart), packed multiplications, LDS accesses by width.
 
   tools/wall_loop_isa.py [--csrc DIR] [--keep FILE.s]
 
@@ -24,15 +26,21 @@ ap.add_argument("--csrc", default=str(ROOT / "pffdtd_amd" / "csrc"))
 ap.add_argument("--keep", default="")
 args = ap.parse_args()
 csrc = Path(args.csrc)
-profiles = "int PR" in (csrc / "pf_wall.h").read_text()  # (wall profiles: a trailing template parameter)
+header = (csrc / "pf_wall.h").read_text()
+profiles = "int PR" in header  # (wall profiles: a trailing template parameter)
+uniform = "int UB" in header   # (uniform branch counts: two more)
 
-# (Real, DP, VEC, FAST, NODES, MC, SG, NS, GD[, PR])
+# (Real, DP, VEC, FAST, NODES, MC, SG, NS, GD[, PR[, UB, USK]])
 kernels = []
 for dp, vec, gd in ((10, "false", 6), (20, "true", 16)):
     kernels.append(f"float, {dp}, {vec}, true, true, 12, false, 3, {gd}")
     if profiles:
         kernels.append(f"float, {dp}, {vec}, true, true, 12, false, 3, {gd}, 1")
         kernels.append(f"float, {dp}, {vec}, true, true, 4, false, 3, {gd}, 2")
+    if uniform:
+        kernels.append(f"float, {dp}, {vec}, true, true, 12, false, 3, {gd}, 1, 11, false")
+        kernels.append(f"float, {dp}, {vec}, true, true, 12, false, 3, {gd}, 1, 12, false")
+        kernels.append(f"float, {dp}, {vec}, true, true, 4, false, 3, {gd}, 1, 4, true")
 src = '#include "pf_wall.h"\n' + "".join(f"template __global__ void pf::k_wall2<{k}>(pf::WallParams<float>, float, float);\n" for k in kernels)
 
 with tempfile.TemporaryDirectory() as d:
@@ -45,7 +53,7 @@ with tempfile.TemporaryDirectory() as d:
         sys.exit(r.stderr[-3000:])
     text = asm.read_text().splitlines()
 
-CLASSES = ("total", "VALU", "SALU", "VMEM", "DS", "v_mov", "accvgpr", "v_cndmask", "s_cselect", "s_cmp")
+CLASSES = ("total", "VALU", "SALU", "VMEM", "DS", "v_mov", "accvgpr", "v_cndmask", "s_cselect", "s_cmp", "v_cmp", "v_cmp_lt_i32", "v_pk_mul_f32", "ds_b128", "ds_b64", "ds_read2")
 
 
 def classify(op):
@@ -58,10 +66,22 @@ def classify(op):
             c.append("v_mov")
         elif op.startswith("v_cndmask"):
             c.append("v_cndmask")
+        elif op.startswith("v_cmp"):
+            c.append("v_cmp")
+            if op.startswith("v_cmp_lt_i32"):
+                c.append("v_cmp_lt_i32")
+        elif op.startswith("v_pk_mul_f32"):
+            c.append("v_pk_mul_f32")
     elif op.startswith(("global_", "buffer_", "flat_", "scratch_")):
         c.append("VMEM")
     elif op.startswith("ds_"):
         c.append("DS")
+        if op.startswith(("ds_read_b128", "ds_write_b128")):
+            c.append("ds_b128")
+        elif op.startswith(("ds_read_b64", "ds_write_b64")):
+            c.append("ds_b64")
+        elif op.startswith(("ds_read2", "ds_write2")):
+            c.append("ds_read2")
     elif op.startswith("s_") and not op.startswith(("s_waitcnt", "s_nop", "s_branch", "s_cbranch", "s_load", "s_barrier", "s_endpgm", "s_sleep", "s_setprio")):
         c.append("SALU")
         if op.startswith("s_cselect"):
@@ -90,7 +110,7 @@ for line in text:
     funcs[cur]["lines"].append(line)
 
 names = subprocess.run(["c++filt"] + list(funcs), capture_output=True, text=True, stdin=subprocess.DEVNULL).stdout.splitlines()
-print("march loop of k_wall2<float, DP, VEC, FAST, NODES, MC, SG, NS, GD" + (", PR>" if profiles else ">") + ", static instruction counts per body")
+print("march loop of k_wall2<float, DP, VEC, FAST, NODES, MC, SG, NS, GD" + (", PR" if profiles else "") + (", UB, USK" if uniform else "") + ">, static instruction counts per body")
 for (mangled, f), name in zip(funcs.items(), names):
     name = re.sub(r"\(.*", "", name).replace("void pf::", "")
     # instructions in order, labels remembered by the index of the instruction that follows them
@@ -124,11 +144,11 @@ for (mangled, f), name in zip(funcs.items(), names):
         else:
             outer.append([b, e])
     outer = [l for l in outer if l[1] - l[0] > 300]
-    print("  " + " ".join(f"{c:>9}" for c in ("body",) + CLASSES))
+    print("  " + " ".join(f"{c:>{max(9, len(c))}}" for c in ("body",) + CLASSES))
     for n, (b, e) in enumerate(sorted(outer)):
         cnt = dict.fromkeys(CLASSES, 0)
         for t in ins[b:e + 1]:
             cnt["total"] += 1
             for c in classify(t[0]):
                 cnt[c] += 1
-        print("  " + " ".join(f"{v:>9}" for v in [n] + [cnt[c] for c in CLASSES]))
+        print("  " + " ".join(f"{v:>{max(9, len(c))}}" for c, v in zip(("body",) + CLASSES, [n] + [cnt[c] for c in CLASSES])))
