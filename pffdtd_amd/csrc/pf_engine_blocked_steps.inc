@@ -111,7 +111,7 @@
       launch_io(sw, n, true, src_range()); // (sources: unless k_tb3<..., SRC> adds them itself, launch_tb3_src)
       // (debug 0x10000, an experiment: the alike blocks too beside k_tb3 instead of before it)
       hipStream_t sa = (beside && (op.debug & 0x10000)) ? s_edge : s;
-      const unsigned g3 = (wl_ns3 ? 0x1u : 0u) | (wl_ns3z ? 0x8u : 0u); // launch groups that take all three steps in this pass
+      const unsigned g3 = wall_g3(); // launch groups that take all three steps in this pass
       if (g3) launch_walls_x(sa, sw, A, B, C, D, E, X2, X1, T1, T2, T3, 3, g3);
       if (0xfu & ~g3) launch_walls_x(sa, sw, A, B, C, D, nullptr, X2, X1, T1, T2, nullptr, 2, 0xfu & ~g3);
       // (the main stream joins the edge stream -- bricks, the single-step tiles' first step, receivers / source: done long before the wall launches

@@ -267,15 +267,17 @@ template <typename Real> struct Engine : EngineBase {
    Real *ubx[2] = {nullptr, nullptr};                     // single domains with wall regions: two more node-value buffers beside ub[0..2]
    int wl_geo[4] = {0, 0, 0, 0};                          // per launch group: the box margin all its regions' pencils share (standard geometry, pf_wall.h GD), else 0
    int wl_prof[4] = {0, 0, 0, 0};                         // per launch group: the wall profile all its alike blocks' node words match (pf_wall.h PR), else 0
-   int wl_uni = 0;                                        // the branch count every material of the scene has, where the profiled kernels have a uniform form for it (pf_wall.h UB), else 0
+   int wl_uni = 0;                                        // the branch count every material of the scene has, else 0 (pf_wall.h UB)
    unsigned wl_rcv = 0;                                   // launch groups whose regions own a cell that holds a receiver (k_io of step n + 1 reads its u^{n+1})
-   // does launch group gi run the uniform-branch-count bodies in a triple?  ... and leave u^{n+1} of its cells unstored (nothing reads it)?
-   bool wl_uni_group(int gi) const {
-      return sizeof(Real) == 4 && wl_uni > 0 && wl_prof[gi] == 1 && ((gi == 0 && wl_ns3 && wl_geo[0] == 6) || (gi == 3 && wl_ns3z && wl_geo[3] == 16));
-   }
-   bool wl_skip_c(int gi) const {
-      return wl_uni_group(gi) && op.slab_first && op.slab_last && tb_ndirty == 0 && wl_nrest == 0 && !((wl_rcv >> gi) & 1u) &&
-             !(op.debug & (PF_DBG_STORE_UNREAD | PF_DBG_THIRD_STEP_LISTS));
+   unsigned wall_g3() const { return (wl_ns3 ? 0x1u : 0u) | (wl_ns3z ? 0x8u : 0u); } // the launch groups that take three steps per pass
+   // Which kernel steps list q of launch group gi by ns steps (pf_wall.h: wall_choose; launch_walls_x runs it, timing() reports it), and with it -- skip_c: u^{n+1} of the group's
+   // cells stays unstored (the uniform-branch-count bodies test the pointer; nobody reads it in a triple of a single domain in which nothing steps singly and no receiver sits in
+   // those cells); second: the x / y regions' second block list, the chunks of a two-step launch on three-step tables (init_walls: blk0b, mchunk2)
+   struct WallChoice { const pf::WallKernel *k; bool skip_c, second; };
+   WallChoice wall_choice(int gi, int q, int ns) const {
+      const pf::WallKernel *k = pf::wall_choose<sizeof(Real) == 8>(gi, q, ns, mb_max, wl_ns3, wl_ns3z, wl_geo[gi], wl_prof[gi], wl_uni);
+      return {k, k && k->ub > 0 && op.slab_first && op.slab_last && tb_ndirty == 0 && wl_nrest == 0 && !((wl_rcv >> gi) & 1u) && !(op.debug & (PF_DBG_STORE_UNREAD | PF_DBG_THIRD_STEP_LISTS)),
+              gi == 0 && q == 0 && wl_ns3 && ns == 2 && wl_grp[0].nblkb > 0};
    }
    int wl_chunk_want[2] = {0, 0};                         // march steps per block the x / y regions' and the column strips' launches aim for (init_walls)
    size_t wl_brk_lds = 0;                                 // dynamic LDS of a brick launch (the largest brick)
@@ -920,11 +922,13 @@ template <typename Real> struct Engine : EngineBase {
       if (wl_on)
          for (const WlGroup &g : wl_grp) { tm.wall_blocks[0] += g.nblk[0] + g.nblk[2]; tm.wall_blocks[1] += g.nblk[1]; }
       tm.wall_bricks = wl_on ? wl_nbrk : 0;
-      tm.wall_three_steps = (wl_on && (tb3 || (tb3_slab && ws_all3))) ? ((wl_ns3 ? 1 : 0) | (wl_ns3z ? 8 : 0) | (wl_xw[0] ? 0x10 : 0) | (wl_xw[1] ? 0x20 : 0)) : 0;
-      tm.wall_profile = (((tm.wall_three_steps & 1) && wl_geo[0] == 6 && wl_prof[0]) ? 1 : 0) | (((tm.wall_three_steps & 8) && wl_geo[3] == 16 && wl_prof[3]) ? 8 : 0);
-      tm.wall_uniform_branches = 0; tm.wall_unread_skipped = 0;
-      for (int gi : {0, 3})
-         if (((tm.wall_profile >> gi) & 1) && wl_uni_group(gi)) { tm.wall_uniform_branches = wl_uni; if (wl_skip_c(gi)) tm.wall_unread_skipped |= (int64_t)1 << gi; }
+      tm.wall_three_steps = (wl_on && (tb3 || (tb3_slab && ws_all3))) ? (int)(wall_g3() | (wl_xw[0] ? 0x10u : 0u) | (wl_xw[1] ? 0x20u : 0u)) : 0;
+      tm.wall_profile = 0; tm.wall_uniform_branches = 0; tm.wall_unread_skipped = 0;
+      for (int gi = 0; gi < 4; gi++) if ((tm.wall_three_steps >> gi) & 1) { // what a triple launches for the alike blocks of these groups
+         const WallChoice c = wall_choice(gi, 0, 3);
+         tm.wall_profile |= (int64_t)(c.k && c.k->pr > 0) << gi; tm.wall_unread_skipped |= (int64_t)c.skip_c << gi;
+         if (c.k && c.k->ub > 0) tm.wall_uniform_branches = wl_uni;
+      }
       if (t) *t = tm;
       if (reset) tm = pf_timing{};
       return PF_OK;

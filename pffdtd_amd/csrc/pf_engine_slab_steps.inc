@@ -50,8 +50,7 @@
             wsT2 = ws_five ? ubx[0] : wsP[1]; wsT3 = ws_five ? ubx[1] : wsP[2];
             unsigned gblk = 0;
             for (int gi = 0; gi < 4; gi++) if (wl_grp[gi].nblk[0] + wl_grp[gi].nblk[1] + wl_grp[gi].nblk[2]) gblk |= 1u << gi;
-            const unsigned g3 = (wl_ns3 ? 0x1u : 0u) | (wl_ns3z ? 0x8u : 0u);
-            ws_all3 = ws_five && wl_nbrk > 0 && gblk != 0 && (gblk & ~g3) == 0;
+            ws_all3 = ws_five && wl_nbrk > 0 && gblk != 0 && (gblk & ~wall_g3()) == 0;
             if ((wl_xw[0] || wl_xw[1]) && !ws_all3) return set_err(PF_ERR_STATE, "a slab's x wall region without three-step regions");
          }
          // an end slab's own x wall (wl_xw): a region and bricks step it three times in phase 0 like a single domain's -- no edge planes on that side

@@ -6,7 +6,7 @@
    // Conditions: 7-point, margins that fit the pencils (8 cells for the strided ones,
    // 12 or 20 for the column strips), no source within one cell of the shell (a source is added BETWEEN the two steps,
    // which a region that keeps u^{n+1} in registers cannot see), fused boundary pass.  Otherwise the single-step shell of
-   // round 2 runs (debug 0x10000000 forces that).
+   // round 2 runs (debug PF_DBG_NO_WALL_REGIONS forces that).
    // The frequency-dependent nodes are renumbered region by region in the order the lanes visit them (march, lane, pencil
    // cell), so that a wave's branch-state accesses are contiguous; the nodes inside the box follow in list order.
    // How a column strip becomes wall regions (0: it does not fit): 1 = one region with 12-cell pencils (strips of up to 10
@@ -46,7 +46,7 @@
       const bool vb = getenv("PFFDTD_VERBOSE") && atoi(getenv("PFFDTD_VERBOSE")) > 1;
 #define WL_NO(why) do { if (vb) fprintf(stderr, "pffdtd_hip: no wall regions (%s)\n", why); return PF_OK; } while (0)
       if (slab ? (!tb2_slab || single) : (!tb2 || !single)) WL_NO("not a pair-stepping engine of this kind");
-      if (fcc || tb_xr.empty() || swz || (op.debug & 0x10000000)) WL_NO("13-point / no box / exchanged axes / switched off");
+      if (fcc || tb_xr.empty() || swz || (op.debug & PF_DBG_NO_WALL_REGIONS)) WL_NO("13-point / no box / exchanged axes / switched off");
       if (Nb > 0 && !fuse_boundary) WL_NO("boundary pass not fused");
       if (Nbl >= ((int64_t)1 << 24) || Nb >= ((int64_t)1 << 31)) WL_NO("too many nodes");
       constexpr int DPS = 8, V = pf::VecOf<Real>::V;
@@ -451,7 +451,7 @@
                const int ms = R.m0 + c * mchunk, me = std::min(ms + mchunk, R.m1);
                const int lc0 = R.l0 - (R.hl - 1) + R.lt * jt, lc1 = std::min(R.l0 + R.lt * jt + R.lt + (R.hl - 2), R.l1 + (R.hl - 2)); // lanes 1 .. 62 within the region
                const int mlo = ms - R.hm, mhi = me + R.hm - 1; // march steps whose pencils the block evaluates
-               bool fast = lc0 >= 2 && lc1 <= NL - 3 && mlo >= 2 && mhi <= NM - 3 && !(op.debug & 0x8000000);
+               bool fast = lc0 >= 2 && lc1 <= NL - 3 && mlo >= 2 && mhi <= NM - 3 && !(op.debug & PF_DBG_WALLS_ALL_GENERIC);
                const uint4 ref = pen[(size_t)(R.pen_off + (int64_t)(mlo - (R.m0 - R.hm)) * R.nlp + (lc0 - (R.l0 - R.hl)))];
                if (__builtin_popcount(ref.x) > 5 || __builtin_popcount(ref.w & 31u) > 1) fast = false;
                for (int m = mlo; m <= mhi && fast; m++) {
@@ -502,14 +502,9 @@
             if (all) wl_prof[gi] = pr;
          }
       }
-      // Do all materials have the same branch count, one the profiled kernels have a uniform form for (pf_wall.h: fd_regs<..., UNI>: 11 and 12 as
-      // they are, 1 .. 4 through the four-branch kernel; other counts keep the guarded form)?  debug PF_DBG_BRANCH_SELECTS: never
-      wl_uni = 0;
-      {
-         bool uni = sd.Nm > 0 && !(op.debug & PF_DBG_BRANCH_SELECTS);
-         for (int k = 0; k < sd.Nm; k++) uni = uni && sd.Mb[k] == mb_max;
-         if (uni && (mb_max == 11 || mb_max == 12 || (mb_max >= 1 && mb_max <= 4))) wl_uni = mb_max;
-      }
+      // Do all materials have the same branch count (pf_wall.h: fd_regs' uniform form, where wall_choose finds a kernel for the count)?  debug PF_DBG_BRANCH_SELECTS: never
+      wl_uni = (sd.Nm > 0 && !(op.debug & PF_DBG_BRANCH_SELECTS)) ? mb_max : 0;
+      for (int k = 0; k < sd.Nm; k++) if (sd.Mb[k] != mb_max) wl_uni = 0;
       // which launch groups own a cell with a receiver in it?  (the others' u^{n+1} need not reach the scratch grid: launch_walls_x)
       wl_rcv = 0;
       for (int64_t i = 0; i < Nr; i++) {
@@ -558,83 +553,13 @@
          const WlGroup &g = wl_grp[gi];
          wp.nreg = g.nreg;
          for (int i = 0; i < g.nreg; i++) wp.reg[i] = g.reg[i];
-         // (a triple of a single domain in which nothing steps singly and no receiver sits in the group's cells: nobody reads their u^{n+1}; the
-         // uniform-branch-count bodies test the pointer, the others store always)
-         const bool uni = ns == 3 && wl_uni_group(gi);
-         wp.C = (uni && wl_skip_c(gi)) ? nullptr : C;
          for (int q = 0; q < 3; q++) { // alike blocks, generic blocks, alike blocks without nodes (column strips only)
             if (!g.nblk[q]) continue;
-            wp.blk = wl_blk + g.blk0[q];
-            dim3 gd(g.nblk[q]), b(64);
-            if (gi == 0 && q == 0 && wl_ns3 && ns == 2 && g.nblkb > 0) { // the two-step launch's own chunks (init_walls)
-               wp.blk = wl_blk + g.blk0b; gd = dim3(g.nblkb);
-               for (int i = 0; i < g.nreg; i++) wp.reg[i].mchunk = g.mchunk2[i];
-            }
-            hipStream_t st = q == 1 ? s_gen : s;
-#define PF_WALL_N(DP, VEC, S, NSV) do { if (q == 2) { if constexpr (VEC) hipLaunchKernelGGL((pf::k_wall2<Real, DP, VEC, true, false, 12, S, NSV>), gd, b, 0, st, wp, a1, a2); } \
-                              else if (mb_max <= 4) { \
-                                 if (q == 0) hipLaunchKernelGGL((pf::k_wall2<Real, DP, VEC, true, true, 4, S, NSV>), gd, b, 0, st, wp, a1, a2); \
-                                 else hipLaunchKernelGGL((pf::k_wall2<Real, DP, VEC, false, true, 4, S, NSV>), gd, b, 0, st, wp, a1, a2); \
-                              } else { \
-                                 if (q == 0) hipLaunchKernelGGL((pf::k_wall2<Real, DP, VEC, true, true, 12, S, NSV>), gd, b, 0, st, wp, a1, a2); \
-                                 else hipLaunchKernelGGL((pf::k_wall2<Real, DP, VEC, false, true, 12, S, NSV>), gd, b, 0, st, wp, a1, a2); } } while (0)
-#define PF_WALL_S(DP, VEC, S) do { if (ns == 1) PF_WALL_N(DP, VEC, S, 1); else PF_WALL_N(DP, VEC, S, 2); } while (0)
-#define PF_WALL(DP, VEC) do { if (sg) PF_WALL_S(DP, VEC, true); else PF_WALL_S(DP, VEC, false); } while (0)
-            // x / y regions with three-step tables (10-cell pencils, alike blocks only: init_walls): three steps, or the two of a run's last pair
-#define PF_WALL3_N(S, NSV, GDV, PRV, MCLO) do { if (q != 0) break; \
-                              if (mb_max <= 4 || MCLO) hipLaunchKernelGGL((pf::k_wall2<Real, 10, false, true, true, 4, S, NSV, GDV, PRV>), gd, b, 0, st, wp, a1, a2); \
-                              else hipLaunchKernelGGL((pf::k_wall2<Real, 10, false, true, true, MCLO ? 4 : 12, S, NSV, GDV, PRV>), gd, b, 0, st, wp, a1, a2); } while (0)
-#define PF_WALL3P(NSV, GDV, PRV, MCLO) do { if (sg) PF_WALL3_N(true, NSV, GDV, PRV, MCLO); else PF_WALL3_N(false, NSV, GDV, PRV, MCLO); } while (0)
-#define PF_WALL3(NSV, GDV) PF_WALL3P(NSV, GDV, 0, false)
-            // (wl_geo: every region of the group has the standard pencil geometry of a box with that margin -- the kernel with it compiled in;
-            // wl_prof: every alike block of the group has the node words of that wall profile -- the kernel with them compiled in too.  Profile 2 holds
-            // no frequency-dependent node, so no branch state moves whatever the scene's branch count: one instantiation, MC = 4)
-            // (wl_uni: every material has that many branches -- the profiled bodies with fd_regs' uniform form; MC = 4 serves the counts 1 .. 4)
-#define PF_WALLU(DPV, VECV, GDV, MCV, UBV, USKV) do { if (q != 0) break; \
-                              if (sg) hipLaunchKernelGGL((pf::k_wall2<Real, DPV, VECV, true, true, MCV, true, 3, GDV, 1, UBV, USKV>), gd, b, 0, st, wp, a1, a2); \
-                              else hipLaunchKernelGGL((pf::k_wall2<Real, DPV, VECV, true, true, MCV, false, 3, GDV, 1, UBV, USKV>), gd, b, 0, st, wp, a1, a2); } while (0)
-#define PF_WALLU_ANY(DPV, VECV, GDV) do { if (wl_uni == 11) PF_WALLU(DPV, VECV, GDV, 12, 11, false); else if (wl_uni == 12) PF_WALLU(DPV, VECV, GDV, 12, 12, false); \
-                              else PF_WALLU(DPV, VECV, GDV, 4, 4, true); } while (0)
-            bool profiled = false;
-            if constexpr (sizeof(Real) == 4) {
-               if (gi == 0 && wl_ns3 && ns == 3 && wl_geo[0] == 6 && wl_prof[0] > 0) {
-                  if (uni) PF_WALLU_ANY(10, false, 6);
-                  else if (wl_prof[0] == 1) PF_WALL3P(3, 6, 1, false); else PF_WALL3P(3, 6, 2, true);
-                  profiled = true;
-               }
-            }
-            if (profiled) {}
-            else if (gi == 0 && wl_ns3) { if (ns == 3) { if (wl_geo[0] == 6) PF_WALL3(3, 6); else PF_WALL3(3, 0); } else if (ns == 2) PF_WALL3(2, 0); }
-            else if (gi == 3 && ns == 3) { // column strips with three-step tables (wl_ns3z; fp32 only)
-               if constexpr (sizeof(Real) == 4) {
-                  if (q == 0) {
-#define PF_WALLZ3P(GDV, PRV, MCLO) do { \
-                     if (mb_max <= 4 || MCLO) { if (sg) hipLaunchKernelGGL((pf::k_wall2<Real, 20, true, true, true, 4, true, 3, GDV, PRV>), gd, b, 0, st, wp, a1, a2); \
-                                        else hipLaunchKernelGGL((pf::k_wall2<Real, 20, true, true, true, 4, false, 3, GDV, PRV>), gd, b, 0, st, wp, a1, a2); } \
-                     else { if (sg) hipLaunchKernelGGL((pf::k_wall2<Real, 20, true, true, true, MCLO ? 4 : 12, true, 3, GDV, PRV>), gd, b, 0, st, wp, a1, a2); \
-                            else hipLaunchKernelGGL((pf::k_wall2<Real, 20, true, true, true, MCLO ? 4 : 12, false, 3, GDV, PRV>), gd, b, 0, st, wp, a1, a2); } } while (0)
-#define PF_WALLZ3(GDV) PF_WALLZ3P(GDV, 0, false)
-                     if (uni) PF_WALLU_ANY(20, true, 16);
-                     else if (wl_geo[3] == 16 && wl_prof[3] == 1) PF_WALLZ3P(16, 1, false);
-                     else if (wl_geo[3] == 16 && wl_prof[3] == 2) PF_WALLZ3P(16, 2, true);
-                     else if (wl_geo[3] == 16) PF_WALLZ3(16); else PF_WALLZ3(0);
-#undef PF_WALLZ3P
-#undef PF_WALLZ3
-                  }
-               }
-            }
-            else if (gi == 0) PF_WALL(8, false);
-            else if (gi == 1) PF_WALL(12, true);
-            else if (gi == 2) PF_WALL(16, true);
-            else if constexpr (sizeof(Real) == 4) PF_WALL(20, true);
-#undef PF_WALLU_ANY
-#undef PF_WALLU
-#undef PF_WALL3
-#undef PF_WALL3P
-#undef PF_WALL3_N
-#undef PF_WALL
-#undef PF_WALL_S
-#undef PF_WALL_N
+            const WallChoice c = wall_choice(gi, q, ns); // (no kernel: nothing to launch -- lists init_walls never fills, pf_wall.h: wall_choices_match_table)
+            wp.C = c.skip_c ? nullptr : C; wp.blk = wl_blk + (c.second ? g.blk0b : g.blk0[q]);
+            for (int i = 0; i < g.nreg; i++) wp.reg[i].mchunk = c.second ? g.mchunk2[i] : g.reg[i].mchunk;
+            const dim3 gd(c.second ? g.nblkb : g.nblk[q]); const hipStream_t st = q == 1 ? s_gen : s; const std::make_integer_sequence<int, pf::WALL_KERNELS<sizeof(Real) == 8>.cap> rows;
+            if (sg) pf::wall_launch<Real, true>(c.k, gd, st, wp, a1, a2, rows); else pf::wall_launch<Real, false>(c.k, gd, st, wp, a1, a2, rows);
          }
       }
    }
@@ -653,11 +578,9 @@
       bp.lo2 = lo2; bp.sl2 = sl2; bp.l = l; bp.nmat = (int)sd.Nm; bp.ns = ns;
       bp.first = op.slab_first; bp.last = op.slab_last;
       const dim3 g((unsigned)wl_nbrk), b(pf::BRICK_T);
-      if (mb_max <= 4) {
-         if (sg) hipLaunchKernelGGL((pf::k_brick<Real, 4, true>), g, b, wl_brk_lds, s, bp, a1, a2);
-         else hipLaunchKernelGGL((pf::k_brick<Real, 4, false>), g, b, wl_brk_lds, s, bp, a1, a2);
-      } else {
-         if (sg) hipLaunchKernelGGL((pf::k_brick<Real, 12, true>), g, b, wl_brk_lds, s, bp, a1, a2);
-         else hipLaunchKernelGGL((pf::k_brick<Real, 12, false>), g, b, wl_brk_lds, s, bp, a1, a2);
-      }
+      const bool lo = pf::wall_mc(mb_max) == pf::WALL_MC[0];
+      if (lo && sg) hipLaunchKernelGGL((pf::k_brick<Real, pf::WALL_MC[0], true>), g, b, wl_brk_lds, s, bp, a1, a2);
+      else if (lo) hipLaunchKernelGGL((pf::k_brick<Real, pf::WALL_MC[0], false>), g, b, wl_brk_lds, s, bp, a1, a2);
+      else if (sg) hipLaunchKernelGGL((pf::k_brick<Real, pf::WALL_MC[1], true>), g, b, wl_brk_lds, s, bp, a1, a2);
+      else hipLaunchKernelGGL((pf::k_brick<Real, pf::WALL_MC[1], false>), g, b, wl_brk_lds, s, bp, a1, a2);
    }

@@ -39,6 +39,7 @@
 // cpu_engine.h:175-194,225-229,234-257,290-301,363-405.
 #pragma once
 #include <type_traits>
+#include <utility>
 #include "pf_kernels.h"
 
 namespace pf {
@@ -222,7 +223,7 @@ __device__ __forceinline__ Real fd_regs(Real p, Real u2, Real sf, int32_t k, con
 // (mode, side, wall depth): two node cells at pencil depths 2 and 3 from the ghost cell -- the outer one rigid, the inner one frequency-dependent
 // (PR = 1) or rigid too (PR = 2: a room without lossy materials) --, each with every neighbour but the one across the wall surface.  In pencil
 // order the first node lacks its neighbour on the +normal side and the second the one on the -normal side, on either side of the grid.  The host
-// launches these bodies only when every block of every region of the launch carries exactly wall_profile_words() (Engine::launch_walls_x).
+// launches these bodies only when every block of every region of the launch carries exactly wall_profile_words() (wall_choose below).
 struct WallNodes { uint32_t x, z, w; }; // node cells; adjacency of the nodes in pencil order, 6 bits each (file order +x -x +y -y +z -z); lossy flags | cell of the frequency-dependent node << 8
 struct WallProfileRow { int outer, inner; bool fd; }; // depths of the two node layers from the ghost cell; is the inner one frequency-dependent?
 constexpr int WALL_NPROF = 2;
@@ -256,13 +257,13 @@ template <int B, int E, typename F> __device__ __forceinline__ void wall_static_
 // cells -- low side (HI = false): ghost cell 0, owned cells 1 .. GD-1, pencil from coordinate 0; high side: ghost cell DP-1, owned cells
 // DP-GD .. DP-2, pencil from N - DP -- and a compile-time constant: the ghost mirror, the owned range of every store, the ABC cell and the load
 // clamps cost no scalar compares and selects per cell and stage any more (x / y regions: -12 % vector, -29 % scalar instructions per march
-// step).  The host launches these bodies only when every region of the launch has that geometry (Engine::launch_walls_x), else GD = 0.
+// step).  The host launches these bodies only when every region of the launch has that geometry (wall_choose below), else GD = 0.
 // PR > 0 (with GD > 0 only): a wall profile, above -- the per-cell node test is decided at compile time, node cells skip the air update, the rigid
 // update runs in line with constant adjacency (the same upd_rigid call, the same operand order: the same bits), the frequency-dependent node's
 // value goes back with one assignment, and the three words are never made opaque.
 // UB > 0 (bodies with a frequency-dependent wall profile only): the scene's materials all have the same number of branches -- UB of them,
 // or (USK) wp.mmax <= UB of them -- : fd_regs' uniform form, UB slots of branch state per node fetched, rotated and stored, and u^{n+1} of the owned
-// cells is stored only where the host passes a grid for it (wp.C: null when nobody reads it, Engine::launch_walls_x).
+// cells is stored only where the host passes a grid for it (wp.C: null when nobody reads it, Engine::wall_choice).
 template <typename Real, int DP, int MODE, bool FAST, bool NODES, int MC, bool SG, int NS = 2, int GD = 0, bool HI = false, int PR = 0, int UB = 0, bool USK = false,
           typename LDS = WallLds<Real>>
 __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const WallRegion &R, const int j, const int c, const Real a1, const Real a2,
@@ -805,4 +806,76 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FAST && !VE
    else wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
 }
 
+// ---------------- which k_wall2 runs: the instantiations (one table), the choice among them, the launch ----------------
+struct WallKernel { int dp = 0; bool vec = false, fast = false, nodes = false; int mc = 0, ns = 0, gd = 0, pr = 0, ub = 0; bool usk = false; }; // k_wall2's template arguments after Real, SG apart (every row exists with both)
+constexpr int WALL_MC[2] = {4, 12}; // the bounds of a scene's largest branch count the kernels exist for (MC of k_wall2 and k_brick), and the one that serves a count:
+constexpr int wall_mc(int mb_max) { return mb_max <= WALL_MC[0] ? WALL_MC[0] : WALL_MC[1]; }
+// What the library instantiates, said here and nowhere else.  Launch groups (Engine::WlGroup): 0 = the x / y regions, strided pencils of 8 cells, 10 with
+// three-step tables; 1 / 2 / 3 = column strips, vector pencils of 12 / 16 / 20 cells (20: fp32 only, and the only strips with three-step tables).
+constexpr int WALL_DP[4] = {8, 12, 16, 20}, WALL_DP3 = 10;
+template <int N> struct WallKernelTable { WallKernel k[N]; int n = 0; static constexpr int cap = N; constexpr void add(const WallKernel &w) { k[n++] = w; } };
+template <bool F64> constexpr auto wall_kernels() {
+   WallKernelTable<F64 ? 28 : 60> t{};
+   for (int gi = 0; gi < (F64 ? 3 : 4); gi++) for (int mc : WALL_MC) {
+      const int dp = WALL_DP[gi], d3 = gi == 0 ? WALL_DP3 : dp, gd = gi == 0 ? 6 : 16; const bool vec = gi != 0, lo = mc == WALL_MC[0];
+      for (int ns = 1; ns <= 2; ns++) { // one or two steps per pass: alike and generic blocks; strips: alike blocks free of nodes too (no branch state moves: one MC)
+         t.add({dp, vec, true, true, mc, ns}); t.add({dp, vec, false, true, mc, ns}); if (vec && !lo) t.add({dp, vec, true, false, mc, ns});
+      }
+      // three-step tables (fp32, alike blocks): three steps with run-time pencil geometry; with that of a box margin of 6 (x / y) / 16 (strips) cells compiled in; on top
+      // of it wall profile 1 with guarded branch counts; x / y regions: the two steps of a run's closing pair on those tables.  Rows with one MC: profile 2 (no
+      // frequency-dependent node: no branch state moves) and profile 1 for the uniform branch counts 1 .. 4; 11 and 12
+      if (F64 || (gi != 0 && gi != 3)) continue;
+      if (gi == 0) t.add({d3, vec, true, true, mc, 2});
+      t.add({d3, vec, true, true, mc, 3}); t.add({d3, vec, true, true, mc, 3, gd}); t.add({d3, vec, true, true, mc, 3, gd, 1});
+      if (lo) { t.add({d3, vec, true, true, mc, 3, gd, 2}); t.add({d3, vec, true, true, mc, 3, gd, 1, mc, true}); }
+      else { t.add({d3, vec, true, true, mc, 3, gd, 1, 11}); t.add({d3, vec, true, true, mc, 3, gd, 1, 12}); }
+   }
+   return t;
+}
+template <bool F64> inline constexpr auto WALL_KERNELS = wall_kernels<F64>();
+// The choice (a row; null: nothing is launched), a function of what Engine::init_walls found: launch group gi, block list q (0 alike, 1 generic, 2 alike and free of nodes), ns
+// steps in this pass; mb_max: the scene's largest branch count; ns3 / ns3z: the x / y regions / the strips have three-step tables; geo, prof, uni: the box margin / wall profile
+// / branch count all the group's pencils / all materials share (0: none).  Of the rows for these pencils, list and steps the one with most of the facts compiled in.
+template <bool F64> constexpr const WallKernel *wall_choose(int gi, int q, int ns, int mb_max, bool ns3, bool ns3z, int geo, int prof, int uni) {
+   constexpr auto &T = WALL_KERNELS<F64>;
+   if (ns == 3 && !(gi == 0 ? ns3 : gi == 3 && ns3z)) return nullptr; // three steps per pass: on three-step tables only
+   const int dp = gi == 0 && ns3 ? WALL_DP3 : WALL_DP[gi];
+   const WallKernel *best = nullptr; int most = -1;
+   for (const WallKernel &r : T.k) {
+      if (r.dp != dp || r.ns != ns || r.fast != (q != 1) || r.nodes != (q != 2)) continue;
+      const bool bound = r.nodes && r.ub == 0 && !(r.pr > 0 && !WALL_PROFILES[r.pr - 1].fd); // is MC the bound of the branch state the row moves?  (else: none moves, or UB is)
+      const int facts = (r.gd > 0) + (r.pr > 0) + (r.ub > 0);
+      if ((r.gd == 0 || r.gd == geo) && (r.pr == 0 || r.pr == prof) && (r.ub == 0 || (uni > 0 && (r.usk ? uni <= r.ub : uni == r.ub))) && (!bound || r.mc == wall_mc(mb_max)) && facts > most) { best = &r; most = facts; }
+   }
+   return best;
+}
+// The chooser over its domain: it answers "none" in just the cases init_walls and the step functions rule out (below), and every row is somebody's answer -- a clause
+// without an instantiation, or an instantiation nobody launches, fails the build.  The facts meet the rows' fields in == and <= only, so each runs over 0 and over v and
+// v + 1 of every value v a row holds (the full ranges: minutes of compile time); rows of one or two steps hold none of geo / prof / uni: these vary in three-step passes.
+template <bool F64> constexpr bool wall_choices_match_table() {
+   constexpr auto &T = WALL_KERNELS<F64>;
+   bool hit[T.cap] = {}, gv[WALL_DP[3] + 2] = {true}, mv[WALL_MC[1] + 2] = {true};
+   for (const WallKernel &r : T.k) { gv[r.gd] = gv[r.gd + 1] = mv[r.mc] = mv[r.mc + 1] = mv[r.ub] = mv[r.ub + 1] = true; }
+   for (int gi = 0; gi < 4; gi++) for (int q = 0; q < 3; q++) for (int ns = 1; ns <= 3; ns++) for (int t = 0; t < 3; t++) { // t: three-step tables for nobody, x / y, strips too
+      // on three-step tables: fp32 only (init_walls: can3); alike blocks only (a generic block makes init_walls start over without the tables, wl_no_ns3; the strips' pencils
+      // all hold nodes); no third step left to take singly.  Else: three steps per pass are for the groups of Engine::wall_g3; every x / y pencil holds nodes (init_walls:
+      // list 2 is the column strips'); 20-cell strips are fp32's (wl_lo_option / wl_hi_option)
+      const bool t3 = gi == 0 ? t > 0 : (gi == 3 && t > 1 && ns == 3);
+      const bool none = t3 ? (F64 || q != 0 || ns == 1) : (ns == 3 || (gi == 0 && q == 2) || (F64 && gi == 3));
+      for (int mb = 0; mb <= WALL_MC[1]; mb++) for (int uni = 0; mv[mb] && uni <= (ns == 3 ? mb : 0); uni += mb ? mb : 1)
+         for (int geo = 0; geo <= (ns == 3 ? WALL_DP[3] : 0); geo++) for (int prof = 0; gv[geo] && prof <= (ns == 3 ? WALL_NPROF : 0); prof++) {
+            const WallKernel *k = wall_choose<F64>(gi, q, ns, mb, t > 0, t > 1, geo, prof, uni);
+            if (none != !k) return false; else if (k) hit[k - T.k] = true;
+         }
+   }
+   for (bool h : hit) if (!h) return false; // (a table that is not full: rows nobody chooses)
+   return true;
+}
+static_assert(wall_choices_match_table<false>(), "k_wall2, fp32: the chooser and the table of instantiations disagree");
+static_assert(wall_choices_match_table<true>(), "k_wall2, fp64: the chooser and the table of instantiations disagree");
+// launches row k of its precision's table (null: nothing)
+template <typename Real, bool SG, int... I> void wall_launch(const WallKernel *k, dim3 grid, hipStream_t st, const WallParams<Real> &wp, Real a1, Real a2, std::integer_sequence<int, I...>) {
+   constexpr auto &T = WALL_KERNELS<sizeof(Real) == 8>;
+   (void)((k == &T.k[I] && (k_wall2<Real, T.k[I].dp, T.k[I].vec, T.k[I].fast, T.k[I].nodes, T.k[I].mc, SG, T.k[I].ns, T.k[I].gd, T.k[I].pr, T.k[I].ub, T.k[I].usk><<<grid, dim3(64), 0, st>>>(wp, a1, a2), true)) || ...);
+}
 } // namespace pf
