@@ -1,4 +1,4 @@
-"""Synthetic shoebox scenes in the reference's on-disk schema.
+"""Synthetic scenes (shoebox: a box room; room: any air mask) in the reference's on-disk schema.
 
 The reference's voxelizer (python/voxelizer/*) is out of scope; this generator produces the same
 four-file contract (sim_consts.h5, vox_out.h5, comms_out.h5, sim_mats.h5) for a box-shaped room so the
@@ -110,16 +110,30 @@ def shoebox(Nx, Ny, Nz, Nt, fcc=False, wall=3, Nm=1, Mb=2, lossy=True, rigid_eve
     isbn = ~np.all(adj, axis=1)
     bn_ixyz = cand[isbn].astype(np.int64)
     adj_bn = adj[isbn]
-    ins = ins[isbn]
-    bx, by, bz = cx[isbn], cy[isbn], cz[isbn]
-    saf_bn = (NN - adj_bn.sum(axis=1)).astype(np.float64)
-    mat_bn = np.full(bn_ixyz.shape, -1, dtype=np.int8)
+    saf_bn, mat_bn = _node_data(adj_bn, ins[isbn], cx[isbn], cy[isbn], cz[isbn], Nm, lossy, rigid_every)
+
+    if src is None:
+        src = (dims // 2).tolist()
+    if rcv is None:
+        rcv = [[w + 2 + (Nx - 2 * w - 5) // 4, w + 2 + (Ny - 2 * w - 5) // 3, w + 2 + (Nz - 2 * w - 5) // 5],
+               [Nx - w - 4 - (Nx - 2 * w - 5) // 5, Ny - w - 4 - (Ny - 2 * w - 5) // 4, w + 2]]
+    return _contract(Nx, Ny, Nz, Nt, fcc, bn_ixyz, adj_bn, mat_bn, saf_bn, Nm, Mb, src, rcv, sig, diff, h, c)
+
+
+def _node_data(adj_bn, ins, bx, by, bz, Nm, lossy, rigid_every):
+    """saf_bn and mat_bn of a boundary list in linear-index order; ins = the node lies on the air side of its surface"""
+    saf_bn = (adj_bn.shape[1] - adj_bn.sum(axis=1)).astype(np.float64)
+    mat_bn = np.full(ins.shape, -1, dtype=np.int8)
     if lossy:
         mat_bn[ins] = ((bx + 2 * by + 3 * bz)[ins] % Nm).astype(np.int8)
         if rigid_every:
             k = np.flatnonzero(ins)[::rigid_every]
             mat_bn[k] = -1
+    return saf_bn, mat_bn
 
+
+def _contract(Nx, Ny, Nz, Nt, fcc, bn_ixyz, adj_bn, mat_bn, saf_bn, Nm, Mb, src, rcv, sig, diff, h, c):
+    """constants, sources / receivers, input signal and materials around a boundary list: the four-file dict"""
     # constants (python/fdtd/sim_consts.py:29-52)
     l = (1.0 if fcc else np.sqrt(1.0 / 3.0)) * 0.999
     l2 = l * l
@@ -142,11 +156,6 @@ def shoebox(Nx, Ny, Nz, Nt, fcc=False, wall=3, Nm=1, Mb=2, lossy=True, rigid_eve
         alpha = np.array(alpha)
         return np.array(nodes, dtype=np.int64), alpha / alpha.sum()
 
-    if src is None:
-        src = (dims // 2).tolist()
-    if rcv is None:
-        rcv = [[w + 2 + (Nx - 2 * w - 5) // 4, w + 2 + (Ny - 2 * w - 5) // 3, w + 2 + (Nz - 2 * w - 5) // 5],
-               [Nx - w - 4 - (Nx - 2 * w - 5) // 5, Ny - w - 4 - (Ny - 2 * w - 5) // 4, w + 2]]
     in_ixyz, in_alpha = corners(src, (0.3, 0.6, 0.2))
     outs = [corners(r, (0.25, 0.5, 0.75)) for r in rcv]
     out_ixyz = np.concatenate([o[0] for o in outs])
@@ -193,6 +202,47 @@ def shoebox(Nx, Ny, Nz, Nt, fcc=False, wall=3, Nm=1, Mb=2, lossy=True, rigid_eve
                      **{f"mat_{k:02d}_DEF": DEF[k] for k in range(Nm)}},
     }
     return sim
+
+
+def room(air, Nt, fcc=False, Nm=1, Mb=2, lossy=True, rigid_every=0, src=None, rcv=None, sig="impulse", diff=True, h=0.05, c=343.2):
+    """shoebox()'s file contract for a room of any shape.  air = boolean (Nx, Ny, Nz), True inside the air domain, False in the outermost
+    two layers of every face (so that boundary nodes stay off the ghost layer, as in shoebox with wall >= 2).  Boundary nodes are built as
+    shoebox builds them: every cell on either side of the surface with a neighbour on the other side, adjacency bit j = "neighbour j lies
+    on my side", air-side nodes lossy with material (x + 2 y + 3 z) mod Nm, solid-side nodes rigid, the list in linear-index order.  For
+    the box mask (and the box with shoebox's blocks cut out) the result is shoebox's, dataset by dataset (tests/test_rooms.py).
+    src and rcv (a cell and a list of cells: their corner nodes carry the signal) are required and must stand in air, off every boundary node."""
+    air = np.asarray(air)
+    assert air.dtype == np.bool_ and air.ndim == 3
+    Nx, Ny, Nz = air.shape
+    if fcc:
+        assert Nx % 2 == 0 and Ny % 2 == 0 and Nz % 2 == 0  # sim_fdtd.py:103-106
+    for a in range(3):
+        for sl in (slice(0, 2), slice(-2, None)):
+            assert not air[(slice(None),) * a + (sl,)].any(), "the outermost two layers of every face are solid"
+    assert src is not None and rcv is not None, "a room has no default source or receivers"
+    offs = FCC_OFFS if fcc else CART_OFFS
+    pad = np.zeros((Nx + 2, Ny + 2, Nz + 2), dtype=np.bool_)
+    pad[1:-1, 1:-1, 1:-1] = air
+
+    def same(j):  # neighbour j of every cell lies on the cell's side of the surface (beyond the grid: solid)
+        dx, dy, dz = offs[j]
+        return pad[1 + dx:1 + dx + Nx, 1 + dy:1 + dy + Ny, 1 + dz:1 + dz + Nz] == air
+
+    isbn = np.zeros(air.shape, dtype=np.bool_)
+    for j in range(offs.shape[0]):
+        isbn |= ~same(j)
+    if fcc:
+        gx, gy, gz = np.ogrid[:Nx, :Ny, :Nz]
+        isbn &= ((gx + gy + gz) % 2) == 0
+    bn_ixyz = np.flatnonzero(isbn).astype(np.int64)
+    adj_bn = np.stack([same(j)[isbn] for j in range(offs.shape[0])], axis=1)
+    bx, by, bz = _ind2sub(bn_ixyz, Ny, Nz)
+    saf_bn, mat_bn = _node_data(adj_bn, air[isbn], bx, by, bz, Nm, lossy, rigid_every)
+    for p in [src] + list(rcv):
+        x, y, z = (int(v) for v in p)
+        assert 0 <= x < Nx - 1 and 0 <= y < Ny - 1 and 0 <= z < Nz - 1, p
+        assert air[x:x + 2, y:y + 2, z:z + 2].all() and not isbn[x:x + 2, y:y + 2, z:z + 2].any(), f"cell {p}: a corner node outside the air or on a boundary node"
+    return _contract(Nx, Ny, Nz, Nt, fcc, bn_ixyz, adj_bn, mat_bn, saf_bn, Nm, Mb, src, rcv, sig, diff, h, c)
 
 
 def rotate_sim(sim, tr=None):

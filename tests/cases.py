@@ -1,7 +1,8 @@
 """Shared parity cases: deterministic synthetic scenes (pffdtd_amd.synth) keyed by name."""
+import rooms
 from pffdtd_amd import sim_data, synth
 
-# name -> (shoebox kwargs, fcc_flag)
+# name -> (shoebox kwargs, fcc_flag); with room=<a name of rooms.SMALL>: synth.room kwargs and the size of its air mask
 CASES = {
     "cart_lossy": (dict(Nx=24, Ny=22, Nz=20, Nt=60, Nm=2, Mb=[2, 3], rigid_every=7), 0),
     "cart_rigid": (dict(Nx=20, Ny=23, Nz=27, Nt=50, lossy=False), 0),
@@ -21,6 +22,13 @@ CASES = {
     "fcc1_lossy": (dict(Nx=24, Ny=22, Nz=20, Nt=60, fcc=True, Nm=2, Mb=[2, 3], rigid_every=5), 1),
     "fcc2_lossy": (dict(Nx=24, Ny=28, Nz=20, Nt=60, fcc=True, Nm=2, Mb=[2, 3], rigid_every=5), 2),
     "fcc2_mb11": (dict(Nx=22, Ny=24, Nz=26, Nt=70, fcc=True, Nm=2, Mb=[11, 4]), 2),
+    # geometry that meets the walls: a pillar from wall to wall, an L-shaped room, a balcony on a wall
+    "cart_pillar": (dict(room="pillar", Nx=30, Ny=28, Nz=26, Nt=60, Nm=2, Mb=[3, 5], src=[8, 12, 14],
+                         rcv=[[10, 14, 12], [20, 10, 8], [16, 5, 14], [4, 4, 4]]), 0),
+    "cart_lroom": (dict(room="lroom", Nx=30, Ny=28, Nz=26, Nt=60, Nm=2, Mb=[2, 11], rigid_every=9, src=[8, 8, 12],
+                        rcv=[[10, 10, 10], [20, 6, 14], [6, 20, 8], [4, 4, 20]]), 0),
+    "fcc2_balcony": (dict(room="balcony", Nx=30, Ny=32, Nz=26, Nt=60, fcc=True, Nm=2, Mb=[2, 3], src=[10, 12, 12],
+                          rcv=[[12, 14, 10], [18, 16, 14], [24, 12, 14], [4, 26, 4]]), 2),
 }
 
 
@@ -28,7 +36,11 @@ def make_sim(name, **override):
     kw, flag = CASES[name]
     kw = dict(kw)
     kw.update(override)
-    sim = synth.shoebox(**kw)
+    if "room" in kw:
+        air = rooms.small_air(kw.pop("room"), (kw.pop("Nx"), kw.pop("Ny"), kw.pop("Nz")))
+        sim = synth.room(air, **kw)
+    else:
+        sim = synth.shoebox(**kw)
     if flag == 2:
         synth.fold_fcc(sim)
         synth.sort_sim(sim)

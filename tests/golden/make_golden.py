@@ -21,7 +21,7 @@ import oracle  # noqa: E402
 from pffdtd_amd import synth  # noqa: E402
 
 GOLDEN_CASES = ["cart_lossy", "cart_mb11", "cart_outside", "cart_outside_oddz", "cart_wall2", "fcc1_lossy",
-                "fcc1_outside", "fcc2_lossy", "fcc2_outside", "fcc2_mb11"]
+                "fcc1_outside", "fcc2_lossy", "fcc2_outside", "fcc2_mb11", "cart_pillar", "cart_lroom", "fcc2_balcony"]
 
 
 def digest(sim):
@@ -34,8 +34,9 @@ def digest(sim):
     return h.hexdigest()
 
 
-def main():
-    for name in GOLDEN_CASES:
+def main(names):
+    assert set(names) <= set(GOLDEN_CASES), names
+    for name in names or GOLDEN_CASES:
         sim = cases.make_sim(name)
         for prec in ("double", "single"):
             with tempfile.TemporaryDirectory() as d:
@@ -47,4 +48,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])  # no argument: every case; names: those only (a new case leaves the other fixtures' files alone)

@@ -55,7 +55,7 @@ def test_oracle_matches_golden(fx):
 
 @pytest.mark.skipif(oracle.ref_binary("double") is None, reason="compiled reference (oracle/_ref) not available")
 @pytest.mark.parametrize("prec", ["double", "single"])
-@pytest.mark.parametrize("name", ["cart_rigid", "cart_oddz", "fcc1_outside", "fcc2_lossy"])
+@pytest.mark.parametrize("name", ["cart_rigid", "cart_oddz", "fcc1_outside", "fcc2_lossy", "cart_pillar", "cart_lroom", "fcc2_balcony"])
 def test_oracle_matches_compiled_reference(name, prec, tmp_path):
     sim = cases.make_sim(name)
     synth.write_folder(sim, tmp_path, gzip=3)  # the reference reads gzip'ed datasets too
