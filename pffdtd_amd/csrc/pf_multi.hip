@@ -11,7 +11,8 @@
 //     event fires -- while the interior planes run on the main stream.  One host barrier per step keeps the event
 //     bookkeeping race-free (events and plane pointers are double-buffered by step parity).
 //   * the lists need not be pre-sorted (the reference refuses unsorted input, gpu_engine.h:688): they are cut by plane
-//     range here and each engine sorts its own.
+//     range and each engine sorts its own.  The cut -- partition and cut_slab, ONE function for both axes -- is host code of its
+//     own, pf_slab_cut.h; which axis a chain is cut along is decided in one place, cut_axis.
 //   * the cut is cost-balanced by default (a wall plane of frequency-dependent nodes costs ~24 interior planes),
 //     PF_MULTI_EVEN_SPLIT gives the reference's Nx/G rule (gpu_engine.h:532-550).
 //   * two transports for the ghost planes (pf_opts.transport / PFFDTD_TRANSPORT): peer copies PULLED by the receiving slab
@@ -21,6 +22,11 @@
 //     patterns) the planes it sent and received and compares them with its neighbours' (pf_multi_info.exchange_verified).
 // A device id may appear several times in the list ("virtual slabs"): the same code path then runs on one GPU, which is
 // how the exchange logic is tested bit for bit on a 1-GPU box (tests/test_hip_multi.py).
+//
+// The order of a step -- begin, stage if host-staged, barrier, exchange by transport, optional checksum / barrier / compare, end -- is
+// written once, `step`, for the slabs a thread drives: one of them (the default) or all (PF_MULTI_ONE_THREAD, a barrier of one).
+// Whose planes fill a slab's ghost planes is said once too, `neighbours`: the slabs beside it, or itself in the cost model of one rank
+// (pf_opts.only_slab).
 //
 // The chain is an object (pf_multi_create / _run / _destroy) with one persistent host thread per slab, so that a host can
 // warm up, time and inspect it (bench.py --gpus N without a process launcher); pf_run_sim_devices is create + run + destroy.
@@ -36,6 +42,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -43,24 +50,14 @@
 
 #include "pffdtd_hip.h"
 #include "pf_debug.h" // pf_opts_x: the public options + the development / test switches
+#include "pf_slab_cut.h" // Slab, partition, cut_slab: the cut itself, host code that needs no device
 
 extern "C" void pf__set_error(const char *msg); // pf_engine.hip (feeds pf_last_error)
 extern "C" int pf__axis_exchange_pays(const pf_simdata *sd, int64_t *counts); // pf_engine.hip
 
-namespace {
+using pf_cut::Slab;
 
-struct Slab {
-   int64_t x0 = 0, x1 = 0;       // owned global planes [x0, x1)
-   int64_t xlo = 0, xhi = 0;     // global planes held locally [xlo, xhi): owned + one ghost plane per interior side
-   bool first = false, last = false;
-   // host arrays of the local pf_simdata
-   std::vector<int64_t> bn, bnl, bna, in, out, out_reorder, out_rows;
-   std::vector<uint16_t> adj;
-   std::vector<int8_t> K, matl, Q;
-   std::vector<uint8_t> ssaf; // Real bytes
-   std::vector<double> in_sigs, u_out;
-   pf_simdata sd{};
-};
+namespace {
 
 int fail(const char *fmt, const char *a = "") {
    char buf[512];
@@ -68,219 +65,20 @@ int fail(const char *fmt, const char *a = "") {
    pf__set_error(buf);
    return PF_ERR_ARG;
 }
+// what pf_slab_cut.h answers (a message, or nullptr: fine) as a pf_status, the message left for pf_last_error
+int cut_status(const char *msg) { return msg ? fail("%s", msg) : PF_OK; }
 
-// owned plane ranges.  even: Nx/G planes each, +1 for the first Nx%G (gpu_engine.h:532-550).  balanced: equal estimated
-// cost (interior plane = 1; a full plane of lossy nodes with 11 branches = 23, of rigid nodes = 5: measured on MI355X -- round 4,
-// 1024^3 as 8 ranks with wall regions in the slabs: 132 interior planes 0.310 ms per step; 119 / 114 planes + an x wall, which stays
-// single steps, 0.337 / 0.329 -- an end rank is mostly fixed cost, 0.0014 ms per plane against 0.0024 inside)
-// along_z: the chain is cut along FILE Z instead (slab engines then store the grid with the x and z axes exchanged: Engine::swz)
-// wall_scale: the wall planes' weights (23 / 5 interior planes per full plane of lossy / rigid nodes, a fit at 1024^2 planes, Mb = 11, fp32) times
-// this factor -- 1: the constants as they are; pf_multi_create MEASURES the factor on the scene at hand (measure_wall_scale, round 5).
-// wall1 (optional): the per-plane wall cost at scale 1, in interior planes.
-int partition(const pf_simdata *sd, int G, bool even, std::vector<int64_t> &cuts, bool along_z = false, double wall_scale = 1.0,
-              std::vector<double> *wall1 = nullptr) {
-   const int64_t Nx = along_z ? sd->Nz : sd->Nx; // planes along the cut axis
-   if (G < 1 || G >= Nx) return fail(along_z ? "need 1 <= number of slabs < Nz: this scene's chain is cut along file z (the reference: ngpus < Nx, gpu_engine.h:682)"
-                                             : "need 1 <= number of slabs < Nx (gpu_engine.h:682)");
-   cuts.assign(G + 1, 0);
-   cuts[G] = Nx;
-   if (G == 1) return PF_OK;
-   if (even) {
-      const int64_t base = Nx / G, rem = Nx % G;
-      for (int g = 0; g < G; g++) cuts[g + 1] = cuts[g] + base + (g < rem ? 1 : 0);
-      return PF_OK;
-   }
-   const int64_t NzNy = along_z ? sd->Ny * sd->Nx : sd->Ny * sd->Nz; // cells per plane of the cut axis
-   std::vector<double> nb(Nx, 0.0), nl(Nx, 0.0);
-   auto plane_of = [&](int64_t ii) { return along_z ? ii % sd->Nz : ii / (sd->Ny * sd->Nz); };
-   for (int64_t i = 0; i < sd->Nb; i++) nb[plane_of(sd->bn_ixyz[i])] += 1.0;
-   for (int64_t i = 0; i < sd->Nbl; i++) nl[plane_of(sd->bnl_ixyz[i])] += 1.0;
-   double mb_scale = 1.0;
-   if (sd->Nbl > 0) {
-      double s = 0;
-      for (int64_t i = 0; i < sd->Nbl; i++) s += (double)sd->Mb[sd->mat_bnl[i]];
-      mb_scale = s / (double)sd->Nbl / 11.0;
-   }
-   std::vector<double> cum(Nx + 1, 0.0);
-   if (wall1) wall1->assign(Nx, 0.0);
-   for (int64_t x = 0; x < Nx; x++) {
-      double c = (x == 0 || x == Nx - 1) ? 0.0 : 1.0; // the global ghost planes are not updated
-      const double wc = (23.0 * mb_scale * nl[x] + 5.0 * (nb[x] - nl[x])) / (double)NzNy;
-      if (wall1) (*wall1)[x] = wc;
-      c += wall_scale * wc;
-      cum[x + 1] = cum[x] + c;
-   }
-   // Round 6: a cut keeps CUT_CLEAR planes from every source.  A slab in triples takes its shell's three steps in one pass, recomputing three
-   // planes of halo beside its box -- which starts four planes from a cut -- from u^{n-1}, u^n alone: a source there (it is added between the
-   // steps) would send the slab back to the two-steps-plus-one shell.  The headline scene's source sits at Nx / 2, exactly where an even
-   // number of ranks cuts.
-   constexpr int64_t CUT_CLEAR = 8;
-   std::vector<int64_t> src_planes;
-   for (int64_t i = 0; i < sd->Ns; i++) src_planes.push_back(plane_of(sd->in_ixyz[i]));
-   auto clear_of_sources = [&](int64_t x) {
-      for (int64_t p : src_planes) if (x > p - CUT_CLEAR && x <= p + CUT_CLEAR) return false; // (planes x-1 | x are the cut's two sides)
-      return true;
-   };
-   auto nudge = [&](int64_t x, int64_t lo, int64_t hi) { // the nearest plane that is clear of every source, if the slab thicknesses allow one
-      if (clear_of_sources(x)) return x;
-      for (int64_t d = 1; d <= 2 * CUT_CLEAR + 2; d++) {
-         if (x - d >= lo && clear_of_sources(x - d)) return x - d;
-         if (x + d <= hi && clear_of_sources(x + d)) return x + d;
-      }
-      return x;
-   };
-   std::vector<char> pinned(G + 1, 0);
-   bool any_pinned = false;
-   for (int g = 1; g < G; g++) {
-      const double target = cum[Nx] * (double)g / (double)G;
-      int64_t x = (int64_t)(std::lower_bound(cum.begin(), cum.end(), target) - cum.begin());
-      const int64_t lo = cuts[g - 1] + 2, hi = Nx - 2 * (int64_t)(G - g);
-      x = std::max(x, lo);            // every slab updates at least one plane
-      x = std::min(x, hi);
-      const int64_t xn = nudge(x, lo, hi);
-      if (xn != x) { pinned[g] = 1; any_pinned = true; }
-      cuts[g] = xn;
-   }
-   // A cut that a source pushed aside leaves its two neighbours up to CUT_CLEAR planes apart (1024^3 as 8 ranks, source at Nx / 2: 125 and
-   // 142 planes where 133 each was meant -- the thick one was the slowest rank of the chain): such a cut stays where it is and the ranks on
-   // either side of it share THEIR part of the cost equally among themselves (four ranks over 504 planes, four over 520).
-   if (any_pinned) {
-      int a = 0;
-      while (a < G) {
-         int b = a + 1;
-         while (b < G && !pinned[b]) b++;
-         const double c0 = cum[cuts[a]], c1 = cum[cuts[b]];
-         for (int g = a + 1; g < b; g++) {
-            const double target = c0 + (c1 - c0) * (double)(g - a) / (double)(b - a);
-            int64_t x = (int64_t)(std::lower_bound(cum.begin(), cum.end(), target) - cum.begin());
-            const int64_t lo = cuts[g - 1] + 2, hi = cuts[b] - 2 * (int64_t)(b - g);
-            x = std::min(std::max(x, lo), hi);
-            cuts[g] = nudge(x, lo, hi);
-         }
-         a = b;
-      }
-   }
-   return PF_OK;
-}
-
-// the same cut along FILE Z: slab g holds the file's columns z in [xlo, xhi) of every row; its local file has Nz = xhi - xlo
-int cut_slab_z(const pf_simdata *sd, int64_t upd0, int64_t upd1, Slab &s) {
-   const int64_t Nz = sd->Nz, Nt = sd->Nt, nzl = s.xhi - s.xlo;
-   const int rb = sd->real_bytes;
-   auto in_upd = [&](int64_t ii) { const int64_t z = ii % Nz; return z >= upd0 && z < upd1; };
-   auto local = [&](int64_t ii) { return (ii / Nz) * nzl + (ii % Nz - s.xlo); };
-   for (int64_t i = 0; i < sd->Nb; i++) {
-      const int64_t ii = sd->bn_ixyz[i];
-      if (!in_upd(ii)) continue;
-      s.bn.push_back(local(ii));
-      s.adj.push_back(sd->adj_bn[i]);
-      if (sd->K_bn) s.K.push_back(sd->K_bn[i]);
-   }
-   for (int64_t i = 0; i < sd->Nbl; i++) {
-      const int64_t ii = sd->bnl_ixyz[i];
-      if (!in_upd(ii)) continue;
-      s.bnl.push_back(local(ii));
-      s.matl.push_back(sd->mat_bnl[i]);
-      const uint8_t *p = (const uint8_t *)sd->ssaf_bnl + (size_t)i * rb;
-      s.ssaf.insert(s.ssaf.end(), p, p + rb);
-   }
-   for (int64_t i = 0; i < sd->Nba; i++) {
-      const int64_t ii = sd->bna_ixyz[i];
-      if (!in_upd(ii)) continue;
-      s.bna.push_back(local(ii));
-      s.Q.push_back(sd->Q_bna[i]);
-   }
-   for (int64_t i = 0; i < sd->Ns; i++) {
-      const int64_t ii = sd->in_ixyz[i];
-      if (!in_upd(ii)) continue;
-      s.in.push_back(local(ii));
-      s.in_sigs.insert(s.in_sigs.end(), sd->in_sigs + i * Nt, sd->in_sigs + (i + 1) * Nt);
-   }
-   for (int64_t i = 0; i < sd->Nr; i++) { // receivers read u1 at any owned column (a global ghost column included)
-      const int64_t ii = sd->out_ixyz[i], z = ii % Nz;
-      if (z < s.x0 || z >= s.x1) continue;
-      s.out.push_back(local(ii));
-      s.out_rows.push_back(i);
-   }
-   s.out_reorder.resize(s.out.size());
-   for (size_t i = 0; i < s.out.size(); i++) s.out_reorder[i] = (int64_t)i;
-   s.u_out.assign(std::max<size_t>(s.out.size() * (size_t)Nt, 1), 0.0);
-   pf_simdata &l = s.sd;
-   l = *sd;
-   l.Nz = nzl;
-   l.Npts = l.Nx * l.Ny * nzl;
-   l.bn_ixyz = s.bn.data(); l.adj_bn = s.adj.data(); l.K_bn = sd->K_bn ? s.K.data() : nullptr; l.Nb = (int64_t)s.bn.size();
-   l.bnl_ixyz = s.bnl.data(); l.mat_bnl = s.matl.data(); l.ssaf_bnl = s.ssaf.data(); l.Nbl = (int64_t)s.bnl.size();
-   l.bna_ixyz = s.bna.data(); l.Q_bna = s.Q.data(); l.Nba = (int64_t)s.bna.size();
-   l.in_ixyz = s.in.data(); l.in_sigs = s.in_sigs.data(); l.Ns = (int64_t)s.in.size();
-   l.out_ixyz = s.out.data(); l.out_reorder = s.out_reorder.data(); l.Nr = (int64_t)s.out.size();
-   l.u_out = s.u_out.data();
-   l.bn_mask = nullptr;
-   return PF_OK;
-}
-
-// local problem of slab g: lists cut to the planes it updates, indices re-based (gpu_engine.h:784-823)
-int cut_slab(const pf_simdata *sd, const std::vector<int64_t> &cuts, int g, int G, Slab &s, bool along_z = false) {
-   const int64_t Nx = along_z ? sd->Nz : sd->Nx, NzNy = sd->Ny * sd->Nz, Nt = sd->Nt;
-   s.x0 = cuts[g]; s.x1 = cuts[g + 1];
-   s.first = g == 0; s.last = g == G - 1;
-   s.xlo = s.x0 - (s.first ? 0 : 1);
-   s.xhi = s.x1 + (s.last ? 0 : 1);
-   const int64_t upd0 = std::max<int64_t>(s.x0, 1), upd1 = std::min<int64_t>(s.x1, Nx - 1);
-   if (upd1 - upd0 < 1) return fail("a slab must own at least one interior plane");
-   if (along_z) return cut_slab_z(sd, upd0, upd1, s);
-   const int64_t off = s.xlo * NzNy, lo = upd0 * NzNy, hi = upd1 * NzNy;
-   const int rb = sd->real_bytes;
-   for (int64_t i = 0; i < sd->Nb; i++) {
-      const int64_t ii = sd->bn_ixyz[i];
-      if (ii < lo || ii >= hi) continue;
-      s.bn.push_back(ii - off);
-      s.adj.push_back(sd->adj_bn[i]);
-      if (sd->K_bn) s.K.push_back(sd->K_bn[i]);
-   }
-   for (int64_t i = 0; i < sd->Nbl; i++) {
-      const int64_t ii = sd->bnl_ixyz[i];
-      if (ii < lo || ii >= hi) continue;
-      s.bnl.push_back(ii - off);
-      s.matl.push_back(sd->mat_bnl[i]);
-      const uint8_t *p = (const uint8_t *)sd->ssaf_bnl + (size_t)i * rb;
-      s.ssaf.insert(s.ssaf.end(), p, p + rb);
-   }
-   for (int64_t i = 0; i < sd->Nba; i++) {
-      const int64_t ii = sd->bna_ixyz[i];
-      if (ii < lo || ii >= hi) continue;
-      s.bna.push_back(ii - off);
-      s.Q.push_back(sd->Q_bna[i]);
-   }
-   for (int64_t i = 0; i < sd->Ns; i++) {
-      const int64_t ii = sd->in_ixyz[i];
-      if (ii < lo || ii >= hi) continue;
-      s.in.push_back(ii - off);
-      s.in_sigs.insert(s.in_sigs.end(), sd->in_sigs + i * Nt, sd->in_sigs + (i + 1) * Nt);
-   }
-   // receivers read u1 at any owned plane (a global ghost plane included, should someone ask for it)
-   for (int64_t i = 0; i < sd->Nr; i++) {
-      const int64_t ii = sd->out_ixyz[i];
-      if (ii < s.x0 * NzNy || ii >= s.x1 * NzNy) continue;
-      s.out.push_back(ii - off);
-      s.out_rows.push_back(i);
-   }
-   s.out_reorder.resize(s.out.size());
-   for (size_t i = 0; i < s.out.size(); i++) s.out_reorder[i] = (int64_t)i;
-   s.u_out.assign(std::max<size_t>(s.out.size() * (size_t)Nt, 1), 0.0);
-   // the ssaf vector must be Real-aligned: std::vector<uint8_t> storage is new[]-aligned (16 B), fine for float/double
-   pf_simdata &l = s.sd;
-   l = *sd;
-   l.Nx = s.xhi - s.xlo;
-   l.Npts = l.Nx * NzNy;
-   l.bn_ixyz = s.bn.data(); l.adj_bn = s.adj.data(); l.K_bn = sd->K_bn ? s.K.data() : nullptr; l.Nb = (int64_t)s.bn.size();
-   l.bnl_ixyz = s.bnl.data(); l.mat_bnl = s.matl.data(); l.ssaf_bnl = s.ssaf.data(); l.Nbl = (int64_t)s.bnl.size();
-   l.bna_ixyz = s.bna.data(); l.Q_bna = s.Q.data(); l.Nba = (int64_t)s.bna.size();
-   l.in_ixyz = s.in.data(); l.in_sigs = s.in_sigs.data(); l.Ns = (int64_t)s.in.size();
-   l.out_ixyz = s.out.data(); l.out_reorder = s.out_reorder.data(); l.Nr = (int64_t)s.out.size();
-   l.u_out = s.u_out.data();
-   l.bn_mask = nullptr; // every engine rebuilds its own mask from its own boundary nodes (as gpu_engine.h:791)
-   return PF_OK;
+// Which axis is a chain of G slabs cut along?  The reference cuts along x (gpu_engine.h:516-662).  Rooms whose engines would rather
+// store the grid with the x and z axes exchanged (+11-15 % on the reference's rooms) are cut along FILE Z
+// instead: the slab axis is then the exchanged storage's plane axis and ghost planes stay contiguous.  PF_MULTI_CUT_Z forces (and is
+// an error where it cannot be honoured), PF_MULTI_CUT_X forbids.
+enum CutAxis { AXIS_X, AXIS_Z, AXIS_ERROR };
+CutAxis cut_axis(const pf_simdata *sd, const pf_opts_x &o, int G) {
+   const int vb = o.air_variant & 255;
+   const bool can = !o.energy && vb != 40 && vb != 41 && !(o.multi_flags & PF_MULTI_FORCE_PAIRS) && G < sd->Nz;
+   if (o.multi_flags & PF_MULTI_CUT_Z) return can ? AXIS_Z : AXIS_ERROR;
+   if ((o.multi_flags & PF_MULTI_CUT_X) || (o.debug & PF_DBG_SWZ_OFF) || o.layout == PF_LAYOUT_FILE || !can || (sd->Nz - 2) / G < 16) return AXIS_X;
+   return pf__axis_exchange_pays(sd, nullptr) != 0 ? AXIS_Z : AXIS_X;
 }
 
 // ---- RCCL, loaded on demand (ncclSend / ncclRecv over xGMI as the second transport; gpu_engine.h:1086-1126 is the
@@ -549,50 +347,60 @@ void create_slab(Shared &S, int g) {
 // PFFDTD_RCCL_INIT_TIMEOUT_S (60) seconds -- host-staged copies through pinned bounce buffers: slower, but it needs nothing from
 // the driver beyond device <-> pinned-host copies, so a first contact with a new multi-GPU box cannot end without a run.  An
 // EXPLICITLY requested transport that is not available is an error, never silently replaced.
-int init_rccl(Shared &S, bool all_same, std::string &why) {
-   std::lock_guard<std::mutex> lk(g_rccl_mu);
-   if (S.faults & 2) { why = "RCCL switched off by the test switch `test_faults` (csrc/pf_debug.h)"; return PF_ERR_ARG; }
-   if (!g_rccl.load(why)) return PF_ERR_ARG;
-   S.comm.assign(S.G, nullptr);
-   S.rank.assign(S.G, 0);
-   S.rccl_self = all_same && S.G > 1;
-   // RCCL greets with a version banner on STDOUT when NCCL_DEBUG asks for one; a host that prints machine-readable results
-   // there (bench.py: one JSON line) must not find it in between: stdout points at stderr while the communicators are made
-   // (process-wide and not thread-safe: another thread of the host writing to stdout in this window lands on stderr; chains
-   // are created from one thread, before the time loop)
+//
+// Communicators are made through rccl_guarded, here and in pf_rccl_comm_create: `make(*job)` runs on a helper thread, because a
+// rendezvous that never completes (seen on mis-configured boxes) must not hang the caller; after PFFDTD_RCCL_INIT_TIMEOUT_S the helper
+// is abandoned.  It therefore owns nothing but heap state of its own: `job` (shared) and a captureless `make`.  RCCL greets with a
+// version banner on STDOUT when NCCL_DEBUG asks for one; a host that prints machine-readable results there (bench.py: one JSON line)
+// must not find it in between: stdout points at stderr meanwhile (process-wide and not thread-safe: another thread of the host writing
+// to stdout in this window lands on stderr; chains are created from one thread, before the time loop).
+// what: the call as the messages name it.  Returns PF_OK, or PF_ERR_HIP with `why` (timed out, or RCCL's own error).
+template <class Job, class Make>
+int rccl_guarded(const std::shared_ptr<Job> &job, Make make, const char *what, std::string &why) {
+   struct Wait { std::mutex mu; std::condition_variable cv; bool done = false; ncclResult_t r = ncclSuccess; };
+   auto w = std::make_shared<Wait>();
    fflush(stdout);
    const int saved_out = dup(1);
    if (saved_out >= 0) dup2(2, 1);
-   // the communicators are made on a helper thread: a rendezvous that never completes (seen on mis-configured boxes) must not
-   // hang the caller.  After the timeout the helper is abandoned (it holds only heap state of its own).
-   struct Job { std::mutex mu; std::condition_variable cv; bool done = false; ncclResult_t r = ncclSuccess; std::vector<ncclComm_t> comm; std::vector<int> dev; bool self = false; int only = -1; };
-   auto job = std::make_shared<Job>();
-   job->comm.assign(S.G, nullptr); job->dev = S.dev; job->self = S.rccl_self; job->only = S.only;
-   std::thread([job] {
-      ncclResult_t r = ncclSuccess;
-      const int G = (int)job->dev.size();
-      if (job->self) {
-         // virtual slabs: slab g's communicator has ONE rank (the device); its exchange sends the neighbour's plane -- same
-         // device, directly addressable -- to itself.  Group semantics, stream ordering and error paths as on a real chain.
-         for (int g = 0; g < G && r == ncclSuccess; g++) { if (job->only >= 0 && g != job->only) continue; const int d = job->dev[g]; r = g_rccl.CommInitAll(&job->comm[g], 1, &d); }
-      } else r = g_rccl.CommInitAll(job->comm.data(), G, job->dev.data()); // one clique over the chain's devices, rank g = slab g
-      { std::lock_guard<std::mutex> l2(job->mu); job->r = r; job->done = true; }
-      job->cv.notify_all();
+   std::thread([job, w, make] {
+      const ncclResult_t r = make(*job);
+      { std::lock_guard<std::mutex> l2(w->mu); w->r = r; w->done = true; }
+      w->cv.notify_all();
    }).detach();
    double tmo = 60.0;
    if (const char *ev = getenv("PFFDTD_RCCL_INIT_TIMEOUT_S")) { const double v = atof(ev); if (v > 0) tmo = v; }
    bool finished;
-   { std::unique_lock<std::mutex> l2(job->mu); finished = job->cv.wait_for(l2, std::chrono::duration<double>(tmo), [&] { return job->done; }); }
+   { std::unique_lock<std::mutex> l2(w->mu); finished = w->cv.wait_for(l2, std::chrono::duration<double>(tmo), [&] { return w->done; }); }
    if (saved_out >= 0) { fflush(stdout); dup2(saved_out, 1); close(saved_out); }
-   if (!finished) { char b[160]; snprintf(b, sizeof b, "ncclCommInitAll over %d device(s) did not return within %.0f s", S.rccl_self ? 1 : S.G, tmo); why = b; S.comm.clear(); return PF_ERR_HIP; }
-   if (job->r != ncclSuccess) {
-      char b[384];
-      snprintf(b, sizeof b, "ncclCommInitAll over %d device(s) failed: %s", S.rccl_self ? 1 : S.G, g_rccl.GetErrorString(job->r));
-      why = b;
-      for (auto &c : job->comm) if (c) { g_rccl.CommDestroy(c); c = nullptr; }
-      S.comm.clear();
-      return PF_ERR_HIP;
-   }
+   char b[384];
+   if (!finished) snprintf(b, sizeof b, "%s did not return within %.0f s", what, tmo);
+   else if (w->r != ncclSuccess) snprintf(b, sizeof b, "%s failed: %s", what, g_rccl.GetErrorString(w->r));
+   else return PF_OK;
+   why = b;
+   return PF_ERR_HIP;
+}
+int init_rccl(Shared &S, bool all_same, std::string &why) {
+   std::lock_guard<std::mutex> lk(g_rccl_mu);
+   if (S.faults & 2) { why = "RCCL switched off by the test switch `test_faults` (csrc/pf_debug.h)"; return PF_ERR_ARG; }
+   if (!g_rccl.load(why)) return PF_ERR_ARG;
+   S.rank.assign(S.G, 0);
+   S.rccl_self = all_same && S.G > 1;
+   struct Job { std::vector<ncclComm_t> comm; std::vector<int> dev; bool self = false; int only = -1; };
+   auto job = std::make_shared<Job>();
+   job->comm.assign(S.G, nullptr); job->dev = S.dev; job->self = S.rccl_self; job->only = S.only;
+   char what[64];
+   snprintf(what, sizeof what, "ncclCommInitAll over %d device(s)", S.rccl_self ? 1 : S.G);
+   const int rc = rccl_guarded(job, [](Job &j) {
+      const int G = (int)j.dev.size();
+      if (!j.self) return g_rccl.CommInitAll(j.comm.data(), G, j.dev.data()); // one clique over the chain's devices, rank g = slab g
+      // virtual slabs: slab g's communicator has ONE rank (the device); its exchange sends the neighbour's plane -- same
+      // device, directly addressable -- to itself.  Group semantics, stream ordering and error paths as on a real chain.
+      ncclResult_t r = ncclSuccess;
+      for (int g = 0; g < G && r == ncclSuccess; g++) { if (j.only >= 0 && g != j.only) continue; const int d = j.dev[g]; r = g_rccl.CommInitAll(&j.comm[g], 1, &d); }
+      if (r != ncclSuccess) for (auto &c : j.comm) if (c) { g_rccl.CommDestroy(c); c = nullptr; } // (the ones made before the one that failed)
+      return r;
+   }, what, why);
+   if (rc != PF_OK) return rc;
    S.comm = job->comm;
    if (!S.rccl_self) for (int g = 0; g < S.G; g++) S.rank[g] = g;
    return PF_OK;
@@ -647,6 +455,15 @@ int choose_transport(Shared &S, int requested) {
 }
 
 // ---- the phases of one step of slab g ----
+// Whose planes fill slab g's ghost planes: the LAST owned plane of slab lo goes into its plane 0, the FIRST owned plane of slab hi
+// into its last plane (-1: the grid's own end, nothing to fill).  g - 1 and g + 1 -- or, in the cost model of one rank
+// (pf_opts.only_slab), g itself: its own edge planes stand in for the neighbours'.  The relation is symmetric: the same two slabs are
+// the ones that read g's planes.
+struct Neighbours { int lo, hi; };
+Neighbours neighbours(const Shared &S, int g) {
+   const bool self = S.only >= 0;
+   return {g > 0 ? (self ? g : g - 1) : -1, g < S.G - 1 ? (self ? g : g + 1) : -1};
+}
 // A: enqueue the split-phase step, publish the planes to exchange and the event "my edge planes of step n are computed"
 void phase_begin(Shared &S, int g, int64_t n) {
    if (S.err.load()) return;
@@ -668,53 +485,39 @@ void phase_pull(Shared &S, int g, int64_t n) {
       if (e != hipSuccess) S.set_error(PF_ERR_HIP, hipGetErrorString(e));
    };
    if (S.drop_step >= 0 && g == 1 && n == S.drop_step) return; // (test hook: the self-check must notice)
-   if (S.only >= 0) { // (cost model of one rank: its own edge planes stand in for the neighbours')
-      if (g > 0) pull(g, S.recv_lo[k][g], S.send_hi[k][g]);
-      if (g < S.G - 1) pull(g, S.recv_hi[k][g], S.send_lo[k][g]);
-      return;
-   }
-   if (g > 0) pull(g - 1, S.recv_lo[k][g], S.send_hi[k][g - 1]);         // left neighbour's last owned plane -> my plane 0
-   if (g < S.G - 1) pull(g + 1, S.recv_hi[k][g], S.send_lo[k][g + 1]);   // right neighbour's first owned plane -> my last plane
+   const Neighbours q = neighbours(S, g);
+   if (q.lo >= 0) pull(q.lo, S.recv_lo[k][g], S.send_hi[k][q.lo]); // left neighbour's last owned plane -> my plane 0
+   if (q.hi >= 0) pull(q.hi, S.recv_hi[k][g], S.send_lo[k][q.hi]); // right neighbour's first owned plane -> my last plane
 }
-// B, RCCL: slab g SENDS its two edge planes and RECEIVES its two ghost planes, all four operations in one group on its edge
-// stream (ordered after its edge kernels: the sources are complete, and the last readers of the ghost planes are done).
-// grouped: the caller has opened an ncclGroupStart that spans several slabs (one-thread mode: one host thread must not block
-// in the group end of one slab before the matching operations of its neighbour are issued).
-void phase_rccl(Shared &S, int g, int64_t n, bool grouped) {
+// B, RCCL: slab g SENDS two edge planes and RECEIVES its two ghost planes on its edge stream (ordered after its edge kernels: the
+// sources are complete, and the last readers of the ghost planes are done), inside the group that `step` has opened.
+// Over a clique (rank g = slab g) it sends its OWN planes to its neighbours' ranks.  With 1-rank communicators (virtual slabs: every
+// rank[] is 0) the NEIGHBOUR's plane -- same device, directly addressable -- goes through RCCL to itself, after the neighbour's edge event.
+void phase_rccl(Shared &S, int g, int64_t n) {
    const int k = (int)(n & 1);
    const size_t nb = S.plane_bytes;
-   if (S.rccl_self) {
-      // 1-rank communicator: the neighbour's plane goes through RCCL to myself (after the neighbour's edge event)
-      const int ql = S.only >= 0 ? g : g - 1, qh = S.only >= 0 ? g : g + 1; // (cost model of one rank: its own planes)
-      for (int q : {ql, qh})
-         if (q >= 0 && q < S.G && hipStreamWaitEvent(S.edge[g], S.ev[k][q], 0) != hipSuccess) { S.set_error(PF_ERR_HIP, "hipStreamWaitEvent failed"); return; }
-      if (!grouped) NCHK(g, g_rccl.GroupStart());
-      if (g > 0) { NCHK(g, g_rccl.Send(S.send_hi[k][ql], nb, ncclInt8, 0, S.comm[g], S.edge[g])); NCHK(g, g_rccl.Recv(S.recv_lo[k][g], nb, ncclInt8, 0, S.comm[g], S.edge[g])); }
-      if (g < S.G - 1) { NCHK(g, g_rccl.Send(S.send_lo[k][qh], nb, ncclInt8, 0, S.comm[g], S.edge[g])); NCHK(g, g_rccl.Recv(S.recv_hi[k][g], nb, ncclInt8, 0, S.comm[g], S.edge[g])); }
-      if (!grouped) NCHK(g, g_rccl.GroupEnd());
-      return;
+   const Neighbours q = neighbours(S, g);
+   if (S.rccl_self)
+      for (int p : {q.lo, q.hi})
+         if (p >= 0 && hipStreamWaitEvent(S.edge[g], S.ev[k][p], 0) != hipSuccess) { S.set_error(PF_ERR_HIP, "hipStreamWaitEvent failed"); return; }
+   if (q.lo >= 0) {
+      NCHK(g, g_rccl.Send(S.rccl_self ? S.send_hi[k][q.lo] : S.send_lo[k][g], nb, ncclInt8, S.rank[q.lo], S.comm[g], S.edge[g]));
+      NCHK(g, g_rccl.Recv(S.recv_lo[k][g], nb, ncclInt8, S.rank[q.lo], S.comm[g], S.edge[g]));
    }
-   if (!grouped) NCHK(g, g_rccl.GroupStart());
-   if (g > 0) {
-      NCHK(g, g_rccl.Send(S.send_lo[k][g], nb, ncclInt8, S.rank[g - 1], S.comm[g], S.edge[g]));
-      NCHK(g, g_rccl.Recv(S.recv_lo[k][g], nb, ncclInt8, S.rank[g - 1], S.comm[g], S.edge[g]));
+   if (q.hi >= 0) {
+      NCHK(g, g_rccl.Send(S.rccl_self ? S.send_lo[k][q.hi] : S.send_hi[k][g], nb, ncclInt8, S.rank[q.hi], S.comm[g], S.edge[g]));
+      NCHK(g, g_rccl.Recv(S.recv_hi[k][g], nb, ncclInt8, S.rank[q.hi], S.comm[g], S.edge[g]));
    }
-   if (g < S.G - 1) {
-      NCHK(g, g_rccl.Send(S.send_hi[k][g], nb, ncclInt8, S.rank[g + 1], S.comm[g], S.edge[g]));
-      NCHK(g, g_rccl.Recv(S.recv_hi[k][g], nb, ncclInt8, S.rank[g + 1], S.comm[g], S.edge[g]));
-   }
-   if (!grouped) NCHK(g, g_rccl.GroupEnd());
 }
 // host-staged, part 1 (sender, right after its edge event): my two edge planes -> my pinned buffer, on my edge stream.  The
 // buffer of this parity was last read two steps ago: its readers' copies must be complete (host wait, normally long over).
 void phase_stage(Shared &S, int g, int64_t n) {
    if (S.err.load()) return;
    const int k = (int)(n & 1);
+   const Neighbours q = neighbours(S, g);
    if (S.steps_done[g] >= 2)
-      for (int nb : {g - 1, g + 1}) {
-         if (S.only >= 0) nb = g;
-         if (nb >= 0 && nb < S.G) MCHK(g, hipEventSynchronize(S.ev_h2d[k][nb]));
-      }
+      for (int nb : {q.lo, q.hi})
+         if (nb >= 0) MCHK(g, hipEventSynchronize(S.ev_h2d[k][nb]));
    uint8_t *hb = (uint8_t *)S.hstage[k][g];
    MCHK(g, hipMemcpyAsync(hb, S.send_lo[k][g], S.plane_bytes, hipMemcpyDeviceToHost, S.edge[g]));
    MCHK(g, hipMemcpyAsync(hb + S.plane_bytes, S.send_hi[k][g], S.plane_bytes, hipMemcpyDeviceToHost, S.edge[g]));
@@ -725,14 +528,14 @@ void phase_stage(Shared &S, int g, int64_t n) {
 void phase_unstage(Shared &S, int g, int64_t n) {
    const int k = (int)(n & 1);
    if (S.drop_step >= 0 && g == 1 && n == S.drop_step) { MCHK(g, hipEventRecord(S.ev_h2d[k][g], S.edge[g])); return; } // (test hook: the self-check must notice)
-   const int ql = S.only >= 0 ? g : g - 1, qh = S.only >= 0 ? g : g + 1; // (cost model of one rank: its own planes)
-   if (g > 0) {
-      MCHK(g, hipEventSynchronize(S.ev_d2h[k][ql]));
-      MCHK(g, hipMemcpyAsync(S.recv_lo[k][g], (const uint8_t *)S.hstage[k][ql] + S.plane_bytes, S.plane_bytes, hipMemcpyHostToDevice, S.edge[g])); // left neighbour's LAST owned plane
+   const Neighbours q = neighbours(S, g);
+   if (q.lo >= 0) {
+      MCHK(g, hipEventSynchronize(S.ev_d2h[k][q.lo]));
+      MCHK(g, hipMemcpyAsync(S.recv_lo[k][g], (const uint8_t *)S.hstage[k][q.lo] + S.plane_bytes, S.plane_bytes, hipMemcpyHostToDevice, S.edge[g])); // left neighbour's LAST owned plane
    }
-   if (g < S.G - 1) {
-      MCHK(g, hipEventSynchronize(S.ev_d2h[k][qh]));
-      MCHK(g, hipMemcpyAsync(S.recv_hi[k][g], (const uint8_t *)S.hstage[k][qh], S.plane_bytes, hipMemcpyHostToDevice, S.edge[g]));                 // right neighbour's FIRST owned plane
+   if (q.hi >= 0) {
+      MCHK(g, hipEventSynchronize(S.ev_d2h[k][q.hi]));
+      MCHK(g, hipMemcpyAsync(S.recv_hi[k][g], (const uint8_t *)S.hstage[k][q.hi], S.plane_bytes, hipMemcpyHostToDevice, S.edge[g]));                 // right neighbour's FIRST owned plane
    }
    MCHK(g, hipEventRecord(S.ev_h2d[k][g], S.edge[g]));
 }
@@ -790,29 +593,47 @@ void destroy_slab(Shared &S, int g) {
    }
 }
 
-// steps [n0, n0+ns) of slab g (its own host thread); returns when its streams have drained and its receivers are flushed
-void run_slab(Shared &S, int g, int &local, int64_t n0, int64_t ns) {
-   bool stop = S.err.load() != 0;
-   for (int64_t n = n0; n < n0 + ns && !stop; n++) {
-      hipSetDevice(S.dev[g]);
-      const bool verify = S.steps_done[g] < S.verify_n; // the same decision in every thread: all slabs have done the same steps
+// B by the chain's transport.  RCCL: ONE group around the sends and receives of all the slabs this thread drives -- it must not block
+// in the group end of one slab before the matching operations of its neighbour are issued.
+void rccl_group(Shared &S, int g, bool open) { NCHK(g, open ? g_rccl.GroupStart() : g_rccl.GroupEnd()); }
+void exchange(Shared &S, int g, int64_t n) {
+   if (S.transport == TR_RCCL) phase_rccl(S, g, n);
+   else if (S.transport == TR_HOST) phase_unstage(S, g, n);
+   else phase_pull(S, g, n);
+}
+
+// Step n of the slabs [g0, g1) that the calling thread drives: ONE slab of a chain with a host thread per slab, which meets the others
+// at the barrier, or ALL of them (PF_MULTI_ONE_THREAD) -- the barrier then has one party and the loops over the slabs do the meeting.
+// Returns true when the chain has to stop (an error is up, or the watchdog fired).
+bool step(Shared &S, int g0, int g1, int &local, int64_t n) {
+   int cur = -1;
+   auto use = [&](int g) { if (g != cur) { hipSetDevice(S.dev[g]); cur = g; } }; // (one call per step for a thread with one slab)
+   const bool verify = S.steps_done[g0] < S.verify_n; // the same decision in every thread: all slabs have done the same steps
+   for (int g = g0; g < g1; g++) {
+      use(g);
       phase_begin(S, g, n);
       if (S.transport == TR_HOST) phase_stage(S, g, n);
       if ((S.faults & 4) && g == 1 && S.steps_done[g] == 3) // (test hook: this slab's thread hangs; the watchdog of the others must turn that into an error)
          std::this_thread::sleep_for(std::chrono::duration<double>(3.0 * S.bar_timeout + 1.0));
-      stop = S.bar.wait(local, S.err, S.bar_timeout); // every slab's edge event of step n is recorded, its plane pointers published
-      if (stop) break;
-      if (S.transport == TR_RCCL) phase_rccl(S, g, n, false);
-      else if (S.transport == TR_HOST) phase_unstage(S, g, n);
-      else phase_pull(S, g, n);
-      if (verify) {
-         if (!S.err.load()) phase_checksum(S, g, n);
-         stop = S.bar.wait(local, S.err, S.bar_timeout);
-         if (stop) break;
-         phase_compare(S, g);
-      }
-      phase_end(S, g, n);
    }
+   if (S.bar.wait(local, S.err, S.bar_timeout)) return true; // every slab's edge event of step n is recorded, its plane pointers published
+   if (S.transport == TR_RCCL) rccl_group(S, g0, true);
+   for (int g = g0; g < g1; g++) { use(g); exchange(S, g, n); }
+   if (S.transport == TR_RCCL) rccl_group(S, g0, false);
+   if (verify) {
+      for (int g = g0; g < g1; g++) if (!S.err.load()) phase_checksum(S, g, n);
+      cur = -1; // (phase_checksum chooses its device itself)
+      if (S.bar.wait(local, S.err, S.bar_timeout)) return true;
+      for (int g = g0; g < g1; g++) phase_compare(S, g);
+   }
+   for (int g = g0; g < g1; g++) { use(g); phase_end(S, g, n); }
+   return false;
+}
+
+// steps [n0, n0+ns) of the slabs [g0, g1); returns when their streams have drained and their receivers are flushed
+void run_slabs(Shared &S, int g0, int g1, int &local, int64_t n0, int64_t ns) {
+   bool stop = S.err.load() != 0;
+   for (int64_t n = n0; n < n0 + ns && !stop; n++) stop = step(S, g0, g1, local, n);
    if (S.bar.timed_out.load()) { // (the watchdog fired: report once, do not touch the devices any more -- a stuck stream would block the flush too)
       char b[200];
       snprintf(b, sizeof b, "slab chain hung: a slab's host thread did not reach the step barrier within %.0f s (a device or a collective is stuck; "
@@ -820,7 +641,7 @@ void run_slab(Shared &S, int g, int &local, int64_t n0, int64_t ns) {
       S.set_error(PF_ERR_HIP, b);
       return;
    }
-   finish_slab(S, g);
+   for (int g = g0; g < g1; g++) finish_slab(S, g);
 }
 
 } // namespace
@@ -837,7 +658,8 @@ struct pf_multi {
    int done = 0;
    bool created = false;
    double last_seconds = 0;
-   bool one_thread = false;
+   bool one_thread = false;          // PF_MULTI_ONE_THREAD: no slab threads, the caller's thread drives every slab
+   int bar_local = 0;                // ... and is the barrier's one party
    bool broken = false;              // the watchdog fired and a slab thread never came back: threads are abandoned, the object leaks
 };
 
@@ -860,7 +682,7 @@ void worker(pf_multi *m, int g) {
          seen = m->cmd_seq; kind = m->cmd_kind; n0 = m->cmd_n0; ns = m->cmd_ns;
       }
       if (kind == 2) break;
-      run_slab(S, g, local, n0, ns);
+      run_slabs(S, g, g + 1, local, n0, ns);
       S.bar.wait(local, S.err, S.bar_timeout);
       { std::lock_guard<std::mutex> lk(m->mu); m->done++; }
       m->cv_done.notify_all();
@@ -907,11 +729,6 @@ const char *transport_name(const Shared &S) {
 
 } // namespace
 
-namespace {
-// calibration chains (measure_wall_scale) are cut where the measurement wants them, not by partition()
-thread_local const std::vector<int64_t> *tl_force_cuts = nullptr;
-}
-
 extern "C" {
 
 int pf_slab_partition(const pf_simdata *sd, int32_t nslabs, int32_t even_split, int64_t *cuts) {
@@ -924,7 +741,7 @@ int pf_slab_partition_axis(const pf_simdata *sd, int32_t nslabs, int32_t even_sp
    if (!sd || !cuts) return fail("pf_slab_partition: null argument");
    if (!(wall_scale > 0)) wall_scale = 1.0;
    std::vector<int64_t> c;
-   const int rc = partition(sd, nslabs, even_split != 0, c, along_z != 0, wall_scale);
+   const int rc = cut_status(pf_cut::partition(sd, nslabs, even_split != 0, c, along_z != 0, wall_scale));
    if (rc) return rc;
    for (int g = 0; g <= nslabs; g++) cuts[g] = c[g];
    return PF_OK;
@@ -936,29 +753,25 @@ int pf_slab_partition_axis(const pf_simdata *sd, int32_t nslabs, int32_t even_sp
 // The ratio to what the compiled-in weights (23 / 5 interior planes per full plane of lossy / rigid nodes) predict for that wall is
 // the factor partition() scales them by.  <= 0: not measured (scene too small, too few steps, a chain cut along file z, or a
 // calibration run failed): the caller keeps factor 1.  Costs three short-lived slab engines (a few seconds at 1024^3 / 8).
-static int multi_create_x(pf_simdata *sd, int32_t nslabs, const int32_t *devices, const pf_opts_x *base, pf_multi **out);
+// force_cuts: a calibration chain is cut where the measurement wants it (x planes), not by partition()
+static int multi_create_x(pf_simdata *sd, int32_t nslabs, const int32_t *devices, const pf_opts_x *base, pf_multi **out, const std::vector<int64_t> *force_cuts = nullptr);
 static double slab_wall_scale_x(pf_simdata *sd, int32_t nslabs, int32_t device, const pf_opts_x *base) {
-   if (!sd || nslabs < 2 || tl_force_cuts) return -1.0;
+   if (!sd || nslabs < 2) return -1.0;
    const int64_t Nx = sd->Nx, p0 = Nx / nslabs;
    const int64_t ncal = 63; // steps each calibration chain takes: 9 to warm up, then 18 timed, three times (the fastest counts)
    if (p0 < 24 || (sd->Npts / nslabs) < ((int64_t)1 << 24) || sd->Nt < ncal || 2 * p0 + 8 > Nx) return -1.0;
    std::vector<int64_t> c0;
    std::vector<double> wall1;
-   if (partition(sd, nslabs, false, c0, false, 1.0, &wall1) != PF_OK) return -1.0;
+   if (pf_cut::partition(sd, nslabs, false, c0, false, 1.0, &wall1)) return -1.0;
    const int64_t dp = std::max<int64_t>(16, p0 / 2), cmid = std::max<int64_t>((Nx - p0 - dp) / 2, p0 + 1);
    if (cmid + p0 + dp + 2 > Nx) return -1.0;
    pf_opts_x o = *base;
    o.verify_exchange = 0; o.test_drop_exchange = 0; o.test_faults = 0; o.timing = 0;
    o.transport = PF_TRANSPORT_PEER;
-   // The forced cuts are x planes.  The real chain is cut along file z when the caller forces that or when pf_multi_create would
-   // choose it for G = nslabs (the same rule as there -- evaluated HERE, with the caller's G: a calibration chain of 2 or 3 slabs
-   // could decide otherwise): no x wall to weigh then.  The calibration chains themselves are pinned to x.
-   {
-      const int vb = o.air_variant & 255;
-      const bool can = !o.energy && vb != 40 && vb != 41 && !(o.multi_flags & PF_MULTI_FORCE_PAIRS) && nslabs < sd->Nz;
-      if (o.multi_flags & PF_MULTI_CUT_Z) return -1.0;
-      if (!(o.multi_flags & PF_MULTI_CUT_X) && !(o.debug & 0x2000) && o.layout != PF_LAYOUT_FILE && can && (sd->Nz - 2) / nslabs >= 16 && pf__axis_exchange_pays(sd, nullptr) != 0) return -1.0;
-   }
+   // The forced cuts are x planes.  Where the real chain is (or was meant to be) cut along file z there is no x wall to weigh: the
+   // rule is asked with the CALLER's G -- a calibration chain of 2 or 3 slabs could decide otherwise -- and the calibration chains
+   // themselves are pinned to x.
+   if (cut_axis(sd, o, nslabs) != AXIS_X) return -1.0;
    o.multi_flags = (o.multi_flags | PF_MULTI_CUT_X) & ~(PF_MULTI_CUT_Z | PF_MULTI_MEASURE_WEIGHTS | PF_MULTI_EVEN_SPLIT);
    auto one = [&](const std::vector<int64_t> &cuts, int slab) -> double {
       const int G = (int)cuts.size() - 1;
@@ -966,9 +779,7 @@ static double slab_wall_scale_x(pf_simdata *sd, int32_t nslabs, int32_t device, 
       pf_opts_x oo = o;
       oo.only_slab = slab + 1;
       pf_multi *m = nullptr;
-      tl_force_cuts = &cuts;
-      const int rc = multi_create_x(sd, G, devs.data(), &oo, &m);
-      tl_force_cuts = nullptr;
+      const int rc = multi_create_x(sd, G, devs.data(), &oo, &m, &cuts);
       if (rc != PF_OK || !m) return -1.0;
       double t = -1.0;
       if (pf_multi_run(m, 0, 9) == PF_OK) {
@@ -1015,7 +826,7 @@ int pf_multi_create(pf_simdata *sd, int32_t nslabs, const int32_t *devices, cons
    const pf_opts_x x = pf__take_hooks(base);
    return multi_create_x(sd, nslabs, devices, &x, out);
 }
-static int multi_create_x(pf_simdata *sd, int32_t nslabs, const int32_t *devices, const pf_opts_x *base, pf_multi **out) {
+static int multi_create_x(pf_simdata *sd, int32_t nslabs, const int32_t *devices, const pf_opts_x *base, pf_multi **out, const std::vector<int64_t> *force_cuts) {
    if (!sd || nslabs < 1 || !devices || !out || !base) return fail("pf_multi_create: bad argument");
    *out = nullptr;
    int ndev = 0;
@@ -1052,25 +863,16 @@ static int multi_create_x(pf_simdata *sd, int32_t nslabs, const int32_t *devices
       *out = m;
       return PF_OK;
    }
-   // Which axis?  The reference cuts along x (gpu_engine.h:516-662).  Rooms whose engines would rather store the grid with the
-   // x and z axes exchanged (+11-15 % on the reference's rooms) are cut along FILE Z instead: the slab axis
-   // is then the exchanged storage's plane axis and ghost planes stay contiguous.  PF_MULTI_CUT_Z forces, PF_MULTI_CUT_X forbids.
-   {
-      const int vb = S.base.air_variant & 255;
-      const bool can = !S.base.energy && vb != 40 && vb != 41 && !(S.base.multi_flags & PF_MULTI_FORCE_PAIRS) && G < sd->Nz;
-      if (S.base.multi_flags & PF_MULTI_CUT_Z) {
-         if (!can) { delete m; return fail("PF_MULTI_CUT_Z: single steps only, no energy diagnostic, fewer slabs than Nz"); }
-         S.along_z = true;
-      } else if (!(S.base.multi_flags & PF_MULTI_CUT_X) && !(S.base.debug & 0x2000) && S.base.layout != PF_LAYOUT_FILE && can && (sd->Nz - 2) / G >= 16)
-         S.along_z = pf__axis_exchange_pays(sd, nullptr) != 0;
-   }
+   const CutAxis axis = cut_axis(sd, S.base, G);
+   if (axis == AXIS_ERROR) { delete m; return fail("PF_MULTI_CUT_Z: single steps only, no energy diagnostic, fewer slabs than Nz"); }
+   S.along_z = axis == AXIS_Z;
    int rc = PF_OK;
-   if (tl_force_cuts) { // (a calibration chain of pf_slab_wall_scale)
-      if ((int)tl_force_cuts->size() != G + 1 || S.along_z) { delete m; return fail("internal: forced cuts do not fit the chain (they are x planes)"); }
-      S.cuts = *tl_force_cuts;
+   if (force_cuts) {
+      if ((int)force_cuts->size() != G + 1 || S.along_z) { delete m; return fail("internal: forced cuts do not fit the chain (they are x planes)"); }
+      S.cuts = *force_cuts;
    } else {
       // the wall planes' weights: the compiled-in figures times the caller's factor (pf_opts.wall_scale > 0), or times what three cost models
-      // of this scene on this device and build give (PF_MULTI_MEASURE_WEIGHTS)
+      // of this scene on this device and build give (PF_MULTI_MEASURE_WEIGHTS; slab_wall_scale_x clears the flag for its own chains)
       const bool even = (S.base.multi_flags & PF_MULTI_EVEN_SPLIT) != 0;
       S.wall_scale = 1.0;
       if (S.base.wall_scale > 0) S.wall_scale = S.base.wall_scale;
@@ -1078,10 +880,10 @@ static int multi_create_x(pf_simdata *sd, int32_t nslabs, const int32_t *devices
          const double k = slab_wall_scale_x(sd, G, devices[0], &S.base);
          if (k > 0) { S.wall_scale = k; S.wall_measured = true; }
       }
-      rc = partition(sd, G, even, S.cuts, S.along_z, S.wall_scale);
+      rc = cut_status(pf_cut::partition(sd, G, even, S.cuts, S.along_z, S.wall_scale));
    }
    S.slabs.resize(G);
-   for (int g = 0; g < G && rc == PF_OK; g++) rc = cut_slab(sd, S.cuts, g, G, S.slabs[g], S.along_z);
+   for (int g = 0; g < G && rc == PF_OK; g++) rc = cut_status(pf_cut::cut_slab(sd, S.cuts, g, G, S.slabs[g], S.along_z));
    S.plane_bytes = S.along_z ? pf_grid_bytes(1, sd->Ny, sd->Nx, sd->real_bytes) : pf_grid_bytes(1, sd->Ny, sd->Nz, sd->real_bytes);
    S.verify_n = S.base.verify_exchange > 0 ? S.base.verify_exchange : 0;
    if (const char *ev = getenv("PFFDTD_VERIFY_EXCHANGE")) S.verify_n = std::max(atoi(ev), 0);
@@ -1099,8 +901,8 @@ static int multi_create_x(pf_simdata *sd, int32_t nslabs, const int32_t *devices
    S.hbuf.resize(G);
    if (rc == PF_OK) rc = choose_transport(S, S.base.transport);
    if (rc != PF_OK) { delete m; return rc; }
-   S.bar.n = S.only >= 0 ? 1 : G;
    m->one_thread = (S.base.multi_flags & PF_MULTI_ONE_THREAD) != 0 && S.only < 0;
+   S.bar.n = (S.only >= 0 || m->one_thread) ? 1 : G; // the host threads that step the chain
    if (m->one_thread) {
       // the reference's arrangement (one host thread drives every GPU, gpu_engine.h:993-1145): kept for debugging
       for (int g = 0; g < G && !S.err.load(); g++) create_slab(S, g);
@@ -1132,29 +934,8 @@ int pf_multi_run(pf_multi *m, int64_t n0, int64_t nsteps) {
       return rc;
    }
    if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   if (m->one_thread) {
-      const int G = S.G;
-      for (int64_t n = n0; n < n0 + nsteps && !S.err.load(); n++) {
-         const bool verify = S.steps_done[0] < S.verify_n;
-         for (int g = 0; g < G; g++) { hipSetDevice(S.dev[g]); phase_begin(S, g, n); if (S.transport == TR_HOST) phase_stage(S, g, n); }
-         if (S.err.load()) break;
-         if (S.transport == TR_RCCL) {
-            bool open = g_rccl.GroupStart() == ncclSuccess;
-            for (int g = 0; g < G && !S.err.load(); g++) { hipSetDevice(S.dev[g]); phase_rccl(S, g, n, true); }
-            if (!open || g_rccl.GroupEnd() != ncclSuccess) S.set_error(PF_ERR_HIP, "RCCL group call failed");
-         } else if (S.transport == TR_HOST) {
-            for (int g = 0; g < G && !S.err.load(); g++) { hipSetDevice(S.dev[g]); phase_unstage(S, g, n); }
-         } else {
-            for (int g = 0; g < G && !S.err.load(); g++) { hipSetDevice(S.dev[g]); phase_pull(S, g, n); }
-         }
-         if (verify) {
-            for (int g = 0; g < G && !S.err.load(); g++) phase_checksum(S, g, n);
-            for (int g = 0; g < G && !S.err.load(); g++) phase_compare(S, g);
-         }
-         for (int g = 0; g < G && !S.err.load(); g++) { hipSetDevice(S.dev[g]); phase_end(S, g, n); }
-      }
-      for (int g = 0; g < G; g++) finish_slab(S, g);
-   } else {
+   if (m->one_thread) run_slabs(S, 0, S.G, m->bar_local, n0, nsteps);
+   else {
       post(m, 1, n0, nsteps);
       wait_done(m);
       if (m->broken && !S.err.load()) S.set_error(PF_ERR_HIP, "slab chain hung: a slab's host thread never came back");
@@ -1251,27 +1032,15 @@ int pf_rccl_comm_create(const void *id128, int32_t nranks, int32_t rank, int32_t
    *out = nullptr;
    std::string why;
    { std::lock_guard<std::mutex> lk(g_rccl_mu); if (!g_rccl.load(why)) return fail("%s", why.c_str()); }
-   // on a helper thread with a timeout, like the chain's communicators: a rendezvous that never completes must not hang the caller
-   struct Job { std::mutex mu; std::condition_variable cv; bool done = false; ncclResult_t r = ncclSuccess; ncclComm_t c = nullptr; ncclUniqueId id; int n, rk, dev; };
+   struct Job { ncclComm_t c = nullptr; ncclUniqueId id; int n, rk, dev; };
    auto job = std::make_shared<Job>();
    memcpy(&job->id, id128, sizeof job->id); job->n = nranks; job->rk = rank; job->dev = device;
-   fflush(stdout);
-   const int saved_out = dup(1); // (RCCL's banner goes to stdout: a host that prints machine-readable results there must not find it in between)
-   if (saved_out >= 0) dup2(2, 1);
-   std::thread([job] {
-      ncclResult_t r = ncclSuccess;
-      if (hipSetDevice(job->dev) != hipSuccess) r = ncclUnhandledCudaError;
-      if (r == ncclSuccess) r = g_rccl.CommInitRank(&job->c, job->n, job->id, job->rk);
-      { std::lock_guard<std::mutex> l2(job->mu); job->r = r; job->done = true; }
-      job->cv.notify_all();
-   }).detach();
-   double tmo = 60.0;
-   if (const char *ev = getenv("PFFDTD_RCCL_INIT_TIMEOUT_S")) { const double v = atof(ev); if (v > 0) tmo = v; }
-   bool finished;
-   { std::unique_lock<std::mutex> l2(job->mu); finished = job->cv.wait_for(l2, std::chrono::duration<double>(tmo), [&] { return job->done; }); }
-   if (saved_out >= 0) { fflush(stdout); dup2(saved_out, 1); close(saved_out); }
-   if (!finished) { char b[160]; snprintf(b, sizeof b, "ncclCommInitRank (rank %d of %d) did not return within %.0f s", rank, nranks, tmo); pf__set_error(b); return PF_ERR_HIP; }
-   if (job->r != ncclSuccess) { char b[256]; snprintf(b, sizeof b, "ncclCommInitRank (rank %d of %d) failed: %s", rank, nranks, g_rccl.GetErrorString(job->r)); pf__set_error(b); return PF_ERR_HIP; }
+   char what[64];
+   snprintf(what, sizeof what, "ncclCommInitRank (rank %d of %d)", rank, nranks);
+   const int rc = rccl_guarded(job, [](Job &j) {
+      return hipSetDevice(j.dev) != hipSuccess ? ncclUnhandledCudaError : g_rccl.CommInitRank(&j.c, j.n, j.id, j.rk);
+   }, what, why);
+   if (rc != PF_OK) { pf__set_error(why.c_str()); return rc; }
    pf_rccl_comm *c = new pf_rccl_comm();
    c->c = job->c; c->nranks = nranks; c->rank = rank;
    *out = c;

@@ -452,3 +452,47 @@ def test_partition_weights_are_measured_at_creation_and_change_no_bits():
     assert seen["fixed"][:2] == (1.0, False) and seen["given"][:2] == (1.7, False), seen
     assert seen["measured"][2] == [x1 - x0 for x0, x1 in engine.slab_partition(sd, G, wall_scale=seen["measured"][0])], seen
     print("wall weights:", seen)
+
+
+# ---- the cost model of one rank (pf_opts.only_slab): its exchange, through every transport -------------------------------------
+def test_one_rank_cost_model_exchanges_its_own_planes_through_every_transport():
+    """only_slab = 2 of three slabs cut evenly along x: the middle slab (planes 16..31 of 48) alone exists and is fed its OWN edge planes
+    as ghost planes -- by peer copies, by RCCL (a 1-rank communicator) and host-staged.  The physics is wrong by design, the exchange
+    must not be: (a) the three transports deliver the same bits over all steps; (b) until something non-zero can have reached an
+    exchanged plane -- the 7-point scheme moves one cell per step, so for K steps, K = the source's distance in planes to the slab's
+    nearer edge plane -- the slab is the single-domain oracle's; (c) receivers outside the slab stay zero."""
+    xs = 24
+    kw = dict(Nx=48, Ny=20, Nz=24, Nt=40, wall=3, Nm=1, Mb=3, src=[xs, 10, 12],
+              rcv=[[xs + 1, 10, 12], [xs - 1, 11, 13], [18, 10, 12], [8, 10, 12], [40, 9, 11]])
+
+    def make():
+        sd = sim_data.SimData.from_sim(synth.shoebox(**kw), "single")
+        sd.scale_input()
+        return sd
+    ref = make()
+    oracle.run_sim(ref)
+    per = int(ref.Ny * ref.Nz)
+    sx, rx = ref.in_ixyz // per, ref.out_ixyz // per  # (synth spreads a source and a receiver over the eight cells around it: planes x, x + 1)
+    near = np.abs(rx - xs) <= 3
+    rows = {}
+    for transport in (engine.PF_TRANSPORT_PEER, engine.PF_TRANSPORT_RCCL, engine.PF_TRANSPORT_HOST):
+        sd = make()
+        m = engine.HipMulti(sd, [0, 0, 0], multi_flags=engine.PF_MULTI_EVEN_SPLIT | engine.PF_MULTI_CUT_X, transport=transport, only_slab=2)
+        m.run(0, 9)
+        m.run(9, int(sd.Nt) - 9)
+        info, sl = m.info(), m.slab(1)
+        m.close()
+        assert info["transport"] == transport and not info["cut_along_z"]
+        assert (sl["x0"], sl["x1"]) == (16, 32)
+        rows[transport] = sd.u_out.copy()
+    inside = (rx >= sl["x0"]) & (rx < sl["x1"])
+    assert inside.sum() == 24 and (~inside).sum() == 16 and near.sum() == 16
+    K = int(min(sx.min() - sl["x0"], sl["x1"] - 1 - sx.max()))
+    assert K >= 6
+    peer = rows[engine.PF_TRANSPORT_PEER]
+    assert all(np.abs(peer[r]).max() > 0 for r in np.flatnonzero(inside))
+    for transport, got in rows.items():
+        assert np.array_equal(got[inside], peer[inside]), transport                   # (a)
+        assert np.array_equal(got[inside][:, :K], ref.u_out[inside][:, :K]), transport  # (b)
+        assert not got[~inside].any(), transport                                      # (c)
+    assert np.abs(ref.u_out[near][:, :K]).max() > 0  # (b) is not vacuous: the wave has reached a near receiver within K steps

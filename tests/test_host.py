@@ -268,3 +268,19 @@ def test_a_cut_pushed_aside_by_a_source_does_not_leave_a_thick_rank():
     assert all(not (512 - 8 < x <= 512 + 8) for x in cuts), cuts
     sizes = [b - a for a, b in parts]
     assert max(sizes) - min(sizes) <= 6 and max(sizes) <= 131, sizes
+
+
+def test_the_c_chains_cut_under_sanitizers(tmp_path):
+    """csrc/pf_slab_cut.h -- what pf_multi_create cuts a scene with -- has no device in it: tests/slab_cut_check.cpp drives it on a small
+    unsorted scene (G = 2, 3, 5, both axes, both split rules, fp32 and fp64) as a program of its own, built with the host compiler under
+    the address and undefined-behaviour sanitizers; it names every violated condition on stderr."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
+    if not cxx:
+        pytest.skip("no host C++ compiler")
+    exe = tmp_path / "slab_cut_check"
+    subprocess.run([cxx, "-std=c++17", "-O0", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", str(ROOT / "include"), "-I", str(ROOT / "pffdtd_amd" / "csrc"), str(ROOT / "tests" / "slab_cut_check.cpp"), "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stderr == "", r.stderr[-3000:]
