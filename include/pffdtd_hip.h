@@ -91,7 +91,9 @@ typedef struct pf_opts {
    int32_t readout_chunk; /* receiver ring depth in steps before a D2H flush (0 = default) */
    int32_t air_variant;   /* 0 = automatic (measured at creation); 3 = the reference's kernel sequence (flips, air, ABC lists); 4 / 7 =
                              barrier-free marching kernel with virtual ghosts / in-kernel ABC; 25 = lean fused kernel (7-point); 40 =
-                             temporally blocked pairs forced (41: their driver only); | 256 = separate rigid / branch-ODE kernels */
+                             temporally blocked pairs forced (41: their driver only); 42 = 13-point blocked pairs with the shell in bricks
+                             (folded FCC, single domain, file order: everything 40 needs, and no source within two cells of the shell);
+                             | 256 = separate rigid / branch-ODE kernels */
    int32_t air_chunk;     /* planes marched per workgroup (0 = auto, <0 = that many equal chunks) */
    int32_t timing;        /* 1 = bracket the air kernel with HIP events every step (pf_engine_timing) */
    void   *ext_u0;        /* optional caller-owned DEVICE buffers for the two state grids, each of */
@@ -174,6 +176,7 @@ typedef struct pf_timing {
                                0: the guarded form ran (mixed counts, other counts) or no such region */
    int64_t wall_unread_skipped; /* triples: wall regions (bits as in wall_three_steps) that do not store u^{n+1} of their cells because nothing reads it:
                                no receiver in their cells, no tile or node that steps singly */
+   int64_t fcc_shell_bricks;/* air_variant 42: bricks this engine launches per pair (the whole 13-point shell, pf_brick_fcc.h); 0 otherwise */
 } pf_timing;
 
 typedef struct pf_engine pf_engine;

@@ -312,7 +312,7 @@
          }
       }
       if (triple && vol == 0) return PF_OK; // (every 20-row tile holds a receiver, a source or geometry: init_tb2 tries the pairs' smaller tiles)
-      if (vbase == 40 && vol == 0) return set_err(PF_ERR_ARG, "air_variant 40 (temporal blocking) requested but the scene has no boundary-free tiles");
+      if (vbase == 40 && vol == 0) return set_err(PF_ERR_ARG, "air_variant %d (temporal blocking) requested but the scene has no boundary-free tiles", op.air_variant & 255);
       // auto: the shell costs grow with the perimeter of the y-z cross-section, the gain with its area -- measured on
       // MI355X: 512^2 planes -4.5 %, 768^2 +9 %, 1024^2 +13 % for a box room; and two extra grids must be worth it.
       // Single-domain engines then time a blocked pair against the single-step kernels at creation (autotune()), so the

@@ -23,6 +23,7 @@
 #include "pf_tb3.h"
 #include "pf_wall.h"
 #include "pf_brick.h"
+#include "pf_brick_fcc.h"
 
 // shared between the two units (defined in pf_engine.hip)
 extern "C" void pf__set_error(const char *msg);
@@ -300,6 +301,7 @@ template <typename Real> struct Engine : EngineBase {
       auto F = [](void *p) { if (p) hipFree(p); };
       for (Real *g : own_list) F(g); // state grids this engine allocated (u0/u1 unless external, the temporal-blocking spares)
       own_list.clear();
+      free_fcc_bricks();
       F(wl_pen); F(wl_rec); F(wl_rest); F(wl_blk); F(wl_brk); F(wl_binfo); F(wl_blos); F(ubx[0]); F(ubx[1]); F(edge_sel3); F(vh1b); F(gh1b); F(d_lossy); F(mask); F(zs_map); F(zs_adj); F(zs_li); F(zs_rest); F(zs_fd); F(tb_clean); F(tb_dirty); F(tb_srct); F(tb_sample); F(sh_tiles); F(Lu); F(vh_old); F(u2in); F(d_acc); F(d_DEF); F(d_bn); F(d_bnl); F(d_bna); F(d_in); F(d_out); F(d_adj); F(d_Q); F(d_mat); F(d_Mb); F(d_ssaf);
       F(d_beta); F(d_insig); F(d_mq); F(ub[0]); F(ub[1]); F(ub[2]); F(u2ba); F(vh1); F(gh1); F(ring);
       if (h_ring) hipHostFree(h_ring);
@@ -427,7 +429,7 @@ template <typename Real> struct Engine : EngineBase {
          swz = true;
          return PF_OK;
       }
-      if ((op.debug & 0x2000) || !single || ext || op.energy || vb == 41) return PF_OK;
+      if ((op.debug & 0x2000) || !single || ext || op.energy || vb == 41 || vb == 42) return PF_OK; // (42: file order unless the caller says otherwise)
       int64_t counts[2];
       swz = pf__axis_exchange_pays(&sd, counts) != 0;
       if (counts[0] + counts[1] > 0 && getenv("PFFDTD_VERBOSE") && atoi(getenv("PFFDTD_VERBOSE")) > 0)
@@ -532,9 +534,13 @@ template <typename Real> struct Engine : EngineBase {
          // memory (the 13-point default); 25 = lean fused kernel (7-point); 40 / 41 = temporally blocked pairs forced / driver only
          vbase = op.air_variant & 255;
          if (op.air_variant & ~(255 | 256)) return set_err(PF_ERR_ARG, "air_variant %d: unknown flag bits", op.air_variant);
-         if (vbase != 0 && vbase != 3 && vbase != 4 && vbase != 7 && vbase != 25 && vbase != 40 && vbase != 41)
+         if (vbase != 0 && vbase != 3 && vbase != 4 && vbase != 7 && vbase != 25 && vbase != 40 && vbase != 41 && vbase != 42)
             return set_err(PF_ERR_ARG, "air_variant %d: choose 0 (auto), 3 (unfused reference sequence), 4 / 7 (barrier-free kernel: virtual ghosts / "
-                                       "in-kernel ABC), 25 (lean fused kernel, 7-point), 40 / 41 (blocked pairs); the other variants were retired", op.air_variant);
+                                       "in-kernel ABC), 25 (lean fused kernel, 7-point), 40 / 41 (blocked pairs), 42 (13-point blocked pairs with the shell in "
+                                       "bricks); the other variants were retired", op.air_variant);
+         // 42 = 40 with the 13-point shell in bricks (init_fcc_bricks, once the pairs stand): every precondition of 40 and its own
+         fb_want = vbase == 42;
+         if (fb_want) { int rcf = check_fcc_bricks(); if (rcf) return rcf; vbase = 40; }
          if (op.numerics != PF_NUM_CPU_EXACT && op.numerics != PF_NUM_GPU_SAFEGUARDED)
             return set_err(PF_ERR_ARG, "numerics must be PF_NUM_CPU_EXACT (0) or PF_NUM_GPU_SAFEGUARDED (2)");
          sg = op.numerics == PF_NUM_GPU_SAFEGUARDED;
@@ -652,6 +658,7 @@ template <typename Real> struct Engine : EngineBase {
       if (tb2) { int rc = autotune(); if (rc) { tb2_probe = false; return rc; } }
       else if (fcc) { int rc = autotune_fcc_lw(); if (rc) { tb2_probe = false; return rc; } } // (pairs dropped or never offered)
       tb2_probe = false;
+      if (fb_want) { int rc = init_fcc_bricks(); if (rc) return rc; }
       if (tb3) tb3_remember_home();
       if (!tb2 && op.slab_first && op.slab_last) { int rc = sample_placement_single(); if (rc) return rc; }
       // hipGraph replay of the step loop (six steps per graph): measured on MI355X / ROCm 7.2 it does not beat plain
@@ -673,6 +680,7 @@ template <typename Real> struct Engine : EngineBase {
 
 #include "pf_engine_blocking.inc"
 #include "pf_engine_walls.inc"
+#include "pf_engine_fcc_bricks.inc"
 #include "pf_engine_blocked_steps.inc"
 #include "pf_engine_tune.inc"
 #include "pf_engine_launch.inc"
@@ -922,6 +930,7 @@ template <typename Real> struct Engine : EngineBase {
       if (wl_on)
          for (const WlGroup &g : wl_grp) { tm.wall_blocks[0] += g.nblk[0] + g.nblk[2]; tm.wall_blocks[1] += g.nblk[1]; }
       tm.wall_bricks = wl_on ? wl_nbrk : 0;
+      tm.fcc_shell_bricks = fb_on ? fb_nbrk : 0;
       tm.wall_three_steps = (wl_on && (tb3 || (tb3_slab && ws_all3))) ? (int)(wall_g3() | (wl_xw[0] ? 0x10u : 0u) | (wl_xw[1] ? 0x20u : 0u)) : 0;
       tm.wall_profile = 0; tm.wall_uniform_branches = 0; tm.wall_unread_skipped = 0;
       for (int gi = 0; gi < 4; gi++) if ((tm.wall_three_steps >> gi) & 1) { // what a triple launches for the alike blocks of these groups

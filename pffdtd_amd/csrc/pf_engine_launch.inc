@@ -235,6 +235,7 @@
    int step_pair(int64_t n) {
       if (n < 0 || n + 1 >= Nt) return set_err(PF_ERR_ARG, "step pair %ld outside [0,Nt=%ld)", (long)n, (long)Nt);
       if (wl_on) return step_pair_walls(n);
+      if (fb_on) return step_pair_fcc_bricks(n);
       hipStream_t s = s_main;
       Real *A = u0, *B = u1, *C = bufC, *D = bufD;
       std::pair<hipEvent_t, hipEvent_t> ev{}, eva{};

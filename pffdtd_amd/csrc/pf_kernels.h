@@ -220,6 +220,8 @@ struct AirParams {
    // storage coordinates; only the ORDER in which the neighbours enter the sums follows the file's axes, so that the bits are
    // the reference's whatever the storage order
    int32_t swz;
+   // k_air_fcc<..., CLIP> only: the tile stores its cells of rows [cy0, cy1) x columns [cz0, cz1) (whole vectors) and no others
+   int32_t cy0, cy1, cz0, cz1;
 };
 
 // =============================================================================================================
@@ -406,13 +408,14 @@ __global__ __launch_bounds__(64 * WY * WZ) void k_air_cart(const Real *__restric
 // Same marching scheme; all three planes keep R+2 rows, and every row used with a z offset gets its wave-edge
 // columns from the edge lanes.
 // =============================================================================================================
-template <typename Real, int R, int WY, int WZ, bool SG, bool DPP, bool VG = false, bool ABCK = false, int LW = 64>
+template <typename Real, int R, int WY, int WZ, bool SG, bool DPP, bool VG = false, bool ABCK = false, int LW = 64, bool CLIP = false>
 __global__ __launch_bounds__(64 * WY * WZ) void k_air_fcc(const Real *__restrict__ u1, Real *u0,
                                                          const uint8_t *__restrict__ mask, Real a1, Real a2,
                                                          AirParams ap, Real labc, const Real *u0_src = nullptr,
                                                          const int32_t *__restrict__ tiles = nullptr) {
    // u0_src: read u^{n-1} there instead of from u0 (out of place: the shell of a temporally blocked pair);
    // tiles: block b works on tile tiles[b] = (xc*nyt + yt)*nzt + zt instead of walking the whole range
+   // CLIP: only the cells inside AirParams::cy0 .. cz1 are stored (the box's single-step tiles where bricks own the shell: Engine::step_pair_fcc_bricks)
    typedef typename VecOf<Real>::type vec;
    constexpr int V = VecOf<Real>::V;
    const uint32_t total = (uint32_t)ap.nzt * ap.nyt * ap.nxc;
@@ -582,7 +585,7 @@ __global__ __launch_bounds__(64 * WY * WZ) void k_air_fcc(const Real *__restrict
 #pragma unroll
          for (int i = 0; i < V; i++)
             if ((bits >> i) & 1u) o[i] = old[r][i];
-         if (active && (y0 + r <= Ny - 2)) __builtin_nontemporal_store(o, (vec *)(po + soff[r]));
+         if (active && (y0 + r <= Ny - 2) && (!CLIP || (y0 + r >= ap.cy0 && y0 + r < ap.cy1 && z0 >= ap.cz0 && z0 < ap.cz1))) __builtin_nontemporal_store(o, (vec *)(po + soff[r]));
       }
 #pragma unroll
       for (int j = 0; j < R + 2; j++) {

@@ -75,7 +75,7 @@ int cut_status(const char *msg) { return msg ? fail("%s", msg) : PF_OK; }
 enum CutAxis { AXIS_X, AXIS_Z, AXIS_ERROR };
 CutAxis cut_axis(const pf_simdata *sd, const pf_opts_x &o, int G) {
    const int vb = o.air_variant & 255;
-   const bool can = !o.energy && vb != 40 && vb != 41 && !(o.multi_flags & PF_MULTI_FORCE_PAIRS) && G < sd->Nz;
+   const bool can = !o.energy && vb != 40 && vb != 41 && vb != 42 && !(o.multi_flags & PF_MULTI_FORCE_PAIRS) && G < sd->Nz;
    if (o.multi_flags & PF_MULTI_CUT_Z) return can ? AXIS_Z : AXIS_ERROR;
    if ((o.multi_flags & PF_MULTI_CUT_X) || (o.debug & PF_DBG_SWZ_OFF) || o.layout == PF_LAYOUT_FILE || !can || (sd->Nz - 2) / G < 16) return AXIS_X;
    return pf__axis_exchange_pays(sd, nullptr) != 0 ? AXIS_Z : AXIS_X;
