@@ -1,5 +1,54 @@
 // pf_engine_blocked_steps.inc -- part of `template <typename Real> struct Engine` (pf_engine.hip includes it INSIDE the class body; not a translation unit):
-// single-domain pairs with wall regions and triples (Engine::step_pair_walls, step_triple), the five-grid role cycle, pf_engine_set_spares.
+// single-domain pairs, pairs with wall regions and triples (Engine::step_pair, step_pair_walls, step_triple), the five-grid role cycle,
+// pf_engine_set_spares.
+   // steps n and n+1 in one go; the state moves from (u0, u1) to (bufC, bufD), which swap roles with them
+   int step_pair(int64_t n) {
+      if (n < 0 || n + 1 >= Nt) return set_err(PF_ERR_ARG, "step pair %ld outside [0,Nt=%ld)", (long)n, (long)Nt);
+      if (wl_on) return step_pair_walls(n);
+      if (fb_on) return step_pair_fcc_bricks(n);
+      hipStream_t s = s_main;
+      Real *A = u0, *B = u1, *C = bufC, *D = bufD;
+      // node values: step n reads X2 = u^{n-1} and writes the free buffer T, step n+1 reads X1 = u^n and writes X2
+      Real *X2 = ub[2], *X1 = ub[1], *T = ub[0];
+      // the column strips update their own boundary nodes (zs_map): the list kernel visits the others and takes the strips' branch ODEs along
+      const bool strips = zs_map != nullptr;
+      const Range nodes = strips ? Range{0, zs_nrest} : Range{0, Nb};
+      const Grids g1{A, B, C}, g2{B, C, D};
+      const Bnd b1{T, X2, {vh1, gh1}, {vh1, gh1}, strips ? zs_rest : nullptr, 0, 0}, b2{X2, X1, b1.in, b1.out, b1.sel, 0, 0};
+      EvPair ev{}, eva{}, evt{};
+      if (op.timing) { ev = ev_get(); eva = ev_get(); hipEventRecord(ev.first, s); hipEventRecord(eva.first, s); } // step events: one per step
+      // The FIRST step of the shell reads u^{n-1}, u^n only and writes cells the pair kernel does not: it runs BESIDE the pair
+      // kernel, on the edge stream (its launches are small and latency-bound -- strided strips, list gathers -- and fill the gaps
+      // the bandwidth-bound pair kernel leaves); the second step needs the box's u^{n+1} and follows.  PF_DBG_WALLS_ONE_STREAM: one stream.
+      const bool beside = !(op.debug & PF_DBG_WALLS_ONE_STREAM);
+      hipStream_t sh = beside ? s_edge : s;
+      if (beside) { HIPCHK(hipEventRecord(ev_pre, s)); HIPCHK(hipStreamWaitEvent(s_edge, ev_pre, 0)); }
+      launch_shell(sh, g1, strips ? b1.u0b : nullptr);
+      launch_rigid(sh, g1, b1, nodes, strips);
+      launch_fd(sh, g1, b1, {0, Nbl});
+      launch_io(sh, g1, n, true, src_range());
+      // (with per-launch events on, the pair kernel waits for the shell: its recorded duration is the kernel's own, not the overlap's)
+      if (op.timing && beside) { HIPCHK(hipEventRecord(ev_edge, s_edge)); HIPCHK(hipStreamWaitEvent(s, ev_edge, 0)); }
+      if (op.timing) { evt = ev_get(); hipEventRecord(evt.first, s); }
+      launch_tb2(s, n, A, B, C, D);
+      if (op.timing) { hipEventRecord(evt.second, s); tb2_ev.push_back(evt); }
+      if (beside && !op.timing) { HIPCHK(hipEventRecord(ev_edge, s_edge)); HIPCHK(hipStreamWaitEvent(s, ev_edge, 0)); }
+      if (op.timing) { hipEventRecord(eva.second, s); air_ev.push_back(eva); eva = ev_get(); } // ("air" of the first step: the pair kernel and the shell beside it)
+      if (ring_fill == 0) ring_n0 = n;
+      ring_fill++; steps_done++;
+      if (op.timing) { hipEventRecord(ev.second, s); step_ev.push_back(ev); ev = ev_get(); hipEventRecord(ev.first, s); hipEventRecord(eva.first, s); }
+      launch_shell(s, g2, strips ? b2.u0b : nullptr);
+      if (op.timing) { hipEventRecord(eva.second, s); air_ev.push_back(eva); }
+      launch_rigid(s, g2, b2, nodes, strips);
+      launch_fd(s, g2, b2, {0, Nbl});
+      launch_io(s, g2, n + 1, true, src_range());
+      ring_fill++; steps_done++;
+      u0 = C; u1 = D; bufC = A; bufD = B; ub[0] = X1; ub[1] = X2; ub[2] = T; // the state after the pair (newest node values in ub[1], the ones before in ub[2])
+      if (op.timing) { hipEventRecord(ev.second, s); step_ev.push_back(ev); }
+      HIPCHK(hipGetLastError());
+      if (ring_fill == ring_depth) return flush();
+      return PF_OK;
+   }
    // steps n and n+1 with the shell in pairs as well.  Order: box (both steps), then the first step of what no wall region
    // owns -- the box's dirty tiles and the boundary nodes inside it --, source / receivers of step n, the wall regions (both
    // steps; they read u^{n-1}, u^n and the old branch state only), then the second step of the dirty tiles and their nodes.
@@ -15,46 +64,42 @@
       // node values: X2 = u^{n-1}, X1 = u^n are only read; u^{n+1} -> T1, u^{n+2} -> T2, two buffers nobody reads during the pair (round 6: five
       // node-value buffers, so that a region's or a brick's halo node may be evaluated while its owner already stores)
       Real *X2 = ub[2], *X1 = ub[1], *T1 = ub[0], *T2 = ubx[0];
-      auto get_ev = [&]() { std::pair<hipEvent_t, hipEvent_t> e{}; if (!ev_pool.empty()) { e = ev_pool.back(); ev_pool.pop_back(); } else { hipEventCreate(&e.first); hipEventCreate(&e.second); } return e; };
-      std::pair<hipEvent_t, hipEvent_t> ev{}, ev2{}, evt{}, eva{};
+      // branch state: everything that takes both steps reads S0 and writes S1; the box's own nodes S0 -> S1 in their first step, S1 in place in their second
+      const BranchState S0{vh1, gh1}, S1{vh1b, gh1b};
+      const Grids g1{A, B, C}, g2{B, C, D};
+      EvPair ev{}, ev2{}, evt{}, eva{};
       // "air" of a pair with wall regions (pf_timing.air_ms_total, the CLI's "Air update" line): the alike blocks' launches and the
       // box kernel on the main stream -- the regions' boundary nodes are inside those launches and cannot be told apart
-      if (op.timing) { ev = get_ev(); ev2 = get_ev(); evt = get_ev(); eva = get_ev(); hipEventRecord(ev.first, s); hipEventRecord(eva.first, s); }
+      if (op.timing) { ev = ev_get(); ev2 = ev_get(); evt = ev_get(); eva = ev_get(); hipEventRecord(ev.first, s); hipEventRecord(eva.first, s); }
       // The wall regions read u^{n-1}, u^n and the old branch state only and write cells the box kernel does not: any order will do.
       // The generic blocks (edges, corners: a few hundred waves, each a long chain of dependent steps) go to the second stream
       // and run beside the alike blocks' launches, which are issue-bound; beside the bandwidth-bound box kernel they crawl
-      // (measured: 0.47 -> 3.6 ms), so that one comes after.  debug 0x4000000: everything on the main stream.
-      const bool beside = !(op.debug & 0x4000000);
+      // (measured: 0.47 -> 3.6 ms), so that one comes after.  PF_DBG_WALLS_ONE_STREAM: everything on the main stream.
+      const bool beside = !(op.debug & PF_DBG_WALLS_ONE_STREAM);
       hipStream_t sw = beside ? s_edge : s_main;
       if (beside) { HIPCHK(hipEventRecord(ev_pre, s_main)); HIPCHK(hipStreamWaitEvent(s_edge, ev_pre, 0)); }
-      u0_src = A; u1 = B; u0 = C;
-      tb3_src_n = n;
-      launch_dirty_tiles(sw);
-      bnd_sel = wl_rest; bs_vout = vh1b; bs_gout = gh1b;
-      ub[0] = T1; ub[2] = X2;
-      launch_rigid(sw, {0, wl_nrest});
-      launch_bricks(sw, A, B, C, D, nullptr, X2, X1, T1, T2, nullptr, 2); // the frame: both steps, beside the alike blocks
-      launch_walls_x(s, sw, A, B, C, D, nullptr, X2, X1, T1, T2, nullptr, 2, 0xf); // (every wall launch beside the box kernel instead of before it: 492 vs 511-516 Gvox/s)
+      launch_dirty_tiles(sw, g1);
+      launch_rigid(sw, g1, Bnd{T1, X2, S0, S1, wl_rest, 0, 0}, {0, wl_nrest});
+      launch_bricks(sw, A, B, C, D, nullptr, X2, X1, T1, T2, nullptr, S0, S1, 2); // the frame: both steps, beside the alike blocks
+      launch_walls_x(s, sw, A, B, C, D, nullptr, X2, X1, T1, T2, nullptr, S0, S1, 2, 0xf); // (every wall launch beside the box kernel instead of before it: 492 vs 511-516 Gvox/s)
       if (op.timing) hipEventRecord(evt.first, s);
-      launch_tb2(s, A, B, C, D);
+      launch_tb2(s, n, A, B, C, D);
       if (op.timing) { hipEventRecord(evt.second, s); tb2_ev.push_back(evt); hipEventRecord(eva.second, s); air_ev.push_back(eva); }
       if (beside) { HIPCHK(hipEventRecord(ev_edge, s_edge)); HIPCHK(hipStreamWaitEvent(s_main, ev_edge, 0)); }
-      launch_io(s, n, true, src_range()); // (receivers read u^n; the source goes into u^{n+1}, which only the second step below reads -- or went in inside k_tb3<..., SRC>)
+      launch_io(s, g1, n, true, src_range()); // (receivers read u^n; the source goes into u^{n+1}, which only the second step below reads -- or went in inside k_tb3<..., SRC>)
       if (ring_fill == 0) ring_n0 = n;
       ring_fill++; steps_done++;
       if (op.timing) { hipEventRecord(ev.second, s); step_ev.push_back(ev); hipEventRecord(ev2.first, s); }
-      std::swap(vh1, vh1b); std::swap(gh1, gh1b); // the state after the pair (the nodes inside the box: after its first step)
-      u0_src = B; u1 = C; u0 = D;
-      launch_dirty_tiles(s);
-      bs_vout = bs_gout = nullptr;
-      ub[0] = T2; ub[2] = X1; // second step of the box's nodes: u2b = u^n of the node, its u^{n+2} where the regions put theirs
-      launch_rigid(s, {0, wl_nrest});
-      ub[0] = X2; ub[1] = T2; ub[2] = T1; ubx[0] = X1; // (newest in ub[1], the one before in ub[2], ub[0] free: the single steps' convention)
-      bnd_sel = nullptr;
-      launch_io(s, n + 1, true, src_range());
+      launch_dirty_tiles(s, g2);
+      launch_rigid(s, g2, Bnd{T2, X1, S1, S1, wl_rest, 0, 0}, {0, wl_nrest}); // second step of the box's nodes: u2b = u^n of the node, its u^{n+2} where the regions put theirs
+      launch_io(s, g2, n + 1, true, src_range());
       ring_fill++; steps_done++;
-      if (on_cycle) { u0_src = nullptr; u0 = C; u1 = D; bufD = A; bufE = B; } // (bufC stays the triples' u^{n+1} grid)
-      else { u0_src = nullptr; u0 = C; u1 = D; bufC = A; bufD = B; }
+      // the state after the pair
+      u0 = C; u1 = D;
+      if (on_cycle) { bufD = A; bufE = B; } // (bufC stays the triples' u^{n+1} grid)
+      else { bufC = A; bufD = B; }
+      ub[0] = X2; ub[1] = T2; ub[2] = T1; ubx[0] = X1; // (newest in ub[1], the one before in ub[2], ub[0] free: the single steps' convention)
+      vh1 = S1.v; gh1 = S1.g; vh1b = S0.v; gh1b = S0.g;
       if (tb3) tb3_pick();
       if (op.timing) { hipEventRecord(ev2.second, s); step_ev.push_back(ev2); }
       HIPCHK(hipGetLastError());
@@ -91,85 +136,78 @@
       Real *A = u0, *B = u1, *C = bufC, *D = bufD, *E = bufE;
       // node values: X2 = u^{n-1}, X1 = u^n are only read during the triple; u^{n+1} -> T1, u^{n+2} -> T2, u^{n+3} -> T3 (five buffers)
       Real *X2 = ub[2], *X1 = ub[1], *T1 = ub[0], *T2 = ubx[0], *T3 = ubx[1];
-      auto get_ev = [&]() { std::pair<hipEvent_t, hipEvent_t> e{}; if (!ev_pool.empty()) { e = ev_pool.back(); ev_pool.pop_back(); } else { hipEventCreate(&e.first); hipEventCreate(&e.second); } return e; };
-      std::pair<hipEvent_t, hipEvent_t> ev{}, evt{}, eva{};
-      if (op.timing) { ev = get_ev(); evt = get_ev(); eva = get_ev(); hipEventRecord(ev.first, s); hipEventRecord(eva.first, s); }
-      const bool beside = !(op.debug & 0x4000000);
+      // branch state: whatever takes two or three steps in its first launch reads S0 and writes S1; every later launch of the pass S1 in place
+      const BranchState S0{vh1, gh1}, S1{vh1b, gh1b};
+      const Grids g1{A, B, C}, g2{B, C, D}, g3s{C, D, E};
+      EvPair ev{}, evt{}, eva{};
+      if (op.timing) { ev = ev_get(); evt = ev_get(); eva = ev_get(); hipEventRecord(ev.first, s); hipEventRecord(eva.first, s); }
+      const bool beside = !(op.debug & PF_DBG_WALLS_ONE_STREAM);
       hipStream_t sw = beside ? s_edge : s_main; // the bricks (or the generic wall blocks) and the first step of the single-step tiles: beside the alike blocks
       if (beside) { HIPCHK(hipEventRecord(ev_pre, s_main)); HIPCHK(hipStreamWaitEvent(s_edge, ev_pre, 0)); }
       // ---- step n: single-step tiles and the box's own nodes A, B -> C; the frame's bricks A, B -> C, D, E (all three steps); wall regions
       // A, B -> C, D (x / y regions with three-step tables: -> C, D, E); box A, B -> D, E
-      u0_src = A; u1 = B; u0 = C;
-      tb3_src_n = n;
-      launch_dirty_tiles(sw);
-      bnd_sel = wl_rest; bs_vout = vh1b; bs_gout = gh1b;
-      ub[0] = T1; ub[2] = X2;
-      launch_rigid(sw, {0, wl_nrest});
-      launch_bricks(sw, A, B, C, D, E, X2, X1, T1, T2, T3, 3);
+      launch_dirty_tiles(sw, g1);
+      launch_rigid(sw, g1, Bnd{T1, X2, S0, S1, wl_rest, 0, 0}, {0, wl_nrest});
+      launch_bricks(sw, A, B, C, D, E, X2, X1, T1, T2, T3, S0, S1, 3);
       // receivers read u^n (B), the source goes into u^{n+1} (C) of its single-step tile, which that tile's first step (above, same stream) has
       // written and only its second step (after the box kernel) reads: the launch rides beside the walls instead of in the serial tail
-      launch_io(sw, n, true, src_range()); // (sources: unless k_tb3<..., SRC> adds them itself, launch_tb3_src)
-      // (debug 0x10000, an experiment: the alike blocks too beside k_tb3 instead of before it)
-      hipStream_t sa = (beside && (op.debug & 0x10000)) ? s_edge : s;
+      launch_io(sw, g1, n, true, src_range()); // (sources: unless k_tb3<..., SRC> adds them itself, launch_tb3_src)
+      // (PF_DBG_WALLS_BESIDE_BOX, an experiment: the alike blocks too beside k_tb3 instead of before it)
+      hipStream_t sa = (beside && (op.debug & PF_DBG_WALLS_BESIDE_BOX)) ? s_edge : s;
       const unsigned g3 = wall_g3(); // launch groups that take all three steps in this pass
-      if (g3) launch_walls_x(sa, sw, A, B, C, D, E, X2, X1, T1, T2, T3, 3, g3);
-      if (0xfu & ~g3) launch_walls_x(sa, sw, A, B, C, D, nullptr, X2, X1, T1, T2, nullptr, 2, 0xfu & ~g3);
+      if (g3) launch_walls_x(sa, sw, A, B, C, D, E, X2, X1, T1, T2, T3, S0, S1, 3, g3);
+      if (0xfu & ~g3) launch_walls_x(sa, sw, A, B, C, D, nullptr, X2, X1, T1, T2, nullptr, S0, S1, 2, 0xfu & ~g3);
       // (the main stream joins the edge stream -- bricks, the single-step tiles' first step, receivers / source: done long before the wall launches
       // end -- BEFORE the box kernel: behind it the cross-stream wait would sit in front of the tail's first launch, 15 us of nothing)
       if (beside) { HIPCHK(hipEventRecord(ev_edge, s_edge)); HIPCHK(hipStreamWaitEvent(s_main, ev_edge, 0)); }
       if (op.timing) hipEventRecord(evt.first, s);
-      launch_tb3(s, A, B, C, D, E);
+      launch_tb3(s, n, A, B, C, D, E);
       if (op.timing) { hipEventRecord(evt.second, s); tb2_ev.push_back(evt); hipEventRecord(eva.second, s); air_ev.push_back(eva); }
       if (ring_fill == 0) ring_n0 = n;
       ring_fill++; steps_done++;
-      if (op.timing) { hipEventRecord(ev.second, s); step_ev.push_back(ev); ev = get_ev(); hipEventRecord(ev.first, s); }
-      std::swap(vh1, vh1b); std::swap(gh1, gh1b); // the state after two (bricks, three-step regions: three) steps (the nodes inside the box: after their first)
-      // ---- step n+1: single-step tiles and their nodes B, C -> D (the regions and the box have theirs)
-      u0_src = B; u1 = C; u0 = D;
-      launch_dirty_tiles(s);
-      bs_vout = bs_gout = nullptr;
-      ub[0] = T2; ub[2] = X1; // u2b = u^n of the node; its u^{n+2} where the regions put theirs
-      launch_rigid(s, {0, wl_nrest});
-      bnd_sel = nullptr;
+      if (op.timing) { hipEventRecord(ev.second, s); step_ev.push_back(ev); ev = ev_get(); hipEventRecord(ev.first, s); }
+      // ---- step n+1: single-step tiles and their nodes B, C -> D (the regions and the box have theirs); branch state from here on: S1 -- after two
+      // (bricks, three-step regions: three) steps, the nodes inside the box: after their first
+      launch_dirty_tiles(s, g2);
+      launch_rigid(s, g2, Bnd{T2, X1, S1, S1, wl_rest, 0, 0}, {0, wl_nrest}); // u2b = u^n of the node; its u^{n+2} where the regions put theirs
       // Nothing left to step after the box kernel -- no tile steps singly (sources inside k_tb3_src), every region took its three steps --: the
       // readouts of steps n+1 and n+2 (u^{n+1} from C, u^{n+2} from D) are ONE launch instead of two dependent ones
       bool third_left = false; // does a wall region still have its third step to take?
       for (int gi = 0; gi < 4; gi++) third_left = third_left || ((((0xfu & ~g3) >> gi) & 1u) && wl_grp[gi].nreg > 0);
-      const bool io_merged = src_in_kernel() && tb_ndirty == 0 && wl_nrest == 0 && !third_left && !op.timing && !(op.debug & 0x80000) && ring_fill + 2 <= ring_depth;
-      if (io_merged) launch_io(s, n + 1, true, Range{0, 0}, nullptr, D);
-      else launch_io(s, n + 1, true, src_range()); // receivers read u^{n+1} (C: shell, single-step tiles and the tiles that hold a receiver have it); source into u^{n+2} (D)
+      const bool io_merged = src_in_kernel() && tb_ndirty == 0 && wl_nrest == 0 && !third_left && !op.timing && !(op.debug & PF_DBG_THIRD_STEP_LISTS) && ring_fill + 2 <= ring_depth;
+      if (io_merged) launch_io(s, g2, n + 1, true, Range{0, 0}, nullptr, D);
+      else launch_io(s, g2, n + 1, true, src_range()); // receivers read u^{n+1} (C: shell, single-step tiles and the tiles that hold a receiver have it); source into u^{n+2} (D)
       ring_fill++; steps_done++;
-      if (op.timing) { hipEventRecord(ev.second, s); step_ev.push_back(ev); ev = get_ev(); hipEventRecord(ev.first, s); eva = get_ev(); hipEventRecord(eva.first, s); }
+      if (op.timing) { hipEventRecord(ev.second, s); step_ev.push_back(ev); ev = ev_get(); hipEventRecord(ev.first, s); eva = ev_get(); hipEventRecord(eva.first, s); }
       // ---- step n+2: what of the shell has not taken it yet and the single-step tiles, C, D -> E as ONE single step
       // (node values: u^{n+1} in T1, u^{n+2} in T2 -> u^{n+3} into T3; branch state in place)
-      u0_src = C; u1 = D; u0 = E;
-      ub[0] = T3; ub[1] = T2; ub[2] = T1;
-      if (!(op.debug & 0x80000)) {
+      const Bnd b3{T3, T1, S1, S1, nullptr, 0, 0};
+      if (!(op.debug & PF_DBG_THIRD_STEP_LISTS)) {
          // ... as wall regions too, in their one-step form (k_wall2<..., NS = 1>: pencils instead of a six-neighbour gather per node and
-         // of the strided strip kernels; branch state in place): 4.1 GB -> 2.x GB per third step at 1024^3.  debug 0x80000: the list kernels
+         // of the strided strip kernels; branch state in place): 4.1 GB -> 2.x GB per third step at 1024^3.  PF_DBG_THIRD_STEP_LISTS: the list kernels
          // (the edge stream is only needed for generic blocks of regions that have a third step left: none with bricks and three-step regions --
          // and every event between two launches of the main stream costs microseconds of a tail that is all launch gaps)
          bool gen3 = false;
          for (int gi = 0; gi < 4; gi++) gen3 = gen3 || (((0xfu & ~g3) >> gi) & 1u && wl_grp[gi].nblk[1] > 0);
          if (beside && gen3) { HIPCHK(hipEventRecord(ev_pre, s_main)); HIPCHK(hipStreamWaitEvent(s_edge, ev_pre, 0)); }
-         if (0xfu & ~g3) launch_walls_x(s, gen3 ? sw : s, C, D, E, nullptr, nullptr, T1, T2, T3, nullptr, nullptr, 1, 0xfu & ~g3);
-         launch_dirty_tiles(s);
+         if (0xfu & ~g3) launch_walls_x(s, gen3 ? sw : s, C, D, E, nullptr, nullptr, T1, T2, T3, nullptr, nullptr, S1, S1, 1, 0xfu & ~g3);
+         launch_dirty_tiles(s, g3s);
          if (op.timing) { hipEventRecord(eva.second, s); air_ev.push_back(eva); }
-         bnd_sel = wl_rest;
-         launch_rigid(s, {0, wl_nrest});
-         bnd_sel = nullptr;
+         launch_rigid(s, g3s, b3.with(wl_rest), {0, wl_nrest});
          if (beside && gen3) { HIPCHK(hipEventRecord(ev_edge, s_edge)); HIPCHK(hipStreamWaitEvent(s_main, ev_edge, 0)); }
       } else {
-         launch_shell(s);
+         launch_shell(s, g3s);
          if (op.timing) { hipEventRecord(eva.second, s); air_ev.push_back(eva); }
-         launch_rigid(s, {0, Nb});
-         launch_fd(s, {0, Nbl});
+         launch_rigid(s, g3s, b3, {0, Nb});
+         launch_fd(s, g3s, b3, {0, Nbl});
       }
-      if (!io_merged) launch_io(s, n + 2, true, src_range());
+      if (!io_merged) launch_io(s, g3s, n + 2, true, src_range());
       ring_fill++; steps_done++;
+      // the state after the triple
       ub[0] = T1; ub[1] = T3; ub[2] = T2; ubx[0] = X1; ubx[1] = X2; // (newest in ub[1], the one before in ub[2], ub[0] free: the single steps' convention)
-      u0_src = nullptr; u0 = D; u1 = E; bufD = A; bufE = B; // bufC stays the u^{n+1} grid ...
-      tb3_pick();                                           // ... on the placed cycle; off it: back towards it
+      vh1 = S1.v; gh1 = S1.g; vh1b = S0.v; gh1b = S0.g;
+      u0 = D; u1 = E; bufD = A; bufE = B; // bufC stays the u^{n+1} grid ...
+      tb3_pick();                         // ... on the placed cycle; off it: back towards it
       if (op.timing) { hipEventRecord(ev.second, s); step_ev.push_back(ev); }
       HIPCHK(hipGetLastError());
       if (ring_fill == ring_depth) return flush();
@@ -190,6 +228,6 @@
       if (!tb2_geom || (op.slab_first && op.slab_last)) return 1; // not an error: this engine keeps stepping singly
       bufC = (Real *)g2; bufD = (Real *)g3;
       tb2_slab = true;
-      if (!wl_on && !(op.debug & 0x10000000)) { int rcw = init_walls(true); if (rcw) return rcw; }
+      if (!wl_on && !(op.debug & PF_DBG_NO_WALL_REGIONS)) { int rcw = init_walls(true); if (rcw) return rcw; }
       return PF_OK;
    }

@@ -19,11 +19,11 @@
    }
    // Three steps per pass where they can be had: single-domain 7-point engines in file-order storage, 64-lane row segments, the
    // shell as wall regions (init_walls).  The box then keeps THREE cells from anything that is not a plain air update (k_tb3
-   // computes u^{n+1} two cells beyond it).  Anything else: pairs as before.  debug 0x20000: never triples.
+   // computes u^{n+1} two cells beyond it).  Anything else: pairs as before.  PF_DBG_NO_TRIPLES: never triples.
    int init_tb2() {
       tb3 = tb3_geom = tb3_slab = false;
       const bool single = op.slab_first && op.slab_last;
-      if (!fcc && !swz && !(op.debug & (0x20000 | 0x300 | 0x10000000)) && vbase != 41) {
+      if (!fcc && !swz && !(op.debug & (PF_DBG_NO_TRIPLES | PF_DBG_LW32 | PF_DBG_LW16 | PF_DBG_NO_WALL_REGIONS)) && vbase != 41) {
          int rc = init_tb2_impl(true);
          if (rc) return rc;
          if (single && tb2 && wl_on) { tb3 = true; return PF_OK; }
@@ -38,7 +38,7 @@
       tb2 = tb2_geom = tb2_slab = false;
       tb_nsrct = 0;
       const bool single = op.slab_first && op.slab_last;
-      if (op.energy || (op.debug & 0x4000)) return PF_OK; // 0x4000: single steps only
+      if (op.energy || (op.debug & PF_DBG_SINGLE_STEPS)) return PF_OK;
       // exchanged axes (rooms): the pair kernels work in storage coordinates and take their neighbours in the FILE's order (template
       // flag SWZ: 64-lane row segments, single-domain engines); 7-point: k_tb2_reg / k_tb1_tile / k_air_zstrip<..., SWZ>
       if (swz && !single) return PF_OK;
@@ -83,8 +83,8 @@
       {
          int64_t best = -1;
          for (int lw : {64, 32, 16}) {
-            if (op.debug & 0x300) { if (lw != ((op.debug & 0x100) ? 32 : 16)) continue; } // tuning override (as pick_lw)
-            else if (((op.debug & 0x400) || swz || triple) && lw != 64) continue; // (exchanged axes: the SWZ instantiations exist for 64-lane segments only; such rooms have long rows; k_tb3: 64 lanes)
+            if (op.debug & (PF_DBG_LW32 | PF_DBG_LW16)) { if (lw != ((op.debug & PF_DBG_LW32) ? 32 : 16)) continue; } // tuning override (as pick_lw)
+            else if (((op.debug & PF_DBG_LW64) || swz || triple) && lw != 64) continue; // (exchanged axes: the SWZ instantiations exist for 64-lane segments only; such rooms have long rows; k_tb3: 64 lanes)
             const int TC = (lw - 2 * hl) * V;
             int z1 = (int)((Nz - mz1) / 4 * 4);
             const int nz = z1 - tbz0, rem = nz % TC;
@@ -97,12 +97,12 @@
       }
       // Wall regions (init_walls): a column strip costs one 128-byte line per row whatever its width, but its pencils live in
       // registers -- a sliver cut off the box is shared between the two strips instead of all going to the right one.
-      if (!fcc && !(op.debug & 0x10000000)) { // (slab engines too: init_walls(true))
+      if (!fcc && !(op.debug & PF_DBG_NO_WALL_REGIONS)) { // (slab engines too: init_walls(true))
          const int z1full = (int)((Nz - mz1) / 4 * 4);
          if (tbz1 < z1full) {
             const int rem = z1full - tbz1;
             // (the shift that lets both strips become wall regions with the fewest pencils cut in two; else the most even one)
-            const bool ps = (op.debug & 0x2000000) != 0 || sizeof(Real) != 4;
+            const bool ps = (op.debug & PF_DBG_STRIPS_SPLIT) != 0 || sizeof(Real) != 4;
             int best_sh = 0, best_need = 1 << 30;
             for (int sh = 0; sh <= rem; sh += 4) {
                const int lo = wl_lo_option(tbz0 + sh, ps), hi = wl_hi_option(tbz1 + sh, ps);
@@ -346,8 +346,8 @@
       // kernel does the RIGID update only and leaves the result in u0b[li]; the branch ODEs of the lossy ones follow in
       // extra threads of the k_boundary launch, dense over the compact arrays (mode 2).  (Doing the ODEs inside the strip kernel as well was bit-identical
       // but slower -- they ran on the few lanes per wave that hold a node, 2.92 vs 2.59 ms per step -- and was retired.)
-      // debug 0x20000000: mode 0, the list kernel visits every boundary node (the round-1 arrangement; also the fallback).
-      zs_mode = fcc ? 0 : ((op.debug & 0x20000000) ? 0 : 2);
+      // PF_DBG_BND_ALL_NODES: mode 0, the list kernel visits every boundary node (the round-1 arrangement; also the fallback).
+      zs_mode = fcc ? 0 : ((op.debug & PF_DBG_BND_ALL_NODES) ? 0 : 2);
       if (Nb > 0 && !tb_xr.empty() && zs_mode == 2 && Nbl < ((int64_t)1 << 31)) {
          const int xb = tb_xr.front().first, xe = tb_xr.back().second;
          constexpr int V = pf::VecOf<Real>::V;

@@ -141,7 +141,6 @@ template <typename Real> struct Engine : EngineBase {
    bool tb2_probe = false;                                // launch_tb2 under its creation-time name (k_tb2_reg<..., PROBE>)
    std::vector<Real *> own_list;
    uint8_t *mask = nullptr;      // skip-mask (boundary nodes + ghost z + pad + parity)
-   Real *v1_dst = nullptr;       // autotune: destination of the barrier-free 7-point kernel (null = in place)
    int lw_force = 0;             // autotune: lanes per row segment of the barrier-free kernels (0 = pick_lw's rule)
    int order_force = -1;         // autotune: tile order of the marching kernels (-1 = swizzle_mode's rule; 0 plain, 2 XCD-banded)
    float tune_ms[3] = {0, 0, 0}; // measured at creation: lean / barrier-free / blocked pair (per step), ms
@@ -227,9 +226,28 @@ template <typename Real> struct Engine : EngineBase {
    static constexpr int fcc_wt = 8; // waves per workgroup of k_tb2_fcc_x (two of them halo providers)
    int64_t sh_ntiles = 0;
    int sh_nyt = 0, sh_nzt = 0;
-   const Real *u0_src = nullptr;                          // out-of-place single-step launches read u^{n-1} here
-   int lean_yt0 = 0, lean_nyt = -1;                       // row-strip launches of the lean kernel (-1: all tiles)
-   int lean_x2_begin = 0, lean_x2_end = 0;                // a second x slab for the next lean launch (launch_shell_rest)
+   Real *u0_src = nullptr;                                // between the split-phase steps of a slab's pair / triple: u^{n-1} lies here, u0 is the grid being written
+   // What one launch reads and writes is an argument of its launcher, never an engine field.
+   // The grids of one step: old = u^{n-1}, cur = u^n -> nxt = u^{n+1}; in place (the single steps): old == nxt.  (cur is written too: its ghost cells, by the flips.)
+   struct Grids {
+      Real *old, *cur, *nxt;
+      bool in_place() const { return old == nxt; }
+      const Real *src() const { return in_place() ? nullptr : old; } // for the kernels that take "null: u^{n-1} is where u^{n+1} goes"
+   };
+   Grids grids() const { return {u0_src ? u0_src : u0, u1, u0}; }
+   struct BranchState { Real *v, *g; };
+   // What a boundary launch needs beyond the grids: node values (u0b receives u^{n+1}, u2b holds u^{n-1}; may be one buffer), branch state in / out
+   // (in place: the same), sel: the launch visits sel[range] of the boundary list (null: the range itself), the planes whose folded ghost row
+   // launch_fold_row writes first, [fold_b, fold_e).
+   struct Bnd {
+      Real *u0b; const Real *u2b;
+      BranchState in, out;
+      const int32_t *sel;
+      int fold_b, fold_e;
+      Bnd with(const int32_t *list) const { Bnd b = *this; b.sel = list; return b; }
+   };
+   Bnd bnd(int fold_b, int fold_e) const { return {ub[0], ub[2], {vh1, gh1}, {vh1, gh1}, nullptr, fold_b, fold_e}; } // a plain single step
+   struct LeanExtra { int x2_begin = 0, x2_end = 0, nyt = -1, yt0 = 0; }; // a lean launch's second x slab [x2_begin, x2_end); its row strips: tiles [0, nyt) and [yt0, all) (-1: all tiles)
    // boundary nodes inside the column strips are updated by k_air_zstrip itself (it streams their lines anyway; in
    // the list kernel the floor / ceiling nodes of a box room cost half of the whole boundary pass)
    uint32_t *zs_map = nullptr;                            // per strip vector: first node number << 4 | node bits (ZStripParams::zvec)
@@ -241,7 +259,6 @@ template <typename Real> struct Engine : EngineBase {
                                                           // 2: strip kernel does the rigid update, extra threads of the k_boundary launch the branch ODEs (default)
    int32_t *zs_fd = nullptr;                              // mode 2: the lossy nodes (indices into the lossy arrays) inside the strips
    int64_t zs_nfd = 0;
-   const int32_t *bnd_sel = nullptr;                      // launch_boundary visits bnd_sel[range] when set
    // wall regions (pf_wall.h): the shell of a blocked pair -- wall layers, ABC cells, ghost mirrors -- stepped in pairs too
    bool wl_on = false;
    int32_t *edge_sel3 = nullptr; int64_t n_edge_sel3 = 0; bool edge_sel3_failed = false; // slab triples: the nodes of both sides' edge planes, one list (step_begin)
@@ -283,14 +300,20 @@ template <typename Real> struct Engine : EngineBase {
    int wl_chunk_want[2] = {0, 0};                         // march steps per block the x / y regions' and the column strips' launches aim for (init_walls)
    size_t wl_brk_lds = 0;                                 // dynamic LDS of a brick launch (the largest brick)
    Real *vh1b = nullptr, *gh1b = nullptr;                 // the other half of the double-buffered branch state
-   Real *bs_vout = nullptr, *bs_gout = nullptr;           // launch_boundary: where the new branch state goes (null: in place)
    // energy diagnostic (pf_energy.h)
    Real *Lu = nullptr, *vh_old = nullptr, *u2in = nullptr;
    double *d_acc = nullptr, *d_DEF = nullptr;
    double en_h = 0, en_c = 0, en_Ts = 0;
    bool en_ready = false;
    // timing
-   std::vector<std::pair<hipEvent_t, hipEvent_t>> air_ev, step_ev, tb2_ev, ev_pool;
+   typedef std::pair<hipEvent_t, hipEvent_t> EvPair;
+   std::vector<EvPair> air_ev, step_ev, tb2_ev, ev_pool;
+   EvPair ev_get() { // a pair from the pool, or a new one
+      EvPair e{};
+      if (!ev_pool.empty()) { e = ev_pool.back(); ev_pool.pop_back(); }
+      else { hipEventCreate(&e.first); hipEventCreate(&e.second); }
+      return e;
+   }
    pf_timing tm{};
 
    ~Engine() override { destroy(); }
@@ -424,12 +447,12 @@ template <typename Real> struct Engine : EngineBase {
       swz = false;
       const bool single = op.slab_first && op.slab_last, ext = op.ext_u0 && op.ext_u1;
       const int vb = op.air_variant & 255;
-      if (op.debug & 0x1000) {
+      if (op.debug & PF_DBG_SWZ_ON) {
          if (op.energy) return set_err(PF_ERR_ARG, "debug 0x1000 (axes exchanged in storage): no energy diagnostic");
          swz = true;
          return PF_OK;
       }
-      if ((op.debug & 0x2000) || !single || ext || op.energy || vb == 41 || vb == 42) return PF_OK; // (42: file order unless the caller says otherwise)
+      if ((op.debug & PF_DBG_SWZ_OFF) || !single || ext || op.energy || vb == 41 || vb == 42) return PF_OK; // (42: file order unless the caller says otherwise)
       int64_t counts[2];
       swz = pf__axis_exchange_pays(&sd, counts) != 0;
       if (counts[0] + counts[1] > 0 && getenv("PFFDTD_VERBOSE") && atoi(getenv("PFFDTD_VERBOSE")) > 0)
@@ -665,7 +688,7 @@ template <typename Real> struct Engine : EngineBase {
       // launches even on launch-bound grids (234x154x85: 0.0503 vs 0.0473 ms/step, 256^3: 0.0951 vs 0.0921) -- the gaps
       // between dependent kernels are the same inside a graph, and the counter-tick node adds one -- so it is opt-in
       // (debug 0x800000), kept bit-identical by the tests.
-      graph_ok = (op.debug & 0x800000) && op.slab_first && op.slab_last && !tb2 && !op.timing && !op.energy;
+      graph_ok = (op.debug & PF_DBG_GRAPH) && op.slab_first && op.slab_last && !tb2 && !op.timing && !op.energy;
       if (getenv("PFFDTD_VERBOSE") && atoi(getenv("PFFDTD_VERBOSE")) > 0)
          fprintf(stderr, "pffdtd_hip: engine on device %d, %ldx%ldx%ld %s %s, interior path: %s%s, numerics: %s, %d-lane row segments\n", op.device, (long)Nx, (long)Ny, (long)Nz,
                  fcc ? "13-point" : "7-point", sizeof(Real) == 4 ? "fp32" : "fp64",
@@ -689,18 +712,19 @@ template <typename Real> struct Engine : EngineBase {
       if (!d_ctr) HIPCHK(hipMalloc((void **)&d_ctr, 2 * sizeof(int64_t)));
       hipGraph_t g = nullptr;
       HIPCHK(hipStreamBeginCapture(s_main, hipStreamCaptureModeThreadLocal));
+      Real *ua = u0, *uc = u1, *x[3] = {ub[0], ub[1], ub[2]};
       for (int k = 0; k < 6; k++) { // the launches of step_single, with the device counters instead of n / ring_fill
-         fold_x0 = 0; fold_x1 = (int)Nx;
-         launch_pre(s_main);
-         launch_air(s_main, 1, (int)Nx - 1);
-         launch_abc(s_main, {0, Nba});
-         launch_rigid(s_main, {0, Nb});
-         launch_fd(s_main, {0, Nbl});
-         launch_io(s_main, 0, true, {0, Ns}, d_ctr);
+         const Grids gr{ua, uc, ua};
+         const Bnd b{x[0], x[2], {vh1, gh1}, {vh1, gh1}, nullptr, 0, (int)Nx};
+         launch_pre(s_main, gr);
+         launch_air(s_main, gr, 1, (int)Nx - 1);
+         launch_abc(s_main, gr, {0, Nba});
+         launch_rigid(s_main, gr, b, {0, Nb});
+         launch_fd(s_main, gr, b, {0, Nbl});
+         launch_io(s_main, gr, 0, true, {0, Ns}, d_ctr);
          hipLaunchKernelGGL(pf::k_ctr_tick, dim3(1), dim3(1), 0, s_main, d_ctr);
-         rotate();
+         std::swap(ua, uc); std::rotate(x, x + 2, x + 3); // (as rotate(): six of them are one period, the engine's own state stays)
       }
-      rot_count -= 6; // nothing ran: the six rotations above only walked the pointers through one period
       const hipError_t e = hipStreamEndCapture(s_main, &g);
       if (e != hipSuccess || !g) { graph_ok = false; (void)hipGetLastError(); return PF_OK; } // capture unsupported: plain launches
       if (hipGraphInstantiate(&gexec, g, nullptr, nullptr, 0) != hipSuccess) { gexec = nullptr; graph_ok = false; (void)hipGetLastError(); }
@@ -734,22 +758,19 @@ template <typename Real> struct Engine : EngineBase {
    // one whole step on the main stream, in the reference CPU engine's order (cpu_engine.h:127-326)
    int step_single(int64_t n) {
       if (n < 0 || n >= Nt) return set_err(PF_ERR_ARG, "step %ld outside [0,Nt=%ld)", (long)n, (long)Nt);
-      std::pair<hipEvent_t, hipEvent_t> ev{};
-      if (op.timing) {
-         if (!ev_pool.empty()) { ev = ev_pool.back(); ev_pool.pop_back(); }
-         else { hipEventCreate(&ev.first); hipEventCreate(&ev.second); }
-         hipEventRecord(ev.first, s_main);
-      }
-      fold_x0 = 0; fold_x1 = (int)Nx;
-      launch_pre(s_main);
+      EvPair ev{};
+      if (op.timing) { ev = ev_get(); hipEventRecord(ev.first, s_main); }
+      const Grids g = grids();
+      const Bnd b = bnd(0, (int)Nx);
+      launch_pre(s_main, g);
       // (The fused interior kernels skip the boundary nodes' cells and the boundary pass reads u^n only, so the two commute --
       // but running the pass beside the interior kernel on the second stream gains nothing on the rooms: Musikverein 3.87 vs
       // 3.82 ms per step one after the other, CTK 0.547-0.563 vs 0.556-0.558, round 4.)
-      launch_air(s_main, 1, (int)Nx - 1);
-      launch_abc(s_main, {0, Nba});
-      launch_rigid(s_main, {0, Nb});
-      launch_fd(s_main, {0, Nbl});
-      launch_io(s_main, n, true, {0, Ns});
+      launch_air(s_main, g, 1, (int)Nx - 1);
+      launch_abc(s_main, g, {0, Nba});
+      launch_rigid(s_main, g, b, {0, Nb});
+      launch_fd(s_main, g, b, {0, Nbl});
+      launch_io(s_main, g, n, true, {0, Ns});
       if (op.timing) { hipEventRecord(ev.second, s_main); step_ev.push_back(ev); }
       HIPCHK(hipGetLastError());
       rotate();
@@ -793,8 +814,9 @@ template <typename Real> struct Engine : EngineBase {
          if (Ns) hipLaunchKernelGGL(pf::k_energy_in<Real>, g1(Ns, 64), dim3(64), 0, s, u0, u2in, d_in, d_insig, Ns, Nt, n, 0, d_acc);
          if (Nbl) HIPCHK(hipMemcpyAsync(vh_old, vh1, sizeof(Real) * round_up(Nbl, 64) * PF_MMB, hipMemcpyDeviceToDevice, s));
          // the step itself (unfused sequence), with Lu = L(u1) taken after the ghost flips
-         fold_x0 = 0; fold_x1 = (int)Nx;
-         launch_pre(s);
+         const Grids g = grids();
+         const Bnd b = bnd(0, (int)Nx);
+         launch_pre(s, g);
          if (fcc) {
             hipLaunchKernelGGL((pf::k_lap_air<Real, true>), g3, dim3(256), 0, s, u1, Lu, mask, Nx, Ny, Nz, P, plane);
             if (Nb) hipLaunchKernelGGL((pf::k_lap_bn<Real, true>), g1(Nb, 256), dim3(256), 0, s, u1, Lu, d_bn, d_adj, P, plane, Nb);
@@ -802,11 +824,11 @@ template <typename Real> struct Engine : EngineBase {
             hipLaunchKernelGGL((pf::k_lap_air<Real, false>), g3, dim3(256), 0, s, u1, Lu, mask, Nx, Ny, Nz, P, plane);
             if (Nb) hipLaunchKernelGGL((pf::k_lap_bn<Real, false>), g1(Nb, 256), dim3(256), 0, s, u1, Lu, d_bn, d_adj, P, plane, Nb);
          }
-         launch_air(s, 1, (int)Nx - 1);
-         launch_abc(s, {0, Nba});
-         launch_rigid(s, {0, Nb});
-         launch_fd(s, {0, Nbl});
-         launch_io(s, n, true, {0, Ns});
+         launch_air(s, g, 1, (int)Nx - 1);
+         launch_abc(s, g, {0, Nba});
+         launch_rigid(s, g, b, {0, Nb});
+         launch_fd(s, g, b, {0, Nbl});
+         launch_io(s, g, n, true, {0, Ns});
          // after the step (u0 = u^{n+1} until the rotation)
          if (Nbl) hipLaunchKernelGGL(pf::k_energy_loss<Real>, g1(Nbl, 256), dim3(256), 0, s, vh_old, vh1, d_ssaf, d_mat, d_Mb, d_DEF, Nbl, d_acc);
          if (Nba) hipLaunchKernelGGL(pf::k_energy_abcloss<Real>, g1(Nba, 256), dim3(256), 0, s, u0, u2ba, d_bna, d_Q, Nba, d_acc);
@@ -956,7 +978,7 @@ template <typename Real> struct Engine : EngineBase {
       if (rc) return rc;
       const Real *src = which == 0 ? (pair_phase > 0 ? (const Real *)u0_src : (const Real *)u0) : u1; // mid-pair u0 already names the grid being written
       if ((lean || vg) && which == 1) { // write the virtual ghost shell out, exactly as the reference's flips would have
-         launch_flips(s_main);
+         launch_flips(s_main, grids());
          HIPCHK(hipStreamSynchronize(s_main));
       }
       if (swz) { // storage -> file order through a device-side transposition

@@ -98,15 +98,15 @@
                  cut.tile[3][0], cut.tile[3][1], cut.tile[3][2], cut.tile[4][0], cut.tile[4][1], cut.tile[4][2], cut.tile[5][0], cut.tile[5][1], cut.tile[5][2], (long)cut.nodes_owned, (long)fb_nrest, (long)Nb, (long)fb_ntiles);
       return PF_OK;
    }
-   // the bricks, both steps: A = u^{n-1}, B = u^n -> G0 = u^{n+1}, G1 = u^{n+2}; branch state vh1 / gh1 -> vh1b / gh1b (the caller swaps); node
+   // the bricks, both steps: A = u^{n-1}, B = u^n -> G0 = u^{n+1}, G1 = u^{n+2}; branch state si -> so (the caller swaps its two copies); node
    // values x2 = u^{n-1}, x1 = u^n are read, those of the steps go to O0, O1 -- buffers nobody reads during the pass
-   void launch_fcc_bricks(hipStream_t s, const Real *A, const Real *B, Real *G0, Real *G1, const Real *x2, const Real *x1, Real *O0, Real *O1, int ns) {
+   void launch_fcc_bricks(hipStream_t s, const Real *A, const Real *B, Real *G0, Real *G1, const Real *x2, const Real *x1, Real *O0, Real *O1, BranchState si, BranchState so, int ns) {
       if (!fb_nbrk) return;
       pf::BrickFccParams<Real> bp{};
       bp.A = A; bp.B = B; bp.G[0] = G0; bp.G[1] = G1; bp.O[0] = O0; bp.O[1] = O1; bp.x2 = x2; bp.x1 = x1;
       bp.plane = plane; bp.Nx = (int)Nx; bp.Ny = (int)Ny; bp.Nz = (int)Nz; bp.P = (int)P;
       bp.brk = fb_brk; bp.info = fb_info; bp.los = fb_los;
-      bp.sv_in = vh1; bp.sg_in = gh1; bp.sv_out = vh1b; bp.sg_out = gh1b;
+      bp.sv_in = si.v; bp.sg_in = si.g; bp.sv_out = so.v; bp.sg_out = so.g;
       bp.ssaf = d_ssaf; bp.mat = d_mat; bp.Mb = d_Mb; bp.mq = d_mq; bp.beta = d_beta;
       bp.lo2 = lo2; bp.sl2 = sl2; bp.l = l; bp.nmat = (int)sd.Nm; bp.ns = ns;
       const dim3 g((unsigned)fb_nbrk), b(pf::BRICK_T);
@@ -116,9 +116,9 @@
       else if (sg) hipLaunchKernelGGL((pf::k_brick_fcc<Real, pf::WALL_MC[1], true>), g, b, fb_lds, s, bp, a1, a2);
       else hipLaunchKernelGGL((pf::k_brick_fcc<Real, pf::WALL_MC[1], false>), g, b, fb_lds, s, bp, a1, a2);
    }
-   // one out-of-place step of the box's single-step tiles: u1, (u0_src old) -> u0, by k_air_fcc over its own tiles -- which store their cells
+   // one out-of-place step of the box's single-step tiles, by k_air_fcc over its own tiles -- which store their cells
    // of the box and no others (the cells around it are the bricks'; the tile's rows next to a ghost row are computed from whatever lies there)
-   void launch_box_tiles_fcc(hipStream_t s) {
+   void launch_box_tiles_fcc(hipStream_t s, const Grids &g) {
       if (fb_ntiles <= 0) return;
       pf::AirParams ap;
       ap.Ny = Ny; ap.P = P; ap.plane = plane;
@@ -126,8 +126,8 @@
       ap.swizzle = 0; ap.swz = 0;
       ap.Nx = (int)Nx; ap.Nz = (int)Nz; ap.first = op.slab_first; ap.last = op.slab_last; ap.fold = fold ? 1 : 0;
       ap.cy0 = tby0; ap.cy1 = tby1; ap.cz0 = tbz0; ap.cz1 = tbz1;
-      if (sg) hipLaunchKernelGGL((pf::k_air_fcc<Real, 4, 4, 1, true, true, false, true, 64, true>), dim3((uint32_t)fb_ntiles), dim3(256), 0, s, u1, u0, mask, a1, a2, ap, l, u0_src, fb_tiles);
-      else hipLaunchKernelGGL((pf::k_air_fcc<Real, 4, 4, 1, false, true, false, true, 64, true>), dim3((uint32_t)fb_ntiles), dim3(256), 0, s, u1, u0, mask, a1, a2, ap, l, u0_src, fb_tiles);
+      if (sg) hipLaunchKernelGGL((pf::k_air_fcc<Real, 4, 4, 1, true, true, false, true, 64, true>), dim3((uint32_t)fb_ntiles), dim3(256), 0, s, g.cur, g.nxt, mask, a1, a2, ap, l, g.src(), fb_tiles);
+      else hipLaunchKernelGGL((pf::k_air_fcc<Real, 4, 4, 1, false, true, false, true, 64, true>), dim3((uint32_t)fb_ntiles), dim3(256), 0, s, g.cur, g.nxt, mask, a1, a2, ap, l, g.src(), fb_tiles);
    }
    // steps n and n+1 of a 13-point engine whose shell is in bricks.  Order: the first step of what no brick owns -- the box's single-step tiles
    // and the boundary nodes inside it --, the bricks (both steps; they read u^{n-1}, u^n and the old branch state only), all beside the pair
@@ -138,40 +138,35 @@
       Real *A = u0, *B = u1, *C = bufC, *D = bufD;
       // node values: X2 = u^{n-1}, X1 = u^n are only read; u^{n+1} -> T1, u^{n+2} -> T2, two buffers nobody reads during the pair
       Real *X2 = ub[2], *X1 = ub[1], *T1 = ub[0], *T2 = ubx[0];
-      auto get_ev = [&]() { std::pair<hipEvent_t, hipEvent_t> e{}; if (!ev_pool.empty()) { e = ev_pool.back(); ev_pool.pop_back(); } else { hipEventCreate(&e.first); hipEventCreate(&e.second); } return e; };
-      std::pair<hipEvent_t, hipEvent_t> ev{}, ev2{}, evt{}, eva{};
-      if (op.timing) { ev = get_ev(); ev2 = get_ev(); evt = get_ev(); eva = get_ev(); hipEventRecord(ev.first, s); hipEventRecord(eva.first, s); }
-      const bool beside = !(op.debug & 0x4000000); // (debug 0x4000000: everything on the main stream)
+      // branch state: the bricks and the first step of the box's nodes read S0 and write S1; the nodes' second step S1 in place
+      const BranchState S0{vh1, gh1}, S1{vh1b, gh1b};
+      const Grids g1{A, B, C}, g2{B, C, D};
+      EvPair ev{}, ev2{}, evt{}, eva{};
+      if (op.timing) { ev = ev_get(); ev2 = ev_get(); evt = ev_get(); eva = ev_get(); hipEventRecord(ev.first, s); hipEventRecord(eva.first, s); }
+      const bool beside = !(op.debug & PF_DBG_WALLS_ONE_STREAM); // (else everything on the main stream)
       hipStream_t sw = beside ? s_edge : s_main;
       if (beside) { HIPCHK(hipEventRecord(ev_pre, s_main)); HIPCHK(hipStreamWaitEvent(s_edge, ev_pre, 0)); }
-      u0_src = A; u1 = B; u0 = C;
-      tb3_src_n = n;
-      launch_box_tiles_fcc(sw);
-      bnd_sel = fb_rest; bs_vout = vh1b; bs_gout = gh1b;
-      ub[0] = T1; ub[2] = X2;
-      launch_rigid(sw, {0, fb_nrest});
-      launch_fcc_bricks(sw, A, B, C, D, X2, X1, T1, T2, 2);
+      launch_box_tiles_fcc(sw, g1);
+      launch_rigid(sw, g1, Bnd{T1, X2, S0, S1, fb_rest, 0, 0}, {0, fb_nrest});
+      launch_fcc_bricks(sw, A, B, C, D, X2, X1, T1, T2, S0, S1, 2);
       // (with per-launch events on, the pair kernel waits for the bricks: its recorded duration is the kernel's own, not the overlap's)
       if (op.timing && beside) { HIPCHK(hipEventRecord(ev_edge, s_edge)); HIPCHK(hipStreamWaitEvent(s, ev_edge, 0)); }
       if (op.timing) hipEventRecord(evt.first, s);
-      launch_tb2(s, A, B, C, D);
+      launch_tb2(s, n, A, B, C, D);
       if (op.timing) { hipEventRecord(evt.second, s); tb2_ev.push_back(evt); hipEventRecord(eva.second, s); air_ev.push_back(eva); }
       if (beside && !op.timing) { HIPCHK(hipEventRecord(ev_edge, s_edge)); HIPCHK(hipStreamWaitEvent(s_main, ev_edge, 0)); }
-      launch_io(s, n, true, src_range()); // (receivers read u^n; the source goes into u^{n+1}, which only the second step below reads)
+      launch_io(s, g1, n, true, src_range()); // (receivers read u^n; the source goes into u^{n+1}, which only the second step below reads)
       if (ring_fill == 0) ring_n0 = n;
       ring_fill++; steps_done++;
       if (op.timing) { hipEventRecord(ev.second, s); step_ev.push_back(ev); hipEventRecord(ev2.first, s); }
-      std::swap(vh1, vh1b); std::swap(gh1, gh1b); // the state after the pair (the nodes inside the box: after their first step)
-      u0_src = B; u1 = C; u0 = D;
-      launch_box_tiles_fcc(s);
-      bs_vout = bs_gout = nullptr;
-      ub[0] = T2; ub[2] = X1; // second step of the box's nodes: u2b = u^n of the node, its u^{n+2} where the bricks put theirs
-      launch_rigid(s, {0, fb_nrest});
-      ub[0] = X2; ub[1] = T2; ub[2] = T1; ubx[0] = X1; // (newest in ub[1], the one before in ub[2], ub[0] free: the single steps' convention)
-      bnd_sel = nullptr;
-      launch_io(s, n + 1, true, src_range());
+      launch_box_tiles_fcc(s, g2);
+      launch_rigid(s, g2, Bnd{T2, X1, S1, S1, fb_rest, 0, 0}, {0, fb_nrest}); // second step of the box's nodes: u2b = u^n of the node, its u^{n+2} where the bricks put theirs
+      launch_io(s, g2, n + 1, true, src_range());
       ring_fill++; steps_done++;
-      u0_src = nullptr; u0 = C; u1 = D; bufC = A; bufD = B;
+      // the state after the pair
+      u0 = C; u1 = D; bufC = A; bufD = B;
+      ub[0] = X2; ub[1] = T2; ub[2] = T1; ubx[0] = X1; // (newest in ub[1], the one before in ub[2], ub[0] free: the single steps' convention)
+      vh1 = S1.v; gh1 = S1.g; vh1b = S0.v; gh1b = S0.g;
       if (op.timing) { hipEventRecord(ev2.second, s); step_ev.push_back(ev2); }
       HIPCHK(hipGetLastError());
       if (ring_fill == ring_depth) return flush();

@@ -1,5 +1,6 @@
 // pf_engine_launch.inc -- part of `template <typename Real> struct Engine` (pf_engine.hip includes it INSIDE the class body; not a translation unit):
-// kernel launchers (blocked kernels, single-step shell, marching / lean interior kernels, boundary pass, I/O) and Engine::step_pair.
+// kernel launchers (blocked kernels, single-step shell, marching / lean interior kernels, boundary pass, I/O).  Each takes what it reads and
+// writes as arguments (Engine::Grids, Engine::Bnd) and names no state grid or node buffer of the engine itself.
    pf::Tb2Params tile_params() const {
       pf::Tb2Params tp{};
       tp.plane = plane; tp.Nx = (int)Nx; tp.Ny = (int)Ny; tp.Nz = (int)Nz; tp.P = (int)P;
@@ -9,13 +10,13 @@
    }
    // two steps of the clean tiles
    // three steps of the clean tiles: A = u^{n-1}, B = u^n -> D = u^{n+2}, E = u^{n+3}; C: where flagged tiles leave their u^{n+1} (null: nowhere)
-   void launch_tb3(hipStream_t s, const Real *A, const Real *B, Real *C, Real *D, Real *E, bool sample = false) {
+   void launch_tb3(hipStream_t s, int64_t n, const Real *A, const Real *B, Real *C, Real *D, Real *E, bool sample = false) {
       if (tb_xr.empty() || tb_nclean <= 0) return;
       pf::Tb2Params tp = tile_params();
       tp.A = A; tp.B = B; tp.C = C; tp.D = D; tp.E = E;
       if (!(op.slab_first && op.slab_last)) tp.band |= 2; // a slab: the planes beside the box read the u^{n+1} of its first and last plane
       sample = sample && tb_sample && tb_nsample > 0;
-      const bool forked = !sample && fork_tb3_src<3>(s, A, B, C, D, E);
+      const bool forked = !sample && fork_tb3_src<3>(s, n, A, B, C, D, E);
       tp.tiles = sample ? tb_sample : tb_clean;
       const dim3 g((uint32_t)(sample ? tb_nsample : tb_nclean)), b(64 * tb3_wt);
       if (sg) {
@@ -36,38 +37,37 @@
    //   * slabs of a chain: 0.5 ms is as long as the slab's whole box kernel, and the edge stream carries the exchange -- Engine::step_begin
    //     launches them FIRST, on the wall regions' second stream, where they finish beside the regions (the rank that holds the source of
    //     an 8-rank chain: 0.250 -> 0.245 ms/step, its neighbours 0.241).
-   // `tb3_src_n`: the step the pass starts at (set by the step drivers).
-   int64_t tb3_src_n = 0;
-   template <int NS> bool fork_tb3_src(hipStream_t s, const Real *A, const Real *B, Real *C, Real *D, Real *E) {
+   // n: the step the pass starts at.
+   template <int NS> bool fork_tb3_src(hipStream_t s, int64_t n, const Real *A, const Real *B, Real *C, Real *D, Real *E) {
       if (!src_in_kernel() || tb2_probe || !(op.slab_first && op.slab_last) || s == s_edge) return false;
       HIPCHK_V(hipEventRecord(ev_src0, s)); HIPCHK_V(hipStreamWaitEvent(s_edge, ev_src0, 0));
-      launch_tb3_src<NS>(s_edge, A, B, C, D, E);
+      launch_tb3_src<NS>(s_edge, n, A, B, C, D, E);
       HIPCHK_V(hipEventRecord(ev_src1, s_edge));
       return true;
    }
-   template <int NS> void launch_tb3_src(hipStream_t se, const Real *A, const Real *B, Real *C, Real *D, Real *E) {
+   template <int NS> void launch_tb3_src(hipStream_t se, int64_t n, const Real *A, const Real *B, Real *C, Real *D, Real *E) {
       if (!src_in_kernel() || tb2_probe) return;
       pf::Tb2Params tp = tile_params();
       tp.A = A; tp.B = B; tp.C = C; tp.D = D; tp.E = E;
       if (!(op.slab_first && op.slab_last)) tp.band |= 2;
       tp.tiles = tb_srct;
       tp.src_idx = d_in; tp.src_sig = d_insig; tp.nsrc = (int32_t)Ns; tp.src_Nt = Nt;
-      tp.src_n = std::min(tb3_src_n, std::max<int64_t>(Nt - NS, 0)); // (the step drivers keep n + NS <= Nt)
+      tp.src_n = std::min(n, std::max<int64_t>(Nt - NS, 0)); // (the step drivers keep n + NS <= Nt)
       const dim3 g((uint32_t)tb_nsrct), b(64 * tb3_wt);
       if (sg) hipLaunchKernelGGL((pf::k_tb3_src<Real, tb3_r, tb3_wt, true, NS>), g, b, 0, se, tp, a1, a2);
       else hipLaunchKernelGGL((pf::k_tb3_src<Real, tb3_r, tb3_wt, false, NS>), g, b, 0, se, tp, a1, a2);
    }
    // the blocked kernel as the creation-time measurements see it: its four streams (k_tb3: two grids read, two written)
-   void launch_probe(hipStream_t s, const Real *A, const Real *B, Real *C, Real *D, bool sample = false) {
-      if (triples() || tb3_geom) launch_tb3(s, A, B, nullptr, C, D, sample);
-      else launch_tb2(s, A, B, C, D, sample);
+   void launch_probe(hipStream_t s, int64_t n, const Real *A, const Real *B, Real *C, Real *D, bool sample = false) {
+      if (triples() || tb3_geom) launch_tb3(s, n, A, B, nullptr, C, D, sample);
+      else launch_tb2(s, n, A, B, C, D, sample);
    }
-   void launch_tb2(hipStream_t s, const Real *A, const Real *B, Real *C, Real *D, bool sample = false) {
+   void launch_tb2(hipStream_t s, int64_t n, const Real *A, const Real *B, Real *C, Real *D, bool sample = false) {
       if (triples()) { // a pair on the triples' tiles: k_tb3's two-step form (the last two steps of a run, Engine::run)
          if (tb_xr.empty() || tb_nclean <= 0) return;
          pf::Tb2Params tp = tile_params();
          tp.A = A; tp.B = B; tp.C = C; tp.D = D; tp.E = nullptr;
-         const bool forked = fork_tb3_src<2>(s, (const Real *)A, (const Real *)B, C, D, nullptr);
+         const bool forked = fork_tb3_src<2>(s, n, A, B, C, D, nullptr);
          tp.tiles = tb_clean;
          const dim3 g((uint32_t)tb_nclean), b(64 * tb3_wt);
          if (sg) hipLaunchKernelGGL((pf::k_tb3<Real, tb3_r, tb3_wt, true, false, 2>), g, b, 0, s, tp, a1, a2);
@@ -84,7 +84,7 @@
       const dim3 g((uint32_t)(sample ? tb_nsample : tb_nclean)), b(256);
       if (fcc) {
          if (tb_lw == 64) { // 12-row tiles; k_tb2_fcc_w: half the vector arithmetic of k_tb2_fcc_x (debug 0x40000: that one, CPU-exact file order only)
-            if ((op.debug & 0x40000) && !sg && !swz) hipLaunchKernelGGL((pf::k_tb2_fcc_x<Real, 2, 8>), g, dim3(512), 0, s, tp, a1, a2);
+            if ((op.debug & PF_DBG_FCC_PAIR_R4) && !sg && !swz) hipLaunchKernelGGL((pf::k_tb2_fcc_x<Real, 2, 8>), g, dim3(512), 0, s, tp, a1, a2);
             else if (sg) { if (swz) hipLaunchKernelGGL((pf::k_tb2_fcc_w<Real, 2, 8, true, true>), g, dim3(512), 0, s, tp, a1, a2);
                            else hipLaunchKernelGGL((pf::k_tb2_fcc_w<Real, 2, 8, true, false>), g, dim3(512), 0, s, tp, a1, a2); }
             else { if (swz) hipLaunchKernelGGL((pf::k_tb2_fcc_w<Real, 2, 8, false, true>), g, dim3(512), 0, s, tp, a1, a2);
@@ -109,11 +109,11 @@
       else if (tb2_probe) hipLaunchKernelGGL((pf::k_tb2_reg<Real, 3, 4, false, 64, true>), g, b, 0, s, tp, a1, a2);
       else hipLaunchKernelGGL((pf::k_tb2_reg<Real, 3, 4, false, 64>), g, b, 0, s, tp, a1, a2);
    }
-   // one out-of-place step of the dirty tiles: u1, (u0_src old) -> u0
-   void launch_dirty_tiles(hipStream_t s) {
+   // one out-of-place step of the dirty tiles
+   void launch_dirty_tiles(hipStream_t s, const Grids &gr) {
       if (tb_xr.empty() || tb_ndirty <= 0) return;
       pf::Tb2Params tp = tile_params();
-      tp.A = u0_src ? u0_src : u0; tp.B = u1; tp.C = u0; tp.D = nullptr;
+      tp.A = gr.old; tp.B = gr.cur; tp.C = gr.nxt; tp.D = nullptr;
       tp.tiles = tb_dirty; tp.mask = mask;
       tp.xsub = tb_ndirty <= 256 ? std::min(16, std::max(tb_chunk / 4, 1)) : 1; // few tiles: shorter marches (4 planes), more workgroups
       const dim3 g((uint32_t)tb_ndirty * (uint32_t)tp.xsub), b(256);
@@ -140,18 +140,19 @@
       else if (tb_lw == 16) hipLaunchKernelGGL((pf::k_tb1_tile<Real, 3, 4, 16>), g, b, 0, s, tp, a1, a2);
       else hipLaunchKernelGGL((pf::k_tb1_tile<Real, 3, 4, 64>), g, b, 0, s, tp, a1, a2);
    }
-   // one out-of-place single step of everything outside the box: u1 -> (u0_src old) -> u0
-   void launch_shell(hipStream_t s) { launch_shell(s, 1, (int)Nx - 1); }
+   // one out-of-place single step of everything outside the box.  strip_u0b: the column strips update their own boundary nodes (zs_map) and leave
+   // the node values there (null: every node is the boundary launch's)
+   void launch_shell(hipStream_t s, const Grids &g, Real *strip_u0b = nullptr) { launch_shell(s, g, 1, (int)Nx - 1, strip_u0b); }
    // 13-point: ghost flips of u1 in memory, then x slabs (whole planes), column strips, and the single-step tiles of the box
-   void launch_shell_fcc(hipStream_t s, int xlo, int xhi, bool flips) { // planes [xlo, xhi); flips: also the ghost shell of u1
-      if (flips) launch_flips(s);
-      if (tb_xr.empty()) { launch_air_march(s, xlo, xhi); return; }
-      if (tbx0 > xlo) launch_air_march(s, xlo, tbx0);
-      if (tbx1 < xhi) launch_air_march(s, tbx1, xhi);
+   void launch_shell_fcc(hipStream_t s, const Grids &g, int xlo, int xhi, bool flips) { // planes [xlo, xhi); flips: also the ghost shell of u^n
+      if (flips) launch_flips(s, g);
+      if (tb_xr.empty()) { launch_air_march(s, g, xlo, xhi); return; }
+      if (tbx0 > xlo) launch_air_march(s, g, xlo, tbx0);
+      if (tbx1 < xhi) launch_air_march(s, g, tbx1, xhi);
       constexpr int V = pf::VecOf<Real>::V;
       {
          pf::ZStripParams<Real> zp{};
-         zp.u1 = u1; zp.u0s = u0_src ? u0_src : u0; zp.u0 = u0; zp.mask = mask;
+         zp.u1 = g.cur; zp.u0s = g.old; zp.u0 = g.nxt; zp.mask = mask;
          zp.plane = plane; zp.Nx = (int)Nx; zp.Ny = (int)Ny; zp.Nz = (int)Nz; zp.P = (int)P;
          zp.x_begin = tbx0; zp.x_end = tbx1; zp.zl = tbz0; zp.zr = tbz1; zp.first = op.slab_first; zp.last = op.slab_last;
          const int64_t nthreads = (int64_t)(zp.zl / V + (P - zp.zr) / V) * (Ny - 2);
@@ -170,56 +171,52 @@
          ap.x_begin = tbx0; ap.x_end = tbx1; ap.chunk = tb_chunk; ap.nxc = tb_nxc; ap.nzt = sh_nzt; ap.nyt = sh_nyt;
          ap.swizzle = 0; ap.swz = swz ? 1 : 0;
          ap.Nx = (int)Nx; ap.Nz = (int)Nz; ap.first = op.slab_first; ap.last = op.slab_last; ap.fold = fold ? 1 : 0;
-         if (sg) hipLaunchKernelGGL((pf::k_air_fcc<Real, 4, 4, 1, true, true, false, true, 64>), dim3((uint32_t)sh_ntiles), dim3(256), 0, s, u1, u0, mask, a1, a2,
-                                    ap, l, u0_src, sh_tiles);
-         else hipLaunchKernelGGL((pf::k_air_fcc<Real, 4, 4, 1, false, true, false, true, 64>), dim3((uint32_t)sh_ntiles), dim3(256), 0, s, u1, u0, mask, a1, a2,
-                            ap, l, u0_src, sh_tiles);
+         if (sg) hipLaunchKernelGGL((pf::k_air_fcc<Real, 4, 4, 1, true, true, false, true, 64>), dim3((uint32_t)sh_ntiles), dim3(256), 0, s, g.cur, g.nxt, mask, a1, a2,
+                                    ap, l, g.src(), sh_tiles);
+         else hipLaunchKernelGGL((pf::k_air_fcc<Real, 4, 4, 1, false, true, false, true, 64>), dim3((uint32_t)sh_ntiles), dim3(256), 0, s, g.cur, g.nxt, mask, a1, a2,
+                            ap, l, g.src(), sh_tiles);
       }
-      launch_dirty_tiles(s);
+      launch_dirty_tiles(s, g);
    }
    // planes [xlo, xhi) without the strips beside the box (slab pairs with wall regions): whole planes outside the box's x range
    // and the box's own single-step tiles
-   void launch_shell_planes(hipStream_t s, int xlo, int xhi, bool tiles = true) {
+   void launch_shell_planes(hipStream_t s, const Grids &g, int xlo, int xhi, bool tiles = true) {
       int xa = xlo;
       for (auto &r : tb_xr) {
-         if (r.first > xa) launch_air_lean(s, xa, r.first);
+         if (r.first > xa) launch_air_lean(s, g, xa, r.first);
          xa = std::max(xa, r.second);
       }
-      if (xhi > xa) launch_air_lean(s, xa, xhi);
-      if (tiles) launch_dirty_tiles(s);
+      if (xhi > xa) launch_air_lean(s, g, xa, xhi);
+      if (tiles) launch_dirty_tiles(s, g);
    }
-   void launch_shell(hipStream_t s, int xlo, int xhi) { // planes [xlo, xhi) (the box lies inside)
-      if (fcc) { launch_shell_fcc(s, xlo, xhi, !tb2_slab); return; } // (slab engines flip on the edge stream, after the exchange)
+   void launch_shell(hipStream_t s, const Grids &g, int xlo, int xhi, Real *strip_u0b = nullptr) { // planes [xlo, xhi) (the box lies inside)
+      if (fcc) { launch_shell_fcc(s, g, xlo, xhi, !tb2_slab); return; } // (slab engines flip on the edge stream, after the exchange)
       int xa = xlo;
       if (tb_xr.size() == 1 && (vbase == 0 || vbase == 40 || vbase == 41) && tb_xr[0].first > xlo && xhi > tb_xr[0].second &&
           tb_xr[0].first - xlo <= 16 && xhi - tb_xr[0].second <= 16) {
          // the usual case: two thin x slabs, below and above the box -- one launch instead of two latency-bound ones
-         lean_x2_begin = tb_xr[0].second; lean_x2_end = xhi;
-         launch_air_lean(s, xlo, tb_xr[0].first);
-         lean_x2_begin = lean_x2_end = 0;
+         launch_air_lean(s, g, xlo, tb_xr[0].first, {tb_xr[0].second, xhi});
          xa = xhi;
       }
       for (auto &r : tb_xr) { // x slabs: everything before / between / after the box's plane ranges, full planes
-         if (r.first > xa) launch_air_lean(s, xa, r.first);
+         if (r.first > xa) launch_air_lean(s, g, xa, r.first);
          xa = std::max(xa, r.second);
       }
-      if (xhi > xa) launch_air_lean(s, xa, xhi);
+      if (xhi > xa) launch_air_lean(s, g, xa, xhi);
       if (tb_xr.empty()) return;
       const int xb = tb_xr.front().first, xe = tb_xr.back().second;
       // beside the box: the two row strips in one lean launch (tile height of the default configuration: 16 rows) ...
       const int th = 8; // lean<2,4>: 8-row tiles (the strips are 5-7 rows thick in a box-shaped room)
-      lean_nyt = (int)cdiv(tby0 - 1, th); lean_yt0 = (tby1 - 1) / th;
-      launch_lean_cfg<2, 4>(s, xb, xe);
-      lean_nyt = -1; lean_yt0 = 0;
+      launch_lean_cfg<2, 4>(s, g, xb, xe, {0, 0, (int)cdiv(tby0 - 1, th), (tby1 - 1) / th});
       // ... and the two column strips
       {
          constexpr int V = pf::VecOf<Real>::V;
          pf::ZStripParams<Real> zp{};
-         zp.u1 = u1; zp.u0s = u0_src ? u0_src : u0; zp.u0 = u0; zp.mask = mask;
+         zp.u1 = g.cur; zp.u0s = g.old; zp.u0 = g.nxt; zp.mask = mask;
          zp.plane = plane; zp.Nx = (int)Nx; zp.Ny = (int)Ny; zp.Nz = (int)Nz; zp.P = (int)P;
          zp.x_begin = xb; zp.x_end = xe; zp.zl = szl; zp.zr = szr; zp.first = op.slab_first; zp.last = op.slab_last;
-         if (zs_map && bnd_sel) { // (inside step_pair) the strips' boundary nodes are updated right here
-            zp.zvec = zs_map; zp.adjv = zs_adj; zp.lossy = zs_li; zp.u0b = ub[0]; zp.sl2 = sl2;
+         if (zs_map && strip_u0b) { // (inside step_pair) the strips' boundary nodes are updated right here
+            zp.zvec = zs_map; zp.adjv = zs_adj; zp.lossy = zs_li; zp.u0b = strip_u0b; zp.sl2 = sl2;
          }
          const int64_t nthreads = (int64_t)(zp.zl / V + (P - zp.zr) / V) * (Ny - 2);
          const int xchunk = 16;
@@ -229,71 +226,15 @@
          else if (sg) hipLaunchKernelGGL((pf::k_air_zstrip<Real, true>), gz, dim3(256), 0, s, zp, a1, a2, l, xchunk);
          else hipLaunchKernelGGL((pf::k_air_zstrip<Real, false>), gz, dim3(256), 0, s, zp, a1, a2, l, xchunk);
       }
-      launch_dirty_tiles(s); // ... and the tiles of the box that hold geometry or a source
+      launch_dirty_tiles(s, g); // ... and the tiles of the box that hold geometry or a source
    }
-   // steps n and n+1 in one go; the state moves from (u0, u1) to (bufC, bufD), which swap roles with them
-   int step_pair(int64_t n) {
-      if (n < 0 || n + 1 >= Nt) return set_err(PF_ERR_ARG, "step pair %ld outside [0,Nt=%ld)", (long)n, (long)Nt);
-      if (wl_on) return step_pair_walls(n);
-      if (fb_on) return step_pair_fcc_bricks(n);
-      hipStream_t s = s_main;
-      Real *A = u0, *B = u1, *C = bufC, *D = bufD;
-      std::pair<hipEvent_t, hipEvent_t> ev{}, eva{};
-      auto get_ev = [&]() { std::pair<hipEvent_t, hipEvent_t> e{}; if (!ev_pool.empty()) { e = ev_pool.back(); ev_pool.pop_back(); } else { hipEventCreate(&e.first); hipEventCreate(&e.second); } return e; };
-      if (op.timing) { ev = get_ev(); eva = get_ev(); hipEventRecord(ev.first, s); hipEventRecord(eva.first, s); } // step events: one per step
-      std::pair<hipEvent_t, hipEvent_t> evt{};
-      // The FIRST step of the shell reads u^{n-1}, u^n only and writes cells the pair kernel does not: it runs BESIDE the pair
-      // kernel, on the edge stream (its launches are small and latency-bound -- strided strips, list gathers -- and fill the gaps
-      // the bandwidth-bound pair kernel leaves); the second step needs the box's u^{n+1} and follows.  debug 0x4000000: one stream.
-      const bool beside = !(op.debug & 0x4000000);
-      hipStream_t sh = beside ? s_edge : s;
-      if (beside) { HIPCHK(hipEventRecord(ev_pre, s)); HIPCHK(hipStreamWaitEvent(s_edge, ev_pre, 0)); }
-      u0_src = A; u1 = B; u0 = C;
-      const Range bnd = zs_map ? Range{0, zs_nrest} : Range{0, Nb};
-      bnd_sel = zs_map ? zs_rest : nullptr;
-      tb3_src_n = n;
-      launch_shell(sh);
-      launch_rigid(sh, bnd);
-      launch_fd(sh, {0, Nbl});
-      launch_io(sh, n, true, src_range());
-      // (with per-launch events on, the pair kernel waits for the shell: its recorded duration is the kernel's own, not the overlap's)
-      if (op.timing && beside) { HIPCHK(hipEventRecord(ev_edge, s_edge)); HIPCHK(hipStreamWaitEvent(s, ev_edge, 0)); }
-      if (op.timing) { evt = get_ev(); hipEventRecord(evt.first, s); }
-      launch_tb2(s, A, B, C, D);
-      if (op.timing) { hipEventRecord(evt.second, s); tb2_ev.push_back(evt); }
-      if (beside && !op.timing) { HIPCHK(hipEventRecord(ev_edge, s_edge)); HIPCHK(hipStreamWaitEvent(s, ev_edge, 0)); }
-      if (op.timing) { hipEventRecord(eva.second, s); air_ev.push_back(eva); eva = get_ev(); } // ("air" of the first step: the pair kernel and the shell beside it)
-      { Real *t = ub[2]; ub[2] = ub[1]; ub[1] = ub[0]; ub[0] = t; }
-      if (ring_fill == 0) ring_n0 = n;
-      ring_fill++; steps_done++;
-      u0_src = B; u1 = C; u0 = D;
-      if (op.timing) { hipEventRecord(ev.second, s); step_ev.push_back(ev); ev = get_ev(); hipEventRecord(ev.first, s); hipEventRecord(eva.first, s); }
-      launch_shell(s);
-      if (op.timing) { hipEventRecord(eva.second, s); air_ev.push_back(eva); }
-      launch_rigid(s, bnd);
-      bnd_sel = nullptr;
-      launch_fd(s, {0, Nbl});
-      launch_io(s, n + 1, true, src_range());
-      { Real *t = ub[2]; ub[2] = ub[1]; ub[1] = ub[0]; ub[0] = t; }
-      ring_fill++; steps_done++;
-      u0_src = nullptr; u0 = C; u1 = D; bufC = A; bufD = B;
-      if (op.timing) { hipEventRecord(ev.second, s); step_ev.push_back(ev); }
-      HIPCHK(hipGetLastError());
-      if (ring_fill == ring_depth) return flush();
-      return PF_OK;
-   }
-
    // ------------------------------------------------------------------------------------------------------------
-   void launch_air(hipStream_t s, int xb, int xe) {
+   void launch_air(hipStream_t s, const Grids &g, int xb, int xe) {
       if (xe <= xb) return;
-      std::pair<hipEvent_t, hipEvent_t> ev{};
-      if (op.timing) {
-         if (!ev_pool.empty()) { ev = ev_pool.back(); ev_pool.pop_back(); }
-         else { hipEventCreate(&ev.first); hipEventCreate(&ev.second); }
-         hipEventRecord(ev.first, s);
-      }
-      if (lean) launch_air_lean(s, xb, xe);
-      else launch_air_march(s, xb, xe);
+      EvPair ev{};
+      if (op.timing) { ev = ev_get(); hipEventRecord(ev.first, s); }
+      if (lean) launch_air_lean(s, g, xb, xe);
+      else launch_air_march(s, g, xb, xe);
       if (op.timing) { hipEventRecord(ev.second, s); air_ev.push_back(ev); }
    }
 
@@ -329,7 +270,7 @@
    // 4 segments in y instead; pick the width with the least padding (ties: the widest).
    int pick_lw() const {
       constexpr int V = pf::VecOf<Real>::V;
-      if (op.debug & 0x300) return (op.debug & 0x100) ? 32 : 16; // tuning override
+      if (op.debug & (PF_DBG_LW32 | PF_DBG_LW16)) return (op.debug & PF_DBG_LW32) ? 32 : 16; // tuning override
       if (lw_force) return lw_force;                             // measured at creation (autotune)
       // narrower segments cost extra edge-column loads (two per segment and row; the 13-point kernel needs them on every
       // row of all three planes): worth it only when they save >= 10 % of the padded width (7-point) / 25 % (13-point);
@@ -354,13 +295,13 @@
       return swz == 2 ? pf::xcd_band_blocks((uint32_t)nzt * nyt, (uint32_t)nxc) : (uint32_t)nzt * nyt * nxc;
    }
    // the barrier-free marching kernels (pf_kernels.h): R = 4 rows per lane, 4 waves stacked in y
-   void launch_air_march(hipStream_t s, int xb, int xe) {
-      const int lw = (op.debug & 0x400) ? 64 : pick_lw();
-      if (lw == 32) launch_march_lw<32>(s, xb, xe);
-      else if (lw == 16) launch_march_lw<16>(s, xb, xe);
-      else launch_march_lw<64>(s, xb, xe);
+   void launch_air_march(hipStream_t s, const Grids &g, int xb, int xe) {
+      const int lw = (op.debug & PF_DBG_LW64) ? 64 : pick_lw();
+      if (lw == 32) launch_march_lw<32>(s, g, xb, xe);
+      else if (lw == 16) launch_march_lw<16>(s, g, xb, xe);
+      else launch_march_lw<64>(s, g, xb, xe);
    }
-   template <int LW> void launch_march_lw(hipStream_t s, int xb, int xe) {
+   template <int LW> void launch_march_lw(hipStream_t s, const Grids &gr, int xb, int xe) {
       constexpr int V = pf::VecOf<Real>::V, R = 4, WY = 4, WZ = 1;
       pf::AirParams ap;
       ap.Ny = Ny; ap.P = P; ap.plane = plane;
@@ -376,38 +317,38 @@
       ap.swz = swz ? 1 : 0;
       const uint32_t total = grid_blocks(ap.swizzle, ap.nzt, ap.nyt, ap.nxc);
       dim3 g(total), b(64 * WY * WZ);
-      if (v1_dst && vg && !fcc) { // autotune: the 7-point kernel writing to a scratch grid
-         hipLaunchKernelGGL((pf::k_air_cart<Real, R, WY, WZ, false, true, true, false, LW>), g, b, 0, s, u1, u0, mask, a1, a2, ap, l, v1_dst);
+      if (vg && !fcc && !gr.in_place()) { // autotune alone: the 7-point kernel writing to a scratch grid (it reads u^{n-1} where it would write in place)
+         hipLaunchKernelGGL((pf::k_air_cart<Real, R, WY, WZ, false, true, true, false, LW>), g, b, 0, s, gr.cur, gr.old, mask, a1, a2, ap, l, gr.nxt);
          return;
       }
-      if (fcc && abck && u0_src) { // out of place (shell of a temporally blocked pair, creation-time measurement)
-         if (sg) hipLaunchKernelGGL((pf::k_air_fcc<Real, R, WY, WZ, true, true, false, true, LW>), g, b, 0, s, u1, u0, mask, a1, a2, ap, l, u0_src, (const int32_t *)nullptr);
-         else hipLaunchKernelGGL((pf::k_air_fcc<Real, R, WY, WZ, false, true, false, true, LW>), g, b, 0, s, u1, u0, mask, a1, a2, ap, l, u0_src, (const int32_t *)nullptr);
+      if (fcc && abck && !gr.in_place()) { // out of place (shell of a temporally blocked pair, creation-time measurement)
+         if (sg) hipLaunchKernelGGL((pf::k_air_fcc<Real, R, WY, WZ, true, true, false, true, LW>), g, b, 0, s, gr.cur, gr.nxt, mask, a1, a2, ap, l, gr.old, (const int32_t *)nullptr);
+         else hipLaunchKernelGGL((pf::k_air_fcc<Real, R, WY, WZ, false, true, false, true, LW>), g, b, 0, s, gr.cur, gr.nxt, mask, a1, a2, ap, l, gr.old, (const int32_t *)nullptr);
          return;
       }
-#define PF_LAUNCH(K, SG) do { if (vg) hipLaunchKernelGGL((K<Real, R, WY, WZ, SG, true, true, false, LW>), g, b, 0, s, u1, u0, mask, a1, a2, ap, l); \
-                              else if (abck) hipLaunchKernelGGL((K<Real, R, WY, WZ, SG, true, false, true, LW>), g, b, 0, s, u1, u0, mask, a1, a2, ap, l); \
-                              else hipLaunchKernelGGL((K<Real, R, WY, WZ, SG, true, false, false, LW>), g, b, 0, s, u1, u0, mask, a1, a2, ap, l); } while (0)
+#define PF_LAUNCH(K, SG) do { if (vg) hipLaunchKernelGGL((K<Real, R, WY, WZ, SG, true, true, false, LW>), g, b, 0, s, gr.cur, gr.nxt, mask, a1, a2, ap, l); \
+                              else if (abck) hipLaunchKernelGGL((K<Real, R, WY, WZ, SG, true, false, true, LW>), g, b, 0, s, gr.cur, gr.nxt, mask, a1, a2, ap, l); \
+                              else hipLaunchKernelGGL((K<Real, R, WY, WZ, SG, true, false, false, LW>), g, b, 0, s, gr.cur, gr.nxt, mask, a1, a2, ap, l); } while (0)
       if (fcc) { if (sg) PF_LAUNCH(pf::k_air_fcc, true); else PF_LAUNCH(pf::k_air_fcc, false); }
       else { if (sg) PF_LAUNCH(pf::k_air_cart, true); else PF_LAUNCH(pf::k_air_cart, false); }
 #undef PF_LAUNCH
    }
 
    // the lean fused 7-point kernel (pf_air_fused.h).  R x WY = rows per lane x waves per workgroup; NT = nontemporal u0 traffic
-   template <int R, int WY, bool NT = true> void launch_lean_cfg(hipStream_t s, int xb, int xe) {
+   template <int R, int WY, bool NT = true> void launch_lean_cfg(hipStream_t s, const Grids &g, int xb, int xe, LeanExtra ex = {}) {
       pf::LeanParams fp{};
-      fp.u1 = u1; fp.u0 = u0; fp.mask = mask;
+      fp.u1 = g.cur; fp.u0 = g.nxt; fp.mask = mask;
       fp.plane = plane;
       fp.Nx = (int)Nx; fp.Ny = (int)Ny; fp.Nz = (int)Nz; fp.P = (int)P;
       fp.x_begin = xb; fp.x_end = xe;
       fp.nzt = lean_nzt;
       fp.nyt = (int)cdiv(Ny - 2, (int64_t)WY * R);
-      fp.u0_src = u0_src; fp.yt0 = 0; fp.yt_split = -1; fp.yt_hi0 = 0;
+      fp.u0_src = g.src(); fp.yt0 = 0; fp.yt_split = -1; fp.yt_hi0 = 0;
       // (row strips of a triple's third step: the strips' tiles reach into the box, whose u^{n+1} -- the step's old value -- is not in
       // memory: those rows are left to k_tb3's own result)
-      if (lean_nyt >= 0 && triples()) { fp.skip_y0 = tby0; fp.skip_y1 = tby1; }
-      if (lean_nyt >= 0) { // row strips: tiles [0, lean_nyt) and [lean_yt0, all) in units of this configuration's tile height
-         const int all = fp.nyt, lo = std::min(lean_nyt, all), hi0 = std::max(std::min(lean_yt0, all), lo);
+      if (ex.nyt >= 0 && triples()) { fp.skip_y0 = tby0; fp.skip_y1 = tby1; }
+      if (ex.nyt >= 0) { // row strips: tiles [0, ex.nyt) and [ex.yt0, all) in units of this configuration's tile height
+         const int all = fp.nyt, lo = std::min(ex.nyt, all), hi0 = std::max(std::min(ex.yt0, all), lo);
          fp.yt_split = lo; fp.yt_hi0 = hi0;
          fp.nyt = lo + (all - hi0);
          if (fp.nyt <= 0) return;
@@ -416,100 +357,99 @@
       int chunk = pick_chunk(nplanes, (int64_t)fp.nzt * fp.nyt, true);
       fp.chunk = chunk;
       fp.nxc = (int)cdiv(nplanes, chunk);
-      if (lean_x2_end > lean_x2_begin) { // a second x slab [lean_x2_begin, lean_x2_end) in the same launch (both thin: one chunk each)
-         chunk = std::max(nplanes, lean_x2_end - lean_x2_begin);
+      if (ex.x2_end > ex.x2_begin) { // a second x slab [ex.x2_begin, ex.x2_end) in the same launch (both thin: one chunk each)
+         chunk = std::max(nplanes, ex.x2_end - ex.x2_begin);
          fp.chunk = chunk;
-         fp.x_lo_end = xe; fp.x2_begin = lean_x2_begin; fp.x_end = lean_x2_end;
+         fp.x_lo_end = xe; fp.x2_begin = ex.x2_begin; fp.x_end = ex.x2_end;
          fp.x2_nlo = 1; fp.nxc = 2;
       }
       fp.swizzle = swizzle_mode((int64_t)fp.nzt * fp.nyt);
       fp.first = op.slab_first; fp.last = op.slab_last;
       fp.do_abc = 1;
       fp.swz = swz ? 1 : 0;
-      dim3 g(grid_blocks(fp.swizzle, fp.nzt, fp.nyt, fp.nxc)), b(64 * WY);
-      if (sg) hipLaunchKernelGGL((pf::k_air_cart_lean<Real, R, WY, true, NT>), g, b, 0, s, fp, a1, a2, l);
-      else hipLaunchKernelGGL((pf::k_air_cart_lean<Real, R, WY, false, NT>), g, b, 0, s, fp, a1, a2, l);
+      dim3 gd(grid_blocks(fp.swizzle, fp.nzt, fp.nyt, fp.nxc)), b(64 * WY);
+      if (sg) hipLaunchKernelGGL((pf::k_air_cart_lean<Real, R, WY, true, NT>), gd, b, 0, s, fp, a1, a2, l);
+      else hipLaunchKernelGGL((pf::k_air_cart_lean<Real, R, WY, false, NT>), gd, b, 0, s, fp, a1, a2, l);
    }
-   void launch_air_lean(hipStream_t s, int xb, int xe) {
+   void launch_air_lean(hipStream_t s, const Grids &g, int xb, int xe, LeanExtra ex = {}) {
       // fastest measured on MI355X: fp32 R = 4 x 4 waves, fp64 R = 2 x 8 waves (register budget)
-      if (sizeof(Real) == 8) launch_lean_cfg<2, 8>(s, xb, xe);
-      else launch_lean_cfg<4, 4>(s, xb, xe);
+      if (sizeof(Real) == 8) launch_lean_cfg<2, 8>(s, g, xb, xe, ex);
+      else launch_lean_cfg<4, 4>(s, g, xb, xe, ex);
    }
 
-   void launch_pre(hipStream_t s) {
+   void launch_pre(hipStream_t s, const Grids &g) {
       if (lean || vg) return; // ghost shell is virtual, u2ba is the old u0 in registers
-      launch_flips(s);
-      if (Nba && !abck) hipLaunchKernelGGL(pf::k_abc_save<Real>, dim3((unsigned)cdiv(Nba, 256)), dim3(256), 0, s, u0, d_bna, u2ba, Nba);
+      launch_flips(s, g);
+      if (Nba && !abck) hipLaunchKernelGGL(pf::k_abc_save<Real>, dim3((unsigned)cdiv(Nba, 256)), dim3(256), 0, s, g.old, d_bna, u2ba, Nba);
    }
-   void launch_flips(hipStream_t s) {
+   void launch_flips(hipStream_t s, const Grids &g) {
       dim3 gy((unsigned)cdiv(Nz, 256), (unsigned)Nx);
-      if (fold) hipLaunchKernelGGL(pf::k_flip_y<Real>, gy, dim3(256), 0, s, u1, Nx, Ny, P, Nz, 4);
-      hipLaunchKernelGGL(pf::k_flip_z<Real>, dim3((unsigned)cdiv(Nx * Ny, 256)), dim3(256), 0, s, u1, Nx * Ny, P, Nz);
-      hipLaunchKernelGGL(pf::k_flip_y<Real>, gy, dim3(256), 0, s, u1, Nx, Ny, P, Nz, fold ? 1 : 3);
+      if (fold) hipLaunchKernelGGL(pf::k_flip_y<Real>, gy, dim3(256), 0, s, g.cur, Nx, Ny, P, Nz, 4);
+      hipLaunchKernelGGL(pf::k_flip_z<Real>, dim3((unsigned)cdiv(Nx * Ny, 256)), dim3(256), 0, s, g.cur, Nx * Ny, P, Nz);
+      hipLaunchKernelGGL(pf::k_flip_y<Real>, gy, dim3(256), 0, s, g.cur, Nx, Ny, P, Nz, fold ? 1 : 3);
       if (op.slab_first || op.slab_last)
-         hipLaunchKernelGGL(pf::k_flip_x<Real>, dim3((unsigned)cdiv(plane, 256)), dim3(256), 0, s, u1, Nx, plane, op.slab_first, op.slab_last);
+         hipLaunchKernelGGL(pf::k_flip_x<Real>, dim3((unsigned)cdiv(plane, 256)), dim3(256), 0, s, g.cur, Nx, plane, op.slab_first, op.slab_last);
    }
-   void launch_abc(hipStream_t s, Range r) {
+   void launch_abc(hipStream_t s, const Grids &g, Range r) {
       if (lean || vg || abck || r.e <= r.b) return;
-      if (sg) hipLaunchKernelGGL((pf::k_abc_loss<Real, true>), dim3((unsigned)cdiv(r.e - r.b, 256)), dim3(256), 0, s, u0, d_bna, d_Q, u2ba, l, r.b, r.e);
-      else hipLaunchKernelGGL((pf::k_abc_loss<Real, false>), dim3((unsigned)cdiv(r.e - r.b, 256)), dim3(256), 0, s, u0, d_bna, d_Q, u2ba, l, r.b, r.e);
+      if (sg) hipLaunchKernelGGL((pf::k_abc_loss<Real, true>), dim3((unsigned)cdiv(r.e - r.b, 256)), dim3(256), 0, s, g.nxt, d_bna, d_Q, u2ba, l, r.b, r.e);
+      else hipLaunchKernelGGL((pf::k_abc_loss<Real, false>), dim3((unsigned)cdiv(r.e - r.b, 256)), dim3(256), 0, s, g.nxt, d_bna, d_Q, u2ba, l, r.b, r.e);
    }
    // Virtual-ghost modes: boundary nodes next to the folded ghost row read it from MEMORY, so that one row is kept
    // materialised.  In a split-phase step the main stream only touches planes [1, Nx-1): the slab's ghost planes may
    // be receiving the neighbours' data at that moment (the edge stream, ordered after the exchange, does those).
-   int fold_x0 = 0, fold_x1 = 0; // plane range of the next launch_fold_row (set by the step drivers)
-   void launch_fold_row(hipStream_t s) {
-      if (!((lean || vg) && fold && need_fold_row) || fold_x1 <= fold_x0) return;
-      dim3 gy((unsigned)cdiv(Nz, 256), (unsigned)(fold_x1 - fold_x0));
-      hipLaunchKernelGGL(pf::k_flip_y<Real>, gy, dim3(256), 0, s, u1 + (int64_t)fold_x0 * plane, (int64_t)(fold_x1 - fold_x0), Ny, P, Nz, 4);
+   void launch_fold_row(hipStream_t s, const Grids &g, const Bnd &bn) { // planes [bn.fold_b, bn.fold_e)
+      if (!((lean || vg) && fold && need_fold_row) || bn.fold_e <= bn.fold_b) return;
+      dim3 gy((unsigned)cdiv(Nz, 256), (unsigned)(bn.fold_e - bn.fold_b));
+      hipLaunchKernelGGL(pf::k_flip_y<Real>, gy, dim3(256), 0, s, g.cur + (int64_t)bn.fold_b * plane, (int64_t)(bn.fold_e - bn.fold_b), Ny, P, Nz, 4);
    }
    // rigid + FD in one pass over the boundary list (plane range given on the boundary list)
-   void launch_boundary(hipStream_t s, Range r) {
-      // (inside step_pair) the branch ODEs of the column strips' lossy nodes ride along in the same launch (k_fd_sel's work)
+   void launch_boundary(hipStream_t s, const Grids &gr, const Bnd &bn, Range r, bool strips_fd) {
+      // strips_fd (inside step_pair, bn.sel = zs_rest): the branch ODEs of the column strips' lossy nodes ride along in the same launch (k_fd_sel's work)
       // (a launch of its own, k_fd_sel, until round 3: same time within noise, one kernel fewer)
-      const bool with_fd = zs_mode == 2 && bnd_sel && bnd_sel == zs_rest && zs_nfd > 0 && r.b == 0 && r.e == zs_nrest;
+      const bool with_fd = strips_fd && zs_mode == 2 && zs_nfd > 0 && r.b == 0 && r.e == zs_nrest;
       if (r.e <= r.b && !with_fd) return;
-      launch_fold_row(s);
+      launch_fold_row(s, gr, bn);
       const int64_t nfd = with_fd ? zs_nfd : 0;
       dim3 g((unsigned)cdiv(r.e - r.b + nfd, 128)), b(128);
-#define PF_BND(F, M) hipLaunchKernelGGL((pf::k_boundary<Real, F, M>), g, b, 0, s, u1, u0, d_bn, d_adj, d_lossy, a2, sl2, P, plane, ub[0], ub[2], d_ssaf, d_mat, d_Mb, d_mq, d_beta, vh1, gh1, bs_vout ? bs_vout : vh1, bs_gout ? bs_gout : gh1, lo2, (int64_t)mb_max, r.b, r.e, u0_src ? u0_src : (const Real *)u0, bnd_sel, swz ? 1 : 0, with_fd ? zs_fd : (const int32_t *)nullptr, nfd, d_bnl, bflags)
+#define PF_BND(F, M) hipLaunchKernelGGL((pf::k_boundary<Real, F, M>), g, b, 0, s, gr.cur, gr.nxt, d_bn, d_adj, d_lossy, a2, sl2, P, plane, bn.u0b, bn.u2b, d_ssaf, d_mat, d_Mb, d_mq, d_beta, bn.in.v, bn.in.g, bn.out.v, bn.out.g, lo2, (int64_t)mb_max, r.b, r.e, (const Real *)gr.old, bn.sel, swz ? 1 : 0, with_fd ? zs_fd : (const int32_t *)nullptr, nfd, d_bnl, bflags)
       // Each XCD walks runs of 64 consecutive workgroups
       // (8192 nodes, a few node rows) inside a window of 512, so most rows of u^n that consecutive node rows share are asked
       // for by ONE L2: fetched bytes 4.53 -> 3.7 GB on the Musikverein, 0.79-0.81 -> 0.75-0.76 ms (CTK 0.150 -> 0.141).
       // One run per XCD over the whole list fetches least (3.36 GB) and is slowest (0.90 ms: eight places in every stream);
       // profiles/r04_rooms_hbm_traffic.md.  (Box rooms in single steps: 1024^3 384 -> 388 Gvox/s; slabs: the same.)
-      // debug 0x100000: plain order; 0x200000: fetch the neighbours inside the wall too.
+      // PF_DBG_BND_PLAIN_ORDER: plain order; PF_DBG_BND_FETCH_ALL: fetch the neighbours inside the wall too.
       const int bnd_g = 64;
-      const int bflags = ((!(op.debug & 0x100000)) ? (1 | (bnd_g << 4)) : 0) | ((op.debug & 0x200000) ? 2 : 0);
+      const int bflags = ((!(op.debug & PF_DBG_BND_PLAIN_ORDER)) ? (1 | (bnd_g << 4)) : 0) | ((op.debug & PF_DBG_BND_FETCH_ALL) ? 2 : 0);
       if (fcc) { if (sg) PF_BND(true, true); else PF_BND(true, false); }
       else { if (sg) PF_BND(false, true); else PF_BND(false, false); }
 #undef PF_BND
    }
    bool boundary_fused() const { return fuse_boundary; }
-   void launch_rigid(hipStream_t s, Range r) {
-      if (boundary_fused()) { launch_boundary(s, r); return; }
+   void launch_rigid(hipStream_t s, const Grids &gr, const Bnd &bn, Range r, bool strips_fd = false) {
+      if (boundary_fused()) { launch_boundary(s, gr, bn, r, strips_fd); return; }
       if (r.e <= r.b) return;
-      launch_fold_row(s);
+      launch_fold_row(s, gr, bn);
       dim3 g((unsigned)cdiv(r.e - r.b, 256)), b(256);
       if (fcc) {
-         if (sg) hipLaunchKernelGGL((pf::k_rigid<Real, true, true>), g, b, 0, s, u1, u0, d_bn, d_adj, a2, sl2, P, plane, r.b, r.e, swz ? 1 : 0);
-         else hipLaunchKernelGGL((pf::k_rigid<Real, true, false>), g, b, 0, s, u1, u0, d_bn, d_adj, a2, sl2, P, plane, r.b, r.e, swz ? 1 : 0);
+         if (sg) hipLaunchKernelGGL((pf::k_rigid<Real, true, true>), g, b, 0, s, gr.cur, gr.nxt, d_bn, d_adj, a2, sl2, P, plane, r.b, r.e, swz ? 1 : 0);
+         else hipLaunchKernelGGL((pf::k_rigid<Real, true, false>), g, b, 0, s, gr.cur, gr.nxt, d_bn, d_adj, a2, sl2, P, plane, r.b, r.e, swz ? 1 : 0);
       } else {
-         if (sg) hipLaunchKernelGGL((pf::k_rigid<Real, false, true>), g, b, 0, s, u1, u0, d_bn, d_adj, a2, sl2, P, plane, r.b, r.e, swz ? 1 : 0);
-         else hipLaunchKernelGGL((pf::k_rigid<Real, false, false>), g, b, 0, s, u1, u0, d_bn, d_adj, a2, sl2, P, plane, r.b, r.e, swz ? 1 : 0);
+         if (sg) hipLaunchKernelGGL((pf::k_rigid<Real, false, true>), g, b, 0, s, gr.cur, gr.nxt, d_bn, d_adj, a2, sl2, P, plane, r.b, r.e, swz ? 1 : 0);
+         else hipLaunchKernelGGL((pf::k_rigid<Real, false, false>), g, b, 0, s, gr.cur, gr.nxt, d_bn, d_adj, a2, sl2, P, plane, r.b, r.e, swz ? 1 : 0);
       }
    }
-   void launch_fd(hipStream_t s, Range r) {
+   void launch_fd(hipStream_t s, const Grids &g, const Bnd &bn, Range r) {
       if (boundary_fused()) return; // done by launch_boundary
       if (r.e > r.b)
-         hipLaunchKernelGGL(pf::k_fd_boundary<Real>, dim3((unsigned)cdiv(r.e - r.b, 128)), dim3(128), 0, s, u0, d_bnl, ub[0], ub[2], d_ssaf, d_mat, d_Mb, d_mq, d_beta, vh1, gh1, lo2, (int64_t)mb_max, r.b, r.e);
+         hipLaunchKernelGGL(pf::k_fd_boundary<Real>, dim3((unsigned)cdiv(r.e - r.b, 128)), dim3(128), 0, s, g.nxt, d_bnl, bn.u0b, bn.u2b, d_ssaf, d_mat, d_Mb, d_mq, d_beta, bn.in.v, bn.in.g, lo2, (int64_t)mb_max, r.b, r.e);
    }
    // receivers on/off + a range of the (sorted) source list
-   void launch_io(hipStream_t s, int64_t n, bool receivers, Range src, const int64_t *ctr = nullptr, const Real *u_next = nullptr) {
+   void launch_io(hipStream_t s, const Grids &g, int64_t n, bool receivers, Range src, const int64_t *ctr = nullptr, const Real *u_next = nullptr) {
       const int64_t nr = receivers ? Nr : 0;
       const int64_t ns = src.e - src.b;
       if (nr == 0 && ns <= 0) return;
       // (u_next: the field the NEXT step's readout reads, taken in the same launch into the next ring column -- no sources then)
-      hipLaunchKernelGGL(pf::k_io<Real>, dim3((unsigned)cdiv(nr + 1, 128)), dim3(128), 0, s, u1, u0, d_out, ring, nr, ring_fill, ring_depth,
+      hipLaunchKernelGGL(pf::k_io<Real>, dim3((unsigned)cdiv(nr + 1, 128)), dim3(128), 0, s, g.cur, g.nxt, d_out, ring, nr, ring_fill, ring_depth,
                          d_in + src.b, d_insig + src.b * Nt, std::max<int64_t>(ns, 0), Nt, n, ctr, u_next);
    }

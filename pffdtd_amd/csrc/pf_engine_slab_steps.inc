@@ -42,7 +42,7 @@
          if (ph == 0) {
             tb3_pick();
             pA = u0; pB = u1; u0_src = pA; u1 = pB; u0 = bufC;
-            wsP[0] = ub[0]; wsP[1] = ub[1]; wsP[2] = ub[2]; bs_vout = vh1b; bs_gout = gh1b;
+            wsP[0] = ub[0]; wsP[1] = ub[1]; wsP[2] = ub[2];
             // round 6: with two more node-value buffers (init_walls) the triple's u^{n+2} / u^{n+3} of the nodes go where nobody reads during it --
             // what lets the wall regions and the frame's bricks take all three steps in THIS phase (ws_all3); else u^{n+2} overwrites u^n and
             // u^{n+3} u^{n-1}, as before
@@ -56,63 +56,62 @@
          // an end slab's own x wall (wl_xw): a region and bricks step it three times in phase 0 like a single domain's -- no edge planes on that side
          const bool wlo = wl_xw[0], whi = wl_xw[1];
          const int sp0 = wlo ? tbx0 : xl + 3, sp1 = whi ? tbx1 : xh - 2; // the planes between the edge planes and the box
-         fold_x0 = 0; fold_x1 = 0;
+         // grids, node values and branch state as the phase machine (here and in step_end) has left them; the triple's first split-phase step, in which
+         // the regions and the bricks write the other copy of the branch state, has every boundary launch write it
+         const Grids g = grids();
+         Bnd b = bnd(0, 0);
+         if (ph == 0) b.out = {vh1b, gh1b};
          // The edge planes of both sides: in the second and third split-phase step of a triple they ARE the step -- four launches and two copies,
          // all launch gaps (75 us each at 1/8 of 1024^3, 150 of a triple's 760) -- so the two sides share one launch of the lean kernel (its
          // second-slab mode) and one of the boundary kernel (a selection list: the nodes of the low planes, then of the high ones)
          if (boundary_fused() && edge_sel3_ready()) {
-            if (!wlo && !whi) {
-               lean_x2_begin = xh - 2; lean_x2_end = xh + 1;
-               launch_air_lean(s_edge, xl, xl + 3);
-               lean_x2_begin = lean_x2_end = 0;
-            } else if (!wlo) launch_air_lean(s_edge, xl, xl + 3);
-            else launch_air_lean(s_edge, xh - 2, xh + 1);
-            bnd_sel = edge_sel3; launch_rigid(s_edge, {0, n_edge_sel3}); bnd_sel = nullptr;
+            if (!wlo && !whi) launch_air_lean(s_edge, g, xl, xl + 3, {xh - 2, xh + 1});
+            else if (!wlo) launch_air_lean(s_edge, g, xl, xl + 3);
+            else launch_air_lean(s_edge, g, xh - 2, xh + 1);
+            launch_rigid(s_edge, g, b.with(edge_sel3), {0, n_edge_sel3});
          } else {
-            if (!wlo) { launch_air_lean(s_edge, xl, xl + 3); launch_rigid(s_edge, bn_lo3); }
-            if (!whi) { launch_air_lean(s_edge, xh - 2, xh + 1); launch_rigid(s_edge, bn_hi3); }
+            if (!wlo) { launch_air_lean(s_edge, g, xl, xl + 3); launch_rigid(s_edge, g, b, bn_lo3); }
+            if (!whi) { launch_air_lean(s_edge, g, xh - 2, xh + 1); launch_rigid(s_edge, g, b, bn_hi3); }
          }
-         if (!wlo) { launch_fd(s_edge, bnl_lo3); launch_io(s_edge, n, false, in_lo3); }
-         if (!whi) { launch_fd(s_edge, bnl_hi3); launch_io(s_edge, n, false, in_hi3); }
+         if (!wlo) { launch_fd(s_edge, g, b, bnl_lo3); launch_io(s_edge, g, n, false, in_lo3); }
+         if (!whi) { launch_fd(s_edge, g, b, bnl_hi3); launch_io(s_edge, g, n, false, in_hi3); }
          HIPCHK(hipEventRecord(ev_edge, s_edge));
-         std::pair<hipEvent_t, hipEvent_t> eva{}, evt{};
-         auto get_ev = [&]() { std::pair<hipEvent_t, hipEvent_t> e{}; if (!ev_pool.empty()) { e = ev_pool.back(); ev_pool.pop_back(); } else { hipEventCreate(&e.first); hipEventCreate(&e.second); } return e; };
-         if (op.timing) { eva = get_ev(); hipEventRecord(eva.first, s_main); }
+         EvPair eva{}, evt{};
+         if (op.timing) { eva = ev_get(); hipEventRecord(eva.first, s_main); }
          if (ph == 0) {
             { int rcs = wall_streams(); if (rcs) return rcs; }
             HIPCHK(hipEventRecord(ev_wall0, s_main));
             HIPCHK(hipStreamWaitEvent(s_wall, ev_wall0, 0));
             HIPCHK(hipStreamWaitEvent(s_wall2, ev_wall0, 0));
-            tb3_src_n = n;
-            launch_tb3_src<3>(s_wall2, pA, pB, bufC, bufD, bufE); // the tiles around the sources (k_tb3_src): first, beside the regions
+            launch_tb3_src<3>(s_wall2, n, pA, pB, bufC, bufD, bufE); // the tiles around the sources (k_tb3_src): first, beside the regions
             if (ws_all3) { // the strips beside the box and the four bars along x: all three steps now (k_wall2 NS = 3, k_brick)
-               launch_bricks(s_wall2, pA, pB, bufC, bufD, bufE, wsP[2], wsP[1], wsP[0], wsT2, wsT3, 3);
-               launch_walls_x(s_wall, s_wall2, pA, pB, bufC, bufD, bufE, wsP[2], wsP[1], wsP[0], wsT2, wsT3, 3, 0xf);
-            } else if (ws_five) launch_walls_x(s_wall, s_wall2, pA, pB, bufC, bufD, nullptr, wsP[2], wsP[1], wsP[0], wsT2, nullptr, 2, 0xf);
-            else launch_walls(s_wall, s_wall2, pA, pB, bufC, bufD, wsP[0], wsP[1], wsP[2]);
-            launch_shell_planes(s_wall, sp0, sp1, false);
-            bnd_sel = wl_rest; launch_rigid(s_wall, {0, wl_nrest}); bnd_sel = nullptr;
+               launch_bricks(s_wall2, pA, pB, bufC, bufD, bufE, wsP[2], wsP[1], wsP[0], wsT2, wsT3, b.in, b.out, 3);
+               launch_walls_x(s_wall, s_wall2, pA, pB, bufC, bufD, bufE, wsP[2], wsP[1], wsP[0], wsT2, wsT3, b.in, b.out, 3, 0xf);
+            } else if (ws_five) launch_walls_x(s_wall, s_wall2, pA, pB, bufC, bufD, nullptr, wsP[2], wsP[1], wsP[0], wsT2, nullptr, b.in, b.out, 2, 0xf);
+            else launch_walls(s_wall, s_wall2, pA, pB, bufC, bufD, wsP[0], wsP[1], wsP[2], b.in, b.out);
+            launch_shell_planes(s_wall, g, sp0, sp1, false);
+            launch_rigid(s_wall, g, b.with(wl_rest), {0, wl_nrest});
             HIPCHK(hipEventRecord(ev_wall, s_wall));
             HIPCHK(hipEventRecord(ev_wall2, s_wall2));
             wall_pending = true;
-            if (op.timing) { evt = get_ev(); hipEventRecord(evt.first, s_main); }
-            launch_tb3(s_main, pA, pB, bufC, bufD, bufE);
+            if (op.timing) { evt = ev_get(); hipEventRecord(evt.first, s_main); }
+            launch_tb3(s_main, n, pA, pB, bufC, bufD, bufE);
             if (op.timing) { hipEventRecord(evt.second, s_main); tb2_ev.push_back(evt); }
-            launch_dirty_tiles(s_main);
+            launch_dirty_tiles(s_main, g);
             HIPCHK(hipStreamWaitEvent(s_main, ev_wall, 0)); // (a source in those planes is added after their update)
          } else if (ph == 1) {
-            launch_shell_planes(s_main, sp0, sp1);
-            bnd_sel = wl_rest; launch_rigid(s_main, {0, wl_nrest}); bnd_sel = nullptr;
+            launch_shell_planes(s_main, g, sp0, sp1);
+            launch_rigid(s_main, g, b.with(wl_rest), {0, wl_nrest});
          } else if (ws_all3) { // the regions and the bricks are at n+3 already: the planes outside the box's x range, the single-step tiles, the box's own nodes
-            launch_shell_planes(s_main, sp0, sp1);
-            bnd_sel = wl_rest; launch_rigid(s_main, {0, wl_nrest}); bnd_sel = nullptr;
+            launch_shell_planes(s_main, g, sp0, sp1);
+            launch_rigid(s_main, g, b.with(wl_rest), {0, wl_nrest});
          } else {
-            launch_shell(s_main, xl + 3, xh - 2);
-            launch_rigid(s_main, bn_mid3);
+            launch_shell(s_main, g, xl + 3, xh - 2);
+            launch_rigid(s_main, g, b, bn_mid3);
          }
          if (op.timing) { hipEventRecord(eva.second, s_main); air_ev.push_back(eva); }
-         launch_fd(s_main, bnl_mid3);
-         launch_io(s_main, n, true, src_in_kernel() ? Range{0, 0} : in_mid3); // (sources in the box: inside k_tb3_src, Engine::launch_tb3_src)
+         launch_fd(s_main, g, b, bnl_mid3);
+         launch_io(s_main, g, n, true, src_in_kernel() ? Range{0, 0} : in_mid3); // (sources in the box: inside k_tb3_src, Engine::launch_tb3_src)
          HIPCHK(hipGetLastError());
          in_step = true;
          pair_now = true; triple_now = true;
@@ -125,30 +124,31 @@
          // the same buffers: first half state out of place into vh1b and node values into P0, second half both in place (P1)
          if (first_half) {
             pA = u0; pB = u1; u0_src = pA; u1 = pB; u0 = bufC;
-            if (wl_on) { wsP[0] = ub[0]; wsP[1] = ub[1]; wsP[2] = ub[2]; bs_vout = vh1b; bs_gout = gh1b; }
+            if (wl_on) { wsP[0] = ub[0]; wsP[1] = ub[1]; wsP[2] = ub[2]; }
          }
-         fold_x0 = 0; fold_x1 = 0; // (virtual-ghost modes with a fold row do not block in pairs)
+         const Grids g = grids();
+         Bnd b = bnd(0, 0); // (no fold row: virtual-ghost modes with one do not block in pairs)
+         if (wl_on && first_half) b.out = {vh1b, gh1b};
          if (fcc) {
             // 13-point: the ghost shell of u1 lives in memory; its flips touch the whole grid, ghost planes included, so
             // they go on the edge stream (ordered after the exchange that filled those planes) and the interior waits
-            launch_flips(s_edge);
+            launch_flips(s_edge, g);
             HIPCHK(hipEventRecord(ev_pre, s_edge));
             HIPCHK(hipStreamWaitEvent(s_main, ev_pre, 0));
-            launch_air_march(s_edge, xl, xl + 2);   // (k_air_fcc reads u^{n-1} from u0_src)
-            launch_air_march(s_edge, xh - 1, xh + 1);
+            launch_air_march(s_edge, g, xl, xl + 2);   // (k_air_fcc's out-of-place form)
+            launch_air_march(s_edge, g, xh - 1, xh + 1);
          } else {
-            // (the lean kernel explicitly, as launch_shell does: it is the one that honours u0_src -- the barrier-free
-            // kernel an engine may have chosen for its single steps reads u^{n-1} from u0, which here is the grid being written)
-            launch_air_lean(s_edge, xl, xl + 2);
-            launch_air_lean(s_edge, xh - 1, xh + 1);
+            // (the lean kernel explicitly, as launch_shell does: it is the one that steps out of place -- the barrier-free
+            // kernel an engine may have chosen for its single steps reads u^{n-1} where it writes)
+            launch_air_lean(s_edge, g, xl, xl + 2);
+            launch_air_lean(s_edge, g, xh - 1, xh + 1);
          }
-         launch_rigid(s_edge, bn_lo2); launch_rigid(s_edge, bn_hi2);
-         launch_fd(s_edge, bnl_lo2); launch_fd(s_edge, bnl_hi2);
-         launch_io(s_edge, n, false, in_lo2); launch_io(s_edge, n, false, in_hi2);
+         launch_rigid(s_edge, g, b, bn_lo2); launch_rigid(s_edge, g, b, bn_hi2);
+         launch_fd(s_edge, g, b, bnl_lo2); launch_fd(s_edge, g, b, bnl_hi2);
+         launch_io(s_edge, g, n, false, in_lo2); launch_io(s_edge, g, n, false, in_hi2);
          HIPCHK(hipEventRecord(ev_edge, s_edge));
-         std::pair<hipEvent_t, hipEvent_t> eva{}, evt{};
-         auto get_ev = [&]() { std::pair<hipEvent_t, hipEvent_t> e{}; if (!ev_pool.empty()) { e = ev_pool.back(); ev_pool.pop_back(); } else { hipEventCreate(&e.first); hipEventCreate(&e.second); } return e; };
-         if (op.timing) { eva = get_ev(); hipEventRecord(eva.first, s_main); }
+         EvPair eva{}, evt{};
+         if (op.timing) { eva = ev_get(); hipEventRecord(eva.first, s_main); }
          if (first_half) {
             if (wl_on) { // beside the box kernel, on a stream of their own: a slab's regions are a few hundred waves, each a chain of dependent march steps
                { int rcs = wall_streams(); if (rcs) return rcs; }
@@ -157,54 +157,54 @@
                HIPCHK(hipEventRecord(ev_wall0, s_main));
                HIPCHK(hipStreamWaitEvent(s_wall, ev_wall0, 0));
                HIPCHK(hipStreamWaitEvent(s_wall2, ev_wall0, 0));
-               launch_walls(s_wall, s_wall2, pA, pB, bufC, bufD, wsP[0], wsP[1], wsP[2]);
+               launch_walls(s_wall, s_wall2, pA, pB, bufC, bufD, wsP[0], wsP[1], wsP[2], b.in, b.out);
                // the first step of the planes between the edge planes and the box (an end slab's x wall) and of the boundary nodes
                // no region owns: behind the alike blocks, not behind the box kernel (they only read u^{n-1}, u^n)
-               launch_shell_planes(s_wall, xl + 2, xh - 1, false);
-               bnd_sel = wl_rest; launch_rigid(s_wall, {0, wl_nrest}); bnd_sel = nullptr;
+               launch_shell_planes(s_wall, g, xl + 2, xh - 1, false);
+               launch_rigid(s_wall, g, b.with(wl_rest), {0, wl_nrest});
                HIPCHK(hipEventRecord(ev_wall, s_wall));
                HIPCHK(hipEventRecord(ev_wall2, s_wall2));
                wall_pending = true;
             }
-            if (op.timing) { evt = get_ev(); hipEventRecord(evt.first, s_main); }
-            launch_tb2(s_main, pA, pB, bufC, bufD);
+            if (op.timing) { evt = ev_get(); hipEventRecord(evt.first, s_main); }
+            launch_tb2(s_main, n, pA, pB, bufC, bufD);
             if (op.timing) { hipEventRecord(evt.second, s_main); tb2_ev.push_back(evt); }
          }
-         if (wl_on && first_half) launch_dirty_tiles(s_main); // (the strips beside the box are the wall regions'; the planes outside it: above)
-         else if (wl_on) launch_shell_planes(s_main, xl + 2, xh - 1);
-         else launch_shell(s_main, xl + 2, xh - 1);
+         if (wl_on && first_half) launch_dirty_tiles(s_main, g); // (the strips beside the box are the wall regions'; the planes outside it: above)
+         else if (wl_on) launch_shell_planes(s_main, g, xl + 2, xh - 1);
+         else launch_shell(s_main, g, xl + 2, xh - 1);
          if (op.timing) { hipEventRecord(eva.second, s_main); air_ev.push_back(eva); }
          if (wl_on && first_half) HIPCHK(hipStreamWaitEvent(s_main, ev_wall, 0)); // (a source in those planes is added after their update)
-         else if (wl_on) { bnd_sel = wl_rest; launch_rigid(s_main, {0, wl_nrest}); bnd_sel = nullptr; }
-         else launch_rigid(s_main, bn_mid2);
-         launch_fd(s_main, bnl_mid2);
-         launch_io(s_main, n, true, in_mid2);
+         else if (wl_on) launch_rigid(s_main, g, b.with(wl_rest), {0, wl_nrest});
+         else launch_rigid(s_main, g, b, bn_mid2);
+         launch_fd(s_main, g, b, bnl_mid2);
+         launch_io(s_main, g, n, true, in_mid2);
          HIPCHK(hipGetLastError());
          in_step = true;
          pair_now = true;
          return PF_OK;
       }
+      const Grids g = grids();
+      const Bnd be = bnd(0, (int)Nx), bm = bnd(1, (int)Nx - 1); // (fold row: the edge stream's launches do every plane's, the main stream's the owned planes')
       if (!(lean || vg)) { // ghost flips / ABC save touch the whole grid: the interior must see them
-         launch_pre(s_edge);
+         launch_pre(s_edge, g);
          HIPCHK(hipEventRecord(ev_pre, s_edge));
          HIPCHK(hipStreamWaitEvent(s_main, ev_pre, 0));
       }
       // edge stream: first / last owned plane
-      fold_x0 = 0; fold_x1 = (int)Nx;
-      launch_air(s_edge, xl, xl + 1);
-      if (xh > xl) launch_air(s_edge, xh, xh + 1);
-      launch_abc(s_edge, bna_lo); launch_abc(s_edge, bna_hi);
-      launch_rigid(s_edge, bn_lo); launch_rigid(s_edge, bn_hi);
-      launch_fd(s_edge, bnl_lo); launch_fd(s_edge, bnl_hi);
-      launch_io(s_edge, n, false, in_lo); launch_io(s_edge, n, false, in_hi);
+      launch_air(s_edge, g, xl, xl + 1);
+      if (xh > xl) launch_air(s_edge, g, xh, xh + 1);
+      launch_abc(s_edge, g, bna_lo); launch_abc(s_edge, g, bna_hi);
+      launch_rigid(s_edge, g, be, bn_lo); launch_rigid(s_edge, g, be, bn_hi);
+      launch_fd(s_edge, g, be, bnl_lo); launch_fd(s_edge, g, be, bnl_hi);
+      launch_io(s_edge, g, n, false, in_lo); launch_io(s_edge, g, n, false, in_hi);
       HIPCHK(hipEventRecord(ev_edge, s_edge));
       // main stream: interior planes
-      fold_x0 = 1; fold_x1 = (int)Nx - 1;
-      launch_air(s_main, xl + 1, xh);
-      launch_abc(s_main, bna_mid);
-      launch_rigid(s_main, bn_mid);
-      launch_fd(s_main, bnl_mid);
-      launch_io(s_main, n, true, in_mid);
+      launch_air(s_main, g, xl + 1, xh);
+      launch_abc(s_main, g, bna_mid);
+      launch_rigid(s_main, g, bm, bn_mid);
+      launch_fd(s_main, g, bm, bnl_mid);
+      launch_io(s_main, g, n, true, in_mid);
       HIPCHK(hipGetLastError());
       in_step = true;
       return PF_OK;
@@ -247,7 +247,6 @@
          if (pair_phase == 0) {        // u^{n+1} complete in bufC; node values and branch state in place from here on
             ub[0] = wsT2; ub[2] = wsP[1]; // (three buffers: both wsP[1] -- a node's u^{n+2} overwrites its u^n)
             std::swap(vh1, vh1b); std::swap(gh1, gh1b);
-            bs_vout = bs_gout = nullptr;
             u0_src = pB; u1 = bufC; u0 = bufD;
             pair_phase = 1;
          } else if (pair_phase == 1) { // u^{n+2} complete in bufD; node values: u^{n+1} in P0, u^{n+2} in T2 (= P1 with three buffers) -> u^{n+3} into T3 (= P2)
@@ -269,7 +268,6 @@
             if (pair_phase == 0) { // second half: node values and branch state in place
                ub[0] = ub[2] = wsP[1];
                std::swap(vh1, vh1b); std::swap(gh1, gh1b);
-               bs_vout = bs_gout = nullptr;
             } else { ub[0] = wsP[2]; ub[1] = wsP[1]; ub[2] = wsP[0]; }
          } else { Real *t = ub[2]; ub[2] = ub[1]; ub[1] = ub[0]; ub[0] = t; }
          if (pair_phase == 0) { // u^{n+1} is complete in bufC: second half reads u^n as the old state and writes bufD

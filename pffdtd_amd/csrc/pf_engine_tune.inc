@@ -3,22 +3,21 @@
    // ---- which interior path?  Measured, not guessed: at creation the candidates run three times each on the real grids,
    // writing to scratch (the state is not touched): lean fused kernel, barrier-free kernel with virtual ghosts, and --
    // where a box exists -- a temporally blocked pair incl. its shell.  The boundary pass and the I/O are common to all.
-   // (7-point only; explicit air_variant requests and debug 0x8000 skip it.)  Sizes decide in ways no static rule
+   // (7-point only; explicit air_variant requests and PF_DBG_NO_AUTOTUNE skip it.)  Sizes decide in ways no static rule
    // caught: 1024^3 fp32 pair 411 > lean 377 > barrier-free 364 Gvox/s, 896^3 barrier-free 362 > pair 335 > lean 303.
    // 13-point: one in-place-equivalent single step (written to scratch) against half a blocked pair with its shell
    // 13-point single steps: lanes per row segment of k_air_fcc (64 / 32 / 16) measured where they pad the rows differently --
    // the static rule asks for a 25 % narrower padded row before it leaves 64 lanes, which rooms stored along their longest axis
    // (2852 columns = 11.1 segments of 256) never offer, although the half-empty last segment costs them 7 % of the lanes
    int autotune_fcc_lw() {
-      if (!fcc || !abck || sg || vbase != 0 || (op.debug & 0x8300) || lw_force || !(op.slab_first && op.slab_last)) return PF_OK;
+      if (!fcc || !abck || sg || vbase != 0 || (op.debug & (PF_DBG_NO_AUTOTUNE | PF_DBG_LW32 | PF_DBG_LW16)) || lw_force || !(op.slab_first && op.slab_last)) return PF_OK;
       if (Nx * Ny * Nz < ((int64_t)1 << 22)) return PF_OK;
       constexpr int V = pf::VecOf<Real>::V;
       Real *scr = try_dzalloc<Real>(npad);
       if (!scr) return PF_OK;
       hipEvent_t e0, e1;
       HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-      Real *U0 = u0;
-      u0_src = U0; u0 = scr; // (out of place: the state is not touched)
+      const Grids g{u0, u1, scr}; // (out of place: the state is not touched)
       int best_lw = 0;
       float best = 0;
       int64_t seen = -1;
@@ -27,9 +26,9 @@
          if (w == seen) continue; // same padded width as the wider segment: the wider one wins anyway
          seen = w;
          lw_force = lw;
-         launch_air_march(s_main, 1, (int)Nx - 1);
+         launch_air_march(s_main, g, 1, (int)Nx - 1);
          hipEventRecord(e0, s_main);
-         for (int i = 0; i < 3; i++) launch_air_march(s_main, 1, (int)Nx - 1);
+         for (int i = 0; i < 3; i++) launch_air_march(s_main, g, 1, (int)Nx - 1);
          hipEventRecord(e1, s_main);
          hipEventSynchronize(e1);
          float ms = 0;
@@ -42,9 +41,9 @@
       // (345.0-345.3 against 335-342 Gvox/s in alternating runs); cubes keep the banded one (2.32 against 2.46 ms at 1024^3).
       for (int mode : {0}) {
          order_force = mode;
-         launch_air_march(s_main, 1, (int)Nx - 1);
+         launch_air_march(s_main, g, 1, (int)Nx - 1);
          hipEventRecord(e0, s_main);
-         for (int i = 0; i < 3; i++) launch_air_march(s_main, 1, (int)Nx - 1);
+         for (int i = 0; i < 3; i++) launch_air_march(s_main, g, 1, (int)Nx - 1);
          hipEventRecord(e1, s_main);
          hipEventSynchronize(e1);
          float ms = 0;
@@ -52,7 +51,6 @@
          if (ms < 0.985f * best) best = ms; else order_force = -1;
       }
       tune_ms[1] = best / 3;
-      u0 = U0; u0_src = nullptr;
       hipEventDestroy(e0); hipEventDestroy(e1);
       HIPCHK(hipStreamSynchronize(s_main));
       hipFree(scr);
@@ -60,7 +58,7 @@
    }
    int autotune_fcc() {
       if (!tb2) return autotune_fcc_lw();
-      if (vbase != 0 || (op.debug & 0x8000)) return PF_OK;
+      if (vbase != 0 || (op.debug & PF_DBG_NO_AUTOTUNE)) return PF_OK;
       hipEvent_t e0, e1;
       HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
       HIPCHK(hipDeviceSynchronize());
@@ -74,17 +72,15 @@
          hipEventElapsedTime(&ms, e0, e1);
          return ms / 3;
       };
-      Real *U0 = u0, *U1 = u1;
-      u0_src = U0; u0 = bufC;
-      for (int i = 0; i < 8 && (double)i * (double)(Nx * Ny * Nz) < 8.0e9; i++) launch_air_march(s_main, 1, (int)Nx - 1); // clocks up
+      const Grids g1{u0, u1, bufC}, g2{u1, bufC, bufD}; // the two steps of a pair
+      for (int i = 0; i < 8 && (double)i * (double)(Nx * Ny * Nz) < 8.0e9; i++) launch_air_march(s_main, g1, 1, (int)Nx - 1); // clocks up
       HIPCHK(hipStreamSynchronize(s_main));
-      tune_ms[1] = timed([&] { launch_flips(s_main); launch_air_march(s_main, 1, (int)Nx - 1); });
+      tune_ms[1] = timed([&] { launch_flips(s_main, g1); launch_air_march(s_main, g1, 1, (int)Nx - 1); });
       tune_ms[2] = 0.5f * timed([&] {
-         launch_tb2(s_main, U0, U1, bufC, bufD);
-         u0_src = U0; u1 = U1; u0 = bufC; launch_shell(s_main);
-         u0_src = U1; u1 = bufC; u0 = bufD; launch_shell(s_main);
+         launch_tb2(s_main, 0, g1.old, g1.cur, bufC, bufD);
+         launch_shell(s_main, g1);
+         launch_shell(s_main, g2);
       });
-      u0_src = nullptr; u0 = U0; u1 = U1;
       if (!(tune_ms[2] < pair_margin * tune_ms[1])) { // not worth it: drop the pair path and its two grids
          tb2 = false;
          for (Real *g : {bufC, bufD}) { own_list.erase(std::remove(own_list.begin(), own_list.end(), g), own_list.end()); hipFree(g); }
@@ -118,8 +114,8 @@
       const float scale = sampled ? (float)(1.0 / tb_sample_frac) : 1.f; // sampled times are reported as whole-launch equivalents
       auto time_fwd = [&](Real *A, Real *B, Real *C, Real *D) -> float {
          hipEventRecord(e0, s_main);
-         launch_probe(s_main, A, B, C, D, true);
-         launch_probe(s_main, A, B, C, D, true);
+         launch_probe(s_main, 0, A, B, C, D, true);
+         launch_probe(s_main, 0, A, B, C, D, true);
          hipEventRecord(e1, s_main);
          hipEventSynchronize(e1);
          float ms = 0;
@@ -127,7 +123,7 @@
          return ms / 2 * scale;
       };
       auto grid = [&](int i, Real *fallback) { return i >= 0 ? pool[i] : fallback; };
-      for (int i = 0; i < 4; i++) launch_probe(s_main, grid(first[0], u0), grid(first[1], u1), pool[first[2]], pool[first[3]]); // clocks up
+      for (int i = 0; i < 4; i++) launch_probe(s_main, 0, grid(first[0], u0), grid(first[1], u1), pool[first[2]], pool[first[3]]); // clocks up
       struct Cand { int r[4]; float ms; };
       std::vector<Cand> cands;
       auto eval = [&](const int r[4]) {
@@ -200,7 +196,7 @@
             Real *A = grid(c.r[0], u0), *B = grid(c.r[1], u1), *C = pool[c.r[2]], *D = pool[c.r[3]];
             auto full = [&](Real *a, Real *b, Real *cc, Real *d) {
                hipEventRecord(e0, s_main);
-               launch_probe(s_main, a, b, cc, d); launch_probe(s_main, a, b, cc, d);
+               launch_probe(s_main, 0, a, b, cc, d); launch_probe(s_main, 0, a, b, cc, d);
                hipEventRecord(e1, s_main); hipEventSynchronize(e1);
                float ms = 0; hipEventElapsedTime(&ms, e0, e1);
                return ms / 2;
@@ -236,14 +232,14 @@
       HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
       const int tsave = op.timing;
       op.timing = 0;
-      Real *const s0 = u0, *const s1 = u1;
-      auto one_step = [&](Real *a, Real *b) { // u0 = a, u1 = b; all-zero state: every kernel writes zeros
-         u0 = a; u1 = b;
-         launch_pre(s_main);
-         launch_air(s_main, 1, (int)Nx - 1);
-         launch_abc(s_main, {0, Nba});
-         launch_rigid(s_main, {0, Nb});
-         launch_fd(s_main, {0, Nbl});
+      auto one_step = [&](Real *a, Real *b) { // u^{n-1} in a, u^n in b, in place; all-zero state: every kernel writes zeros
+         const Grids g{a, b, a};
+         const Bnd bn = bnd(0, 0);
+         launch_pre(s_main, g);
+         launch_air(s_main, g, 1, (int)Nx - 1);
+         launch_abc(s_main, g, {0, Nba});
+         launch_rigid(s_main, g, bn, {0, Nb});
+         launch_fd(s_main, g, bn, {0, Nbl});
       };
       auto time_pair = [&](Real *a, Real *b) -> float {
          hipEventRecord(e0, s_main);
@@ -268,7 +264,6 @@
             worst = std::max(worst, ms);
          }
       op.timing = tsave;
-      u0 = s0; u1 = s1;
       if (verbose) fprintf(stderr, "pffdtd_hip: grid placement (single steps), %d pairs of a pool of %d: as allocated %.4f, chosen %.4f, slowest %.4f ms per step\n",
                            (int)place_ms.size(), n, first, best, worst);
       for (int i = 0; i < n; i++) HIPCHK(hipMemsetAsync(pool[i], 0, npad * sizeof(Real), s_main)); // (zeros from zeros; be explicit)
@@ -288,7 +283,7 @@
       const int fit = (int)std::floor(((double)free_b - 0.03 * (double)total_b) / gb);
       return std::max(0, std::min(want, std::min(cap, fit)));
    }
-   bool place_single_ok() const { return !(op.debug & 0x8000) && !op.energy && vbase == 0 && npad * (int64_t)sizeof(Real) >= ((int64_t)64 << 20); }
+   bool place_single_ok() const { return !(op.debug & PF_DBG_NO_AUTOTUNE) && !op.energy && vbase == 0 && npad * (int64_t)sizeof(Real) >= ((int64_t)64 << 20); }
    int sample_placement_single() {
       if (!own_grids || !place_single_ok()) return PF_OK;
       int extra = 4;
@@ -312,7 +307,7 @@
       return PF_OK;
    }
    int sample_placement() {
-      if (!tb2 || tb2_slab || !bufC || !bufD || (op.debug & 0x8000) || vbase == 41) return PF_OK;
+      if (!tb2 || tb2_slab || !bufC || !bufD || (op.debug & PF_DBG_NO_AUTOTUNE) || vbase == 41) return PF_OK;
       int extra = tb3 ? 3 : 4;
       extra = pool_extra(extra, tb3 ? 5 : 4);
       if (extra == 0 && !own_grids) return PF_OK;
@@ -371,7 +366,7 @@
             HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
             auto t4 = [&](Real *A, Real *B, Real *C, Real *D) {
                hipEventRecord(e0, s_main);
-               launch_probe(s_main, A, B, C, D, true);
+               launch_probe(s_main, 0, A, B, C, D, true);
                hipEventRecord(e1, s_main); hipEventSynchronize(e1);
                float ms = 0; hipEventElapsedTime(&ms, e0, e1);
                return ms;
@@ -426,12 +421,12 @@
       if (five && n >= 5 && tb3_geom && tb2_geom && !(op.slab_first && op.slab_last)) {
          // triples: the wall regions must fit the triples' box (init_walls re-orders the lossy arrays: before the first step only)
          tb2_slab = true;
-         if (!(op.debug & 0x10000000)) { int rcw = init_walls(true); if (rcw) return rcw; }
+         if (!(op.debug & PF_DBG_NO_WALL_REGIONS)) { int rcw = init_walls(true); if (rcw) return rcw; }
          if (wl_on) {
             std::vector<Real *> pool;
             for (int i = 0; i < n; i++) pool.push_back((Real *)grids[i]);
             int w[4] = {0, 1, 2, 3};
-            if (n > 5 && !(op.debug & 0x8000)) {
+            if (n > 5 && !(op.debug & PF_DBG_NO_AUTOTUNE)) {
                const int first[4] = {0, 1, 2, 3};
                tb2_probe = true;
                int rc = search_placement(pool, false, true, place_evals(), first, w);
@@ -467,7 +462,7 @@
       std::vector<Real *> pool;
       for (int i = 0; i < n; i++) pool.push_back((Real *)grids[i]);
       int w[4] = {0, 1, 2, 3};
-      if (n > 4 && !(op.debug & 0x8000)) {
+      if (n > 4 && !(op.debug & PF_DBG_NO_AUTOTUNE)) {
          const int first[4] = {0, 1, 2, 3};
          tb2_probe = true;
          int rc = search_placement(pool, false, true, place_evals(), first, w);
@@ -479,12 +474,12 @@
       u0 = pool[w[0]]; u1 = pool[w[1]]; bufC = pool[w[2]]; bufD = pool[w[3]];
       for (int i = 0; i < 4; i++) idx[i] = w[i];
       tb2_slab = true;
-      if (!wl_on && !(op.debug & 0x10000000)) { int rcw = init_walls(true); if (rcw) return rcw; }
+      if (!wl_on && !(op.debug & PF_DBG_NO_WALL_REGIONS)) { int rcw = init_walls(true); if (rcw) return rcw; }
       return PF_OK;
    }
    int autotune() {
       if (fcc) return autotune_fcc();
-      if (vbase != 0 || fcc || op.energy || (op.debug & 0x8000) || !use_dpp || !(lean || vg)) return PF_OK;
+      if (vbase != 0 || fcc || op.energy || (op.debug & PF_DBG_NO_AUTOTUNE) || !use_dpp || !(lean || vg)) return PF_OK;
       if (Nx * Ny * Nz < ((int64_t)1 << 22)) return PF_OK; // tiny grids: launch-bound either way
       Real *scr = bufC;
       bool own = false;
@@ -505,14 +500,14 @@
       };
       const bool lean0 = lean, vg0 = vg;
       Real *U0 = u0, *U1 = u1;
-      lean = true; vg = false; u0_src = U0; u0 = scr;
+      const Grids gs{U0, U1, scr}; // a single step into scratch: the state is not touched
+      lean = true; vg = false;
       // the device has been idle while the host built the lists: ramp its clocks first (~20 ms of work), or the first
       // candidate is measured -- and every launch here profiled -- at idle clocks (seen: +56 % per launch)
-      for (int i = 0; i < 8 && (double)i * (double)(Nx * Ny * Nz) < 8.0e9; i++) launch_air_lean(s_main, 1, (int)Nx - 1);
+      for (int i = 0; i < 8 && (double)i * (double)(Nx * Ny * Nz) < 8.0e9; i++) launch_air_lean(s_main, gs, 1, (int)Nx - 1);
       HIPCHK(hipStreamSynchronize(s_main));
-      tune_ms[0] = timed([&] { launch_air_lean(s_main, 1, (int)Nx - 1); });
-      u0 = U0; u0_src = nullptr;
-      lean = false; vg = true; v1_dst = scr;
+      tune_ms[0] = timed([&] { launch_air_lean(s_main, gs, 1, (int)Nx - 1); });
+      lean = false; vg = true;
       { // the barrier-free kernel, with 64 / 32 / 16 lanes per row segment where those pad the rows differently
          constexpr int V = pf::VecOf<Real>::V;
          int best_lw = 0;
@@ -523,55 +518,46 @@
             if (k > 0 && w == seen[k - 1]) continue; // same padded width as the wider segment: the wider one wins anyway
             seen[k++] = w;
             lw_force = lw;
-            const float t = timed([&] { launch_air_march(s_main, 1, (int)Nx - 1); });
+            const float t = timed([&] { launch_air_march(s_main, gs, 1, (int)Nx - 1); });
             if (best_lw == 0 || t < 0.98f * tune_ms[1]) { tune_ms[1] = t; best_lw = lw; }
          }
          lw_force = best_lw;
       }
-      v1_dst = nullptr;
       lean = lean0; vg = vg0;
       if (hipGetLastError() != hipSuccess) { lean = lean0; vg = vg0; }
       else if (tune_ms[1] < 0.97f * tune_ms[0]) { lean = false; vg = true; }
       else if (tune_ms[0] < 0.97f * tune_ms[1]) { lean = true; vg = false; }
+      const Grids g1{U0, U1, bufC}, g2{U1, bufC, bufD}; // the first two steps of a blocked pass
+      const Bnd bn = bnd(0, 0);                         // (fields, node values and branch state are all zeros at creation and stay so: every boundary launch in place)
       if (tb3) {
          // three steps per pass, the boundary pass included: the single steps get theirs added (fields and branch state are all zeros
          // at creation and stay so)
-         u0_src = U0; u0 = scr;
-         const float tb = timed([&] { launch_rigid(s_main, {0, Nb}); });
-         u0_src = nullptr; u0 = U0;
+         const float tb = timed([&] { launch_rigid(s_main, gs, bn, {0, Nb}); });
          tune_ms[0] += tb; tune_ms[1] += tb;
          tune_ms[2] = (1.f / 3.f) * timed([&] {
-            bnd_sel = wl_rest;
-            u0_src = U0; u1 = U1; u0 = bufC; launch_dirty_tiles(s_main); launch_rigid(s_main, {0, wl_nrest});
-            launch_walls(s_main, s_main, U0, U1, bufC, bufD, ub[0], ub[1], ub[2]);
-            launch_tb3(s_main, U0, U1, bufC, bufD, bufE);
-            u0_src = U1; u1 = bufC; u0 = bufD; launch_dirty_tiles(s_main); launch_rigid(s_main, {0, wl_nrest});
-            bnd_sel = nullptr;
-            u0_src = bufC; u1 = bufD; u0 = bufE; launch_shell(s_main); launch_rigid(s_main, {0, Nb});
-            u0_src = nullptr; u0 = U0; u1 = U1;
+            launch_dirty_tiles(s_main, g1); launch_rigid(s_main, g1, bn.with(wl_rest), {0, wl_nrest});
+            launch_walls(s_main, s_main, U0, U1, bufC, bufD, ub[0], ub[1], ub[2], bn.in, {vh1b, gh1b});
+            launch_tb3(s_main, 0, U0, U1, bufC, bufD, bufE);
+            launch_dirty_tiles(s_main, g2); launch_rigid(s_main, g2, bn.with(wl_rest), {0, wl_nrest});
+            const Grids g3{bufC, bufD, bufE};
+            launch_shell(s_main, g3); launch_rigid(s_main, g3, bn, {0, Nb});
          });
       } else if (tb2 && wl_on) {
          // wall regions: the pair then includes the boundary pass, so the single steps get theirs added (fields and branch state
          // are all zeros at creation and stay so)
-         u0_src = U0; u0 = scr;
-         const float tb = timed([&] { launch_rigid(s_main, {0, Nb}); });
-         u0_src = nullptr; u0 = U0;
+         const float tb = timed([&] { launch_rigid(s_main, gs, bn, {0, Nb}); });
          tune_ms[0] += tb; tune_ms[1] += tb;
          tune_ms[2] = 0.5f * timed([&] {
-            launch_tb2(s_main, U0, U1, bufC, bufD);
-            bnd_sel = wl_rest;
-            u0_src = U0; u1 = U1; u0 = bufC; launch_dirty_tiles(s_main); launch_rigid(s_main, {0, wl_nrest});
-            launch_walls(s_main, s_main, U0, U1, bufC, bufD, ub[0], ub[1], ub[2]);
-            u0_src = U1; u1 = bufC; u0 = bufD; launch_dirty_tiles(s_main); launch_rigid(s_main, {0, wl_nrest});
-            bnd_sel = nullptr;
-            u0_src = nullptr; u0 = U0; u1 = U1;
+            launch_tb2(s_main, 0, U0, U1, bufC, bufD);
+            launch_dirty_tiles(s_main, g1); launch_rigid(s_main, g1, bn.with(wl_rest), {0, wl_nrest});
+            launch_walls(s_main, s_main, U0, U1, bufC, bufD, ub[0], ub[1], ub[2], bn.in, {vh1b, gh1b});
+            launch_dirty_tiles(s_main, g2); launch_rigid(s_main, g2, bn.with(wl_rest), {0, wl_nrest});
          });
       } else if (tb2) {
          tune_ms[2] = 0.5f * timed([&] {
-            launch_tb2(s_main, U0, U1, bufC, bufD);
-            u0_src = U0; u1 = U1; u0 = bufC; launch_shell(s_main);
-            u0_src = U1; u1 = bufC; u0 = bufD; launch_shell(s_main);
-            u0_src = nullptr; u0 = U0; u1 = U1;
+            launch_tb2(s_main, 0, U0, U1, bufC, bufD);
+            launch_shell(s_main, g1);
+            launch_shell(s_main, g2);
          });
       }
       if (tb2) {

@@ -528,23 +528,22 @@
                  tbx0, tbx1, tby0, tby1, tbz0, tbz1, (long)npen, (long)nrec, (long)wl_nrest, (long)Nb, dps.back(), zb, (long)nfast, (long)ngen, (long)wl_nbrk, blen, (long)hinfo.size(), (long)wl_nbown_dbg, wl_brk_lds);
       return PF_OK;
    }
-   // both steps of the wall regions: A = u^{n-1}, B = u^n -> C = u^{n+1}, D = u^{n+2}; branch state vh1 / gh1 -> vh1b / gh1b;
+   // both steps of the wall regions: A = u^{n-1}, B = u^n -> C = u^{n+1}, D = u^{n+2}; branch state si -> so;
    // node values: P2 = u^{n-1} and P1 = u^n are read, P0 <- u^{n+1}, P1 <- u^{n+2}
    // (s_gen: the stream of the generic blocks -- edges, corners: few waves, each a long chain of dependent steps)
-   // ns = 2: both steps of a pair, A, B -> C, D; branch state vh1 / gh1 -> vh1b / gh1b (the caller swaps), node values P2, P1 -> P0, P1.
-   // ns = 1: ONE step, A, B -> C (the third step of a triple): branch state in place, node values P2 -> P0 (P1, D unused).
-   void launch_walls(hipStream_t s, hipStream_t s_gen, const Real *A, const Real *B, Real *C, Real *D, Real *P0, Real *P1, const Real *P2, int ns = 2) {
-      launch_walls_x(s, s_gen, A, B, C, D, nullptr, P2, P1, P0, P1, nullptr, ns, 0xf); // (three node-value buffers: u^{n+2} of a node overwrites its u^n)
+   void launch_walls(hipStream_t s, hipStream_t s_gen, const Real *A, const Real *B, Real *C, Real *D, Real *P0, Real *P1, const Real *P2, BranchState si, BranchState so) {
+      launch_walls_x(s, s_gen, A, B, C, D, nullptr, P2, P1, P0, P1, nullptr, si, so, 2, 0xf); // (three node-value buffers: u^{n+2} of a node overwrites its u^n)
    }
    // the general form: node values x2 = u^{n-1}, x1 = u^n are read, o1 / o2 / o3 receive u^{n+1} / u^{n+2} / u^{n+3}; gmask: which launch groups
-   // (bit 0: the x / y regions, bits 1-3: the column strips); ns = 3: three steps in one pass (x / y regions with three-step tables: wl_ns3)
+   // (bit 0: the x / y regions, bits 1-3: the column strips); ns = 3: three steps in one pass (x / y regions with three-step tables: wl_ns3);
+   // ns = 1: ONE step, A, B -> C (the third step of a triple), x2 -> o1.  Branch state si -> so (ns = 1: one and the same; else the caller swaps its two copies)
    void launch_walls_x(hipStream_t s, hipStream_t s_gen, const Real *A, const Real *B, Real *C, Real *D, Real *E, const Real *x2, const Real *x1, Real *o1, Real *o2, Real *o3,
-                       int ns, unsigned gmask) {
+                       BranchState si, BranchState so, int ns, unsigned gmask) {
       pf::WallParams<Real> wp{};
       wp.A = A; wp.B = B; wp.C = C; wp.D = D; wp.E = E;
       wp.plane = plane; wp.Nx = (int)Nx; wp.Ny = (int)Ny; wp.Nz = (int)Nz; wp.P = (int)P; wp.first = op.slab_first; wp.last = op.slab_last;
       wp.pen = wl_pen; wp.rec = wl_rec;
-      wp.sv_in = vh1; wp.sg_in = gh1; wp.sv_out = ns == 1 ? vh1 : vh1b; wp.sg_out = ns == 1 ? gh1 : gh1b;
+      wp.sv_in = si.v; wp.sg_in = si.g; wp.sv_out = so.v; wp.sg_out = so.g;
       wp.x2 = x2; wp.x1 = x1; wp.o1 = o1; wp.o2 = o2; wp.o3 = o3;
       wp.ssaf = d_ssaf; wp.mat = d_mat; wp.Mb = d_Mb; wp.mq = d_mq; wp.beta = d_beta;
       wp.lo2 = lo2; wp.sl2 = sl2; wp.l = l; wp.mmax = mb_max; wp.nmat = sd.Nm;
@@ -564,16 +563,16 @@
       }
    }
    // the frame's bricks (pf_brick.h): `ns` steps in one launch, A = u^{n-1}, B = u^n -> G0 = u^{n+1}, G1 = u^{n+2} (, G2 = u^{n+3}); branch state
-   // vh1 / gh1 -> vh1b / gh1b (the caller swaps, as for the wall regions); node values x2 = u^{n-1}, x1 = u^n are read, those of the steps go
+   // si -> so (the caller swaps its two copies, as for the wall regions); node values x2 = u^{n-1}, x1 = u^n are read, those of the steps go
    // to O0, O1 (, O2) -- buffers nobody reads during the pass.
-   void launch_bricks(hipStream_t s, const Real *A, const Real *B, Real *G0, Real *G1, Real *G2, const Real *x2, const Real *x1, Real *O0, Real *O1, Real *O2, int ns) {
+   void launch_bricks(hipStream_t s, const Real *A, const Real *B, Real *G0, Real *G1, Real *G2, const Real *x2, const Real *x1, Real *O0, Real *O1, Real *O2, BranchState si, BranchState so, int ns) {
       if (!wl_nbrk) return;
       pf::BrickParams<Real> bp{};
       bp.x2 = x2; bp.x1 = x1;
       bp.A = A; bp.B = B; bp.G[0] = G0; bp.G[1] = G1; bp.G[2] = G2; bp.O[0] = O0; bp.O[1] = O1; bp.O[2] = O2;
       bp.plane = plane; bp.Nx = (int)Nx; bp.Ny = (int)Ny; bp.Nz = (int)Nz; bp.P = (int)P;
       bp.brk = wl_brk; bp.info = wl_binfo; bp.los = wl_blos;
-      bp.sv_in = vh1; bp.sg_in = gh1; bp.sv_out = vh1b; bp.sg_out = gh1b;
+      bp.sv_in = si.v; bp.sg_in = si.g; bp.sv_out = so.v; bp.sg_out = so.g;
       bp.ssaf = d_ssaf; bp.mat = d_mat; bp.Mb = d_Mb; bp.mq = d_mq; bp.beta = d_beta;
       bp.lo2 = lo2; bp.sl2 = sl2; bp.l = l; bp.nmat = (int)sd.Nm; bp.ns = ns;
       bp.first = op.slab_first; bp.last = op.slab_last;

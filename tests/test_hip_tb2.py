@@ -18,10 +18,10 @@ def scene(src, Nt=23, n=(36, 64, 280), **kw):
     return synth.shoebox(*n, Nt=Nt, Nm=2, Mb=[11, 3], src=src, rcv=rcv, **kw)
 
 
-def run(sim, variant, prec="single", **kw):
+def run(sim, variant, prec="single", timing=True, **kw):
     sd = sim_data.SimData.from_sim(sim, prec, build_mask=False)
     sd.scale_input()
-    eng = engine.HipEngine(sd, air_variant=variant, timing=True, **kw)
+    eng = engine.HipEngine(sd, air_variant=variant, timing=timing, **kw)
     eng.run(0, sd.Nt)
     tm = eng.timing()
     g = [eng.get_grid(0).copy(), eng.get_grid(1).copy()]
@@ -670,6 +670,56 @@ def test_three_steps_per_pass_with_geometry_inside_the_box(prec):
         assert np.array_equal(out, ref.u_out), chunk
         for a, b in zip(g, base_g):
             assert np.array_equal(a[1:-1, 1:-1, 1:-1], b[1:-1, 1:-1, 1:-1]), chunk
+
+
+# ---- the drivers' branches without per-launch events: what callers and the benchmark run ------------------------------------------------
+PF_DBG_NO_TRIPLES, PF_DBG_NO_WALL_REGIONS = 0x20000, 0x10000000  # (csrc/pf_debug.h)
+_EVENTLESS_SCENES = {"triples": lambda: triple_scene(Nt=100, n=(48, 100, 280)), "triples64": lambda: triple_scene(Nt=100, n=(48, 100, 264)),
+                     "fcc_box": lambda: fcc_scene()}
+_eventless_refs = {}
+
+
+def _eventless_ref(key, prec):
+    """the oracle's receivers and both final fields of a scene, computed once and read-only"""
+    if (key, prec) not in _eventless_refs:
+        sd = sim_data.SimData.from_sim(_EVENTLESS_SCENES[key](), prec)
+        sd.scale_input()
+        e = oracle.Engine(sd)
+        for k in range(sd.Nt):
+            e.step(k)
+        ref = [sd.u_out.copy(), e.grid(0).copy(), e.grid(1).copy()]
+        e.close()
+        for a in ref:
+            a.setflags(write=False)
+        _eventless_refs[(key, prec)] = ref
+    return _eventless_refs[(key, prec)]
+
+
+@pytest.mark.parametrize("key,prec,chunk,dbg,want", [
+    ("triples", "single", 0, 0, dict(wall_three_steps=9, tb2_dirty_tiles=0)),
+    ("triples", "single", 7, 0, dict(wall_three_steps=9, tb2_dirty_tiles=0)),  # a ring flush inside a triple: merged and unmerged readouts alternate
+    ("triples64", "double", 0, 0, dict(wall_three_steps=0)),                   # the third step is left: unmerged readouts
+    ("triples", "single", 0, PF_DBG_NO_TRIPLES, dict(wall_three_steps=0)),
+    ("triples", "single", 0, PF_DBG_NO_TRIPLES | PF_DBG_NO_WALL_REGIONS, dict(wall_three_steps=0, wall_blocks=[0, 0])),
+    ("fcc_box", "single", 0, 0, dict(wall_blocks=[0, 0]))],
+    ids=["triples", "triples_ring7", "triples_fp64", "pairs_wall_regions", "pairs_list_shell", "fcc_box"])
+def test_blocked_steps_without_events_give_the_oracles_bits(key, prec, chunk, dbg, want):
+    """Every other test here creates its engine with timing=True, and with events on the drivers take other branches: step_triple never merges
+    the readouts of steps n+1 and n+2 into one launch, step_pair joins the edge stream before the pair kernel instead of after it.  Engines
+    created with timing=False -- the arrangement callers and the benchmark's timed region run: receivers and both final fields equal the
+    oracle's.  (fp32 triples in a box room with sources inside k_tb3, no tile stepping singly and every wall region on three steps -- what
+    wall_three_steps == 9 and tb2_dirty_tiles == 0 say -- is the code's condition for the merged readout.)"""
+    ref_out, ref_u0, ref_u1 = _eventless_ref(key, prec)
+    assert np.abs(ref_out).max() > 0
+    out, g, tm = run(_EVENTLESS_SCENES[key](), 40, prec=prec, timing=False, readout_chunk=chunk, debug=dbg)
+    assert tm["air_path"] == 2 and tm["steps"] == 0, tm  # blocked steps, and no events harvested
+    for k, v in want.items():
+        assert tm[k] == v, (k, tm)
+    if dbg == PF_DBG_NO_TRIPLES:
+        assert sum(tm["wall_blocks"]) > 0, tm
+    assert np.array_equal(out, ref_out)
+    assert np.array_equal(g[0][1:-1, 1:-1, 1:-1], ref_u0[1:-1, 1:-1, 1:-1])
+    assert np.array_equal(g[1][1:-1, 1:-1, 1:-1], ref_u1[1:-1, 1:-1, 1:-1])
 
 
 def test_placement_search_grows_its_pool_when_no_assignment_is_fast(monkeypatch):
