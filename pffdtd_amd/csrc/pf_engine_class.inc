@@ -164,12 +164,10 @@ template <typename Real> struct Engine : EngineBase {
    Real *h_ring = nullptr; // pinned
    int64_t ring_depth = 0, ring_fill = 0, ring_n0 = 0;
    std::vector<int64_t> out_row; // sorted receiver slot -> caller row
-   // plane ranges of the sorted lists: lo = first owned plane (ix==1), hi = last owned plane (ix==Nx-2)
-   Range bn_lo, bn_mid, bn_hi, bnl_lo, bnl_mid, bnl_hi, bna_lo, bna_mid, bna_hi, in_lo, in_mid, in_hi;
-   // the same lists cut for the split-phase pairs, whose edge stream owns two planes per side: planes 1-2 / 3..Nx-4 / Nx-3..Nx-2
-   Range bn_lo2, bn_mid2, bn_hi2, bnl_lo2, bnl_mid2, bnl_hi2, in_lo2, in_mid2, in_hi2;
-   // ... and for the split-phase triples, three planes per side: planes 1-3 / 4..Nx-5 / Nx-4..Nx-2
-   Range bn_lo3, bn_mid3, bn_hi3, bnl_lo3, bnl_mid3, bnl_hi3, in_lo3, in_mid3, in_hi3;
+   // plane ranges of the sorted lists, cut for an edge stream that owns w planes per side (1: single steps, 2: split-phase pairs, 3: triples):
+   // lo = planes 1..w, mid = w+1..Nx-2-w, hi = Nx-1-w..Nx-2
+   struct Cut { Range lo, mid, hi; };
+   Cut bn_cut[4], bnl_cut[4], in_cut[4], bna_cut; // [w]; the ABC list: single steps only
    hipStream_t s_main = nullptr, s_edge = nullptr, s_wall = nullptr, s_wall2 = nullptr; // s_wall, s_wall2: a slab's wall regions, alike / generic blocks (created on first use)
    hipEvent_t ev_pre = nullptr, ev_edge = nullptr, ev_main = nullptr, ev_wall0 = nullptr, ev_wall = nullptr, ev_wall2 = nullptr;
    hipEvent_t ev_src0 = nullptr, ev_src1 = nullptr; // fork / join of k_tb3_src beside the box kernel (single domains: fork_tb3_src)
@@ -186,10 +184,6 @@ template <typename Real> struct Engine : EngineBase {
    // temporal blocking (pf_tb2.h): pairs of steps over a boundary-free box, single-step strips around it
    bool tb2 = false;                                      // pairs inside pf_engine_run (single-domain engines)
    bool tb2_geom = false, tb2_slab = false;               // slab engines: pairs across two split-phase steps (set_spares)
-   int pair_phase = 0;                                    // 1: between the two steps of a split-phase pair
-   bool pair_now = false;                                 // the step in flight is half of a pair
-   bool triple_now = false;                               // ... a third of a triple (tb3_slab; pair_phase then counts 0, 1, 2)
-   Real *pA = nullptr, *pB = nullptr;                     // u^{n-1}, u^n of the pair in flight
    Real *bufC = nullptr, *bufD = nullptr;                 // the two extra state grids of the out-of-place pair
    // three steps per pass (pf_tb3.h, Engine::step_triple): single-domain 7-point engines whose shell steps as wall regions.  Five
    // grids: the state (u^{n-1}, u^n) -> bufD = u^{n+2}, bufE = u^{n+3}; bufC holds u^{n+1} where somebody needs it in memory (the
@@ -226,7 +220,6 @@ template <typename Real> struct Engine : EngineBase {
    static constexpr int fcc_wt = 8; // waves per workgroup of k_tb2_fcc_x (two of them halo providers)
    int64_t sh_ntiles = 0;
    int sh_nyt = 0, sh_nzt = 0;
-   Real *u0_src = nullptr;                                // between the split-phase steps of a slab's pair / triple: u^{n-1} lies here, u0 is the grid being written
    // What one launch reads and writes is an argument of its launcher, never an engine field.
    // The grids of one step: old = u^{n-1}, cur = u^n -> nxt = u^{n+1}; in place (the single steps): old == nxt.  (cur is written too: its ghost cells, by the flips.)
    struct Grids {
@@ -234,7 +227,6 @@ template <typename Real> struct Engine : EngineBase {
       bool in_place() const { return old == nxt; }
       const Real *src() const { return in_place() ? nullptr : old; } // for the kernels that take "null: u^{n-1} is where u^{n+1} goes"
    };
-   Grids grids() const { return {u0_src ? u0_src : u0, u1, u0}; }
    struct BranchState { Real *v, *g; };
    // What a boundary launch needs beyond the grids: node values (u0b receives u^{n+1}, u2b holds u^{n-1}; may be one buffer), branch state in / out
    // (in place: the same), sel: the launch visits sel[range] of the boundary list (null: the range itself), the planes whose folded ghost row
@@ -247,6 +239,28 @@ template <typename Real> struct Engine : EngineBase {
       Bnd with(const int32_t *list) const { Bnd b = *this; b.sel = list; return b; }
    };
    Bnd bnd(int fold_b, int fold_e) const { return {ub[0], ub[2], {vh1, gh1}, {vh1, gh1}, nullptr, fold_b, fold_e}; } // a plain single step
+   // One blocked pass -- a pair or a triple -- by its names in time order: g[k] = the grid of u^{n-1+k}, x[k] = the node values of that time, branch state
+   // s0 before the pass -> s1 (equal: stepped in place).  Entries past the pass's length are null; entries of x may be one buffer (three node
+   // buffers: a node's u^{n+2} overwrites its u^n and its u^{n+3} its u^{n-1}, x[3] == x[1], x[4] == x[0]; pairs without wall regions: x[3] == x[0]).
+   // Step k of the pass and every launch that starts at it are windows into this.
+   struct Pass {
+      Real *g[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *x[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+      BranchState s0{nullptr, nullptr}, s1{nullptr, nullptr};
+      int len = 0; // 0: none, 2, 3
+      static Pass of_grids(Real *A, Real *B, Real *C, Real *D, Real *E = nullptr) { Pass p; p.g[0] = A; p.g[1] = B; p.g[2] = C; p.g[3] = D; p.g[4] = E; p.len = E ? 3 : 2; return p; }
+      Grids grids(int k) const { return {g[k], g[k + 1], g[k + 2]}; }
+      BranchState in(int k) const { return k == 0 ? s0 : s1; } // what a launch that starts at step k reads; all write s1
+      Bnd bnd(int k, const int32_t *sel = nullptr) const { return {x[k + 2], x[k], in(k), s1, sel, 0, 0}; } // (no fold row: virtual-ghost modes with one do not block)
+      // what step j of a launch of ns steps that starts at step `first` writes (null: the launch takes fewer steps)
+      Real *out_g(int first, int ns, int j) const { return j < ns ? g[first + 2 + j] : nullptr; }
+      Real *out_x(int first, int ns, int j) const { return j < ns ? x[first + 2 + j] : nullptr; }
+   };
+   // a slab's pass across split-phase steps (step_begin / step_end): `phase` of its steps are done.  The engine's own state (u0, u1, ub, vh1 ...) is
+   // that of the pass's start until its last step_end.
+   Pass pass;
+   int phase = 0;
+   bool in_pass() const { return pass.len != 0; }
+   Grids grids() const { return in_pass() ? pass.grids(phase) : Grids{u0, u1, u0}; } // the step in flight or next to run
    struct LeanExtra { int x2_begin = 0, x2_end = 0, nyt = -1, yt0 = 0; }; // a lean launch's second x slab [x2_begin, x2_end); its row strips: tiles [0, nyt) and [yt0, all) (-1: all tiles)
    // boundary nodes inside the column strips are updated by k_air_zstrip itself (it streams their lines anyway; in
    // the list kernel the floor / ceiling nodes of a box room cost half of the whole boundary pass)
@@ -262,9 +276,6 @@ template <typename Real> struct Engine : EngineBase {
    // wall regions (pf_wall.h): the shell of a blocked pair -- wall layers, ABC cells, ghost mirrors -- stepped in pairs too
    bool wl_on = false;
    int32_t *edge_sel3 = nullptr; int64_t n_edge_sel3 = 0; bool edge_sel3_failed = false; // slab triples: the nodes of both sides' edge planes, one list (step_begin)
-   Real *wsT2 = nullptr, *wsT3 = nullptr;                 // ... where the triple's u^{n+2} / u^{n+3} of the nodes go (round 6: two more buffers when there are five)
-   bool ws_five = false, ws_all3 = false;                 // ... five node-value buffers; the regions and the bricks take all three steps in the first split-phase step
-   Real *wsP[3] = {nullptr, nullptr, nullptr};            // slab pairs with wall regions: the node-value buffers u0b / u1b / u2b at the start of the pair
    // launch groups: 0 = regions normal to x / y (lanes along z, pencils of 8 cells); 1 / 2 / 3 = regions normal to z (lanes along
    // y) with vector pencils of 12 / 16 / 20 cells.  Each has a list of alike blocks and one of generic blocks.
    struct WlGroup { int nreg = 0; pf::WallRegion reg[pf::WALL_MAXREG]; uint32_t blk0[3] = {0, 0, 0}, nblk[3] = {0, 0, 0};
@@ -288,6 +299,13 @@ template <typename Real> struct Engine : EngineBase {
    int wl_uni = 0;                                        // the branch count every material of the scene has, else 0 (pf_wall.h UB)
    unsigned wl_rcv = 0;                                   // launch groups whose regions own a cell that holds a receiver (k_io of step n + 1 reads its u^{n+1})
    unsigned wall_g3() const { return (wl_ns3 ? 0x1u : 0u) | (wl_ns3z ? 0x8u : 0u); } // the launch groups that take three steps per pass
+   // a slab's triples: with five node-value buffers (init_walls), bricks and three-step tables for every group that has blocks, the wall regions and the
+   // frame's bricks take all three steps in the triple's FIRST split-phase step
+   bool slab_all3() const {
+      unsigned gblk = 0;
+      for (int gi = 0; gi < 4; gi++) if (wl_grp[gi].nblk[0] + wl_grp[gi].nblk[1] + wl_grp[gi].nblk[2]) gblk |= 1u << gi;
+      return ubx[0] && ubx[1] && wl_nbrk > 0 && gblk != 0 && (gblk & ~wall_g3()) == 0;
+   }
    // Which kernel steps list q of launch group gi by ns steps (pf_wall.h: wall_choose; launch_walls_x runs it, timing() reports it), and with it -- skip_c: u^{n+1} of the group's
    // cells stays unstored (the uniform-branch-count bodies test the pointer; nobody reads it in a triple of a single domain in which nothing steps singly and no receiver sits in
    // those cells); second: the x / y regions' second block list, the chunks of a two-step launch on three-step tables (init_walls: blk0b, mchunk2)
@@ -392,16 +410,13 @@ template <typename Real> struct Engine : EngineBase {
       if (hipMemset(p, 0, bytes) != hipSuccess) { (void)hipGetLastError(); hipFree(p); return nullptr; }
       return p;
    }
-   // split a sorted padded-index list into the ranges of plane 1 / planes 2..Nx-3 / plane Nx-2
-   void plane_ranges(const std::vector<int64_t> &idx, Range &lo, Range &mid, Range &hi, int w = 1) const {
-      const int64_t n = (int64_t)idx.size();
+   // split a sorted padded-index list into the ranges of planes 1..w / w+1..Nx-2-w / Nx-1-w..Nx-2
+   Cut plane_ranges(const std::vector<int64_t> &idx, int w) const {
       auto first_ge = [&](int64_t px) { return (int64_t)(std::lower_bound(idx.begin(), idx.end(), px * plane) - idx.begin()); };
-      if (w >= 2 && Nx < 4 * w) { lo = mid = hi = {0, 0}; return; } // (pairs / triples need far thicker slabs anyway)
+      if (w >= 2 && Nx < 4 * w) return {{0, 0}, {0, 0}, {0, 0}}; // (pairs / triples need far thicker slabs anyway)
       const int64_t b1 = first_ge(1), b2 = first_ge(1 + w), b3 = first_ge(Nx - 1 - w), b4 = first_ge(Nx - 1);
-      lo = {b1, std::min(b2, b4)};
-      if (Nx - 2 > 1) { mid = {b2, std::max(b2, b3)}; hi = {std::max(b2, b3), b4}; }
-      else { mid = {b2, b2}; hi = {b2, b2}; }
-      (void)n;
+      if (Nx - 2 > 1) return {{b1, std::min(b2, b4)}, {b2, std::max(b2, b3)}, {std::max(b2, b3), b4}};
+      return {{b1, std::min(b2, b4)}, {b2, b2}, {b2, b2}};
    }
 
    // Preconditions of the fused interior kernel (pf_air_fused.h).  They hold for every scene the reference's own
@@ -549,9 +564,7 @@ template <typename Real> struct Engine : EngineBase {
          for (int64_t i = 0; i < Nb; i++) adj[i] = sd.adj_bn[perm[i]];
          if ((rc = upload(&d_bn, idx.data(), Nb))) return rc;
          if ((rc = upload(&d_adj, adj.data(), Nb))) return rc;
-         plane_ranges(idx, bn_lo, bn_mid, bn_hi);
-         plane_ranges(idx, bn_lo2, bn_mid2, bn_hi2, 2);
-         plane_ranges(idx, bn_lo3, bn_mid3, bn_hi3, 3);
+         for (int w = 1; w <= 3; w++) bn_cut[w] = plane_ranges(idx, w);
          // which interior path?  0 = automatic; 3 = the reference's kernel sequence (memory flips, marching kernel, ABC list
          // kernels); 4 = barrier-free marching kernel with virtual ghost shell + in-kernel ABC; 7 = the same with the flips in
          // memory (the 13-point default); 25 = lean fused kernel (7-point); 40 / 41 = temporally blocked pairs forced / driver only
@@ -609,9 +622,7 @@ template <typename Real> struct Engine : EngineBase {
          if ((rc = upload(&d_bnl, idx.data(), Nbl))) return rc;
          if ((rc = upload(&d_ssaf, ssaf.data(), Nbl))) return rc;
          if ((rc = upload(&d_mat, mat.data(), Nbl))) return rc;
-         plane_ranges(idx, bnl_lo, bnl_mid, bnl_hi);
-         plane_ranges(idx, bnl_lo2, bnl_mid2, bnl_hi2, 2);
-         plane_ranges(idx, bnl_lo3, bnl_mid3, bnl_hi3, 3);
+         for (int w = 1; w <= 3; w++) bnl_cut[w] = plane_ranges(idx, w);
          for (int i = 0; i < 3; i++) if ((rc = dzalloc(&ub[i], Nbl))) return rc;
          if ((rc = dzalloc(&vh1, round_up(Nbl, 64) * PF_MMB))) return rc; // [node / 64][branch][node % 64], pf::st_idx
          if ((rc = dzalloc(&gh1, round_up(Nbl, 64) * PF_MMB))) return rc;
@@ -645,7 +656,7 @@ template <typename Real> struct Engine : EngineBase {
          if ((rc = upload(&d_bna, idx.data(), Nba))) return rc;
          if ((rc = upload(&d_Q, Q.data(), Nba))) return rc;
          if ((rc = dzalloc(&u2ba, Nba))) return rc;
-         plane_ranges(idx, bna_lo, bna_mid, bna_hi);
+         bna_cut = plane_ranges(idx, 1);
       }
       { // sources: rows permuted with the nodes, samples cast to Real once (cpu_engine.h:312 casts per step)
          auto perm = sorted_perm(sd.in_ixyz, Ns, idx);
@@ -654,9 +665,7 @@ template <typename Real> struct Engine : EngineBase {
             for (int64_t n = 0; n < Nt; n++) sig[i * Nt + n] = (Real)sd.in_sigs[perm[i] * Nt + n];
          if ((rc = upload(&d_in, idx.data(), Ns))) return rc;
          if ((rc = upload(&d_insig, sig.data(), Ns * Nt))) return rc;
-         plane_ranges(idx, in_lo, in_mid, in_hi);
-         plane_ranges(idx, in_lo2, in_mid2, in_hi2, 2);
-         plane_ranges(idx, in_lo3, in_mid3, in_hi3, 3);
+         for (int w = 1; w <= 3; w++) in_cut[w] = plane_ranges(idx, w);
       }
       { // receivers
          auto perm = sorted_perm(sd.out_ixyz, Nr, idx);
@@ -847,7 +856,7 @@ template <typename Real> struct Engine : EngineBase {
    }
 
    int run(int64_t n0, int64_t nsteps) override {
-      if (in_step || pair_phase) return set_err(PF_ERR_STATE, "pf_engine_run inside a split-phase step (pair)");
+      if (in_step || in_pass()) return set_err(PF_ERR_STATE, "pf_engine_run inside a split-phase step (pair)");
       HIPCHK(hipSetDevice(op.device));
       for (int64_t n = n0; n < n0 + nsteps;) {
          int rc;
@@ -953,7 +962,7 @@ template <typename Real> struct Engine : EngineBase {
          for (const WlGroup &g : wl_grp) { tm.wall_blocks[0] += g.nblk[0] + g.nblk[2]; tm.wall_blocks[1] += g.nblk[1]; }
       tm.wall_bricks = wl_on ? wl_nbrk : 0;
       tm.fcc_shell_bricks = fb_on ? fb_nbrk : 0;
-      tm.wall_three_steps = (wl_on && (tb3 || (tb3_slab && ws_all3))) ? (int)(wall_g3() | (wl_xw[0] ? 0x10u : 0u) | (wl_xw[1] ? 0x20u : 0u)) : 0;
+      tm.wall_three_steps = (wl_on && (tb3 || (tb3_slab && slab_all3()))) ? (int)(wall_g3() | (wl_xw[0] ? 0x10u : 0u) | (wl_xw[1] ? 0x20u : 0u)) : 0;
       tm.wall_profile = 0; tm.wall_uniform_branches = 0; tm.wall_unread_skipped = 0;
       for (int gi = 0; gi < 4; gi++) if ((tm.wall_three_steps >> gi) & 1) { // what a triple launches for the alike blocks of these groups
          const WallChoice c = wall_choice(gi, 0, 3);
@@ -976,7 +985,7 @@ template <typename Real> struct Engine : EngineBase {
       HIPCHK(hipSetDevice(op.device));
       int rc = sync();
       if (rc) return rc;
-      const Real *src = which == 0 ? (pair_phase > 0 ? (const Real *)u0_src : (const Real *)u0) : u1; // mid-pair u0 already names the grid being written
+      const Real *src = which == 0 ? grids().old : grids().cur; // (inside a slab's pass: of the step next to run)
       if ((lean || vg) && which == 1) { // write the virtual ghost shell out, exactly as the reference's flips would have
          launch_flips(s_main, grids());
          HIPCHK(hipStreamSynchronize(s_main));

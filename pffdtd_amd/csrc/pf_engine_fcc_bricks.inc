@@ -98,15 +98,15 @@
                  cut.tile[3][0], cut.tile[3][1], cut.tile[3][2], cut.tile[4][0], cut.tile[4][1], cut.tile[4][2], cut.tile[5][0], cut.tile[5][1], cut.tile[5][2], (long)cut.nodes_owned, (long)fb_nrest, (long)Nb, (long)fb_ntiles);
       return PF_OK;
    }
-   // the bricks, both steps: A = u^{n-1}, B = u^n -> G0 = u^{n+1}, G1 = u^{n+2}; branch state si -> so (the caller swaps its two copies); node
-   // values x2 = u^{n-1}, x1 = u^n are read, those of the steps go to O0, O1 -- buffers nobody reads during the pass
-   void launch_fcc_bricks(hipStream_t s, const Real *A, const Real *B, Real *G0, Real *G1, const Real *x2, const Real *x1, Real *O0, Real *O1, BranchState si, BranchState so, int ns) {
+   // the bricks, both steps from step `first` of the pass: windows as in launch_walls_x -- the node values of the steps go to buffers nobody reads during the pass
+   void launch_fcc_bricks(hipStream_t s, const Pass &p, int first, int ns) {
       if (!fb_nbrk) return;
       pf::BrickFccParams<Real> bp{};
-      bp.A = A; bp.B = B; bp.G[0] = G0; bp.G[1] = G1; bp.O[0] = O0; bp.O[1] = O1; bp.x2 = x2; bp.x1 = x1;
+      bp.A = p.g[first]; bp.B = p.g[first + 1]; bp.x2 = p.x[first]; bp.x1 = p.x[first + 1];
+      for (int j = 0; j < 2; j++) { bp.G[j] = p.out_g(first, ns, j); bp.O[j] = p.out_x(first, ns, j); }
       bp.plane = plane; bp.Nx = (int)Nx; bp.Ny = (int)Ny; bp.Nz = (int)Nz; bp.P = (int)P;
       bp.brk = fb_brk; bp.info = fb_info; bp.los = fb_los;
-      bp.sv_in = si.v; bp.sg_in = si.g; bp.sv_out = so.v; bp.sg_out = so.g;
+      bp.sv_in = p.in(first).v; bp.sg_in = p.in(first).g; bp.sv_out = p.s1.v; bp.sg_out = p.s1.g;
       bp.ssaf = d_ssaf; bp.mat = d_mat; bp.Mb = d_Mb; bp.mq = d_mq; bp.beta = d_beta;
       bp.lo2 = lo2; bp.sl2 = sl2; bp.l = l; bp.nmat = (int)sd.Nm; bp.ns = ns;
       const dim3 g((unsigned)fb_nbrk), b(pf::BRICK_T);
@@ -135,24 +135,22 @@
    // two: neither the pair kernel nor the box's tiles reach one, the bricks mirror in LDS -- the flips in memory wait for the next single step.
    int step_pair_fcc_bricks(int64_t n) {
       hipStream_t s = s_main;
-      Real *A = u0, *B = u1, *C = bufC, *D = bufD;
-      // node values: X2 = u^{n-1}, X1 = u^n are only read; u^{n+1} -> T1, u^{n+2} -> T2, two buffers nobody reads during the pair
-      Real *X2 = ub[2], *X1 = ub[1], *T1 = ub[0], *T2 = ubx[0];
-      // branch state: the bricks and the first step of the box's nodes read S0 and write S1; the nodes' second step S1 in place
-      const BranchState S0{vh1, gh1}, S1{vh1b, gh1b};
-      const Grids g1{A, B, C}, g2{B, C, D};
+      // node values: u^{n-1}, u^n are only read; u^{n+1}, u^{n+2} go to two buffers nobody reads during the pair
+      // branch state: the bricks and the first step of the box's nodes read s0 and write s1; the nodes' second step s1 in place
+      const Pass p = pass_from_state(bufC, bufD, nullptr, ubx[0], nullptr, state_other());
+      const Grids g1 = p.grids(0), g2 = p.grids(1);
       EvPair ev{}, ev2{}, evt{}, eva{};
       if (op.timing) { ev = ev_get(); ev2 = ev_get(); evt = ev_get(); eva = ev_get(); hipEventRecord(ev.first, s); hipEventRecord(eva.first, s); }
       const bool beside = !(op.debug & PF_DBG_WALLS_ONE_STREAM); // (else everything on the main stream)
       hipStream_t sw = beside ? s_edge : s_main;
       if (beside) { HIPCHK(hipEventRecord(ev_pre, s_main)); HIPCHK(hipStreamWaitEvent(s_edge, ev_pre, 0)); }
       launch_box_tiles_fcc(sw, g1);
-      launch_rigid(sw, g1, Bnd{T1, X2, S0, S1, fb_rest, 0, 0}, {0, fb_nrest});
-      launch_fcc_bricks(sw, A, B, C, D, X2, X1, T1, T2, S0, S1, 2);
+      launch_rigid(sw, g1, p.bnd(0, fb_rest), {0, fb_nrest});
+      launch_fcc_bricks(sw, p, 0, 2);
       // (with per-launch events on, the pair kernel waits for the bricks: its recorded duration is the kernel's own, not the overlap's)
       if (op.timing && beside) { HIPCHK(hipEventRecord(ev_edge, s_edge)); HIPCHK(hipStreamWaitEvent(s, ev_edge, 0)); }
       if (op.timing) hipEventRecord(evt.first, s);
-      launch_tb2(s, n, A, B, C, D);
+      launch_tb2(s, n, p);
       if (op.timing) { hipEventRecord(evt.second, s); tb2_ev.push_back(evt); hipEventRecord(eva.second, s); air_ev.push_back(eva); }
       if (beside && !op.timing) { HIPCHK(hipEventRecord(ev_edge, s_edge)); HIPCHK(hipStreamWaitEvent(s_main, ev_edge, 0)); }
       launch_io(s, g1, n, true, src_range()); // (receivers read u^n; the source goes into u^{n+1}, which only the second step below reads)
@@ -160,13 +158,11 @@
       ring_fill++; steps_done++;
       if (op.timing) { hipEventRecord(ev.second, s); step_ev.push_back(ev); hipEventRecord(ev2.first, s); }
       launch_box_tiles_fcc(s, g2);
-      launch_rigid(s, g2, Bnd{T2, X1, S1, S1, fb_rest, 0, 0}, {0, fb_nrest}); // second step of the box's nodes: u2b = u^n of the node, its u^{n+2} where the bricks put theirs
+      launch_rigid(s, g2, p.bnd(1, fb_rest), {0, fb_nrest}); // second step of the box's nodes: u2b = u^n of the node, its u^{n+2} where the bricks put theirs
       launch_io(s, g2, n + 1, true, src_range());
       ring_fill++; steps_done++;
       // the state after the pair
-      u0 = C; u1 = D; bufC = A; bufD = B;
-      ub[0] = X2; ub[1] = T2; ub[2] = T1; ubx[0] = X1; // (newest in ub[1], the one before in ub[2], ub[0] free: the single steps' convention)
-      vh1 = S1.v; gh1 = S1.g; vh1b = S0.v; gh1b = S0.g;
+      end_pass(p);
       if (op.timing) { hipEventRecord(ev2.second, s); step_ev.push_back(ev2); }
       HIPCHK(hipGetLastError());
       if (ring_fill == ring_depth) return flush();

@@ -8,15 +8,19 @@
       tp.chunk = tb_chunk; tp.nxc = tb_nxc; tp.nyt = tb_nyt; tp.nzt = tb_nzt;
       return tp;
    }
-   // two steps of the clean tiles
-   // three steps of the clean tiles: A = u^{n-1}, B = u^n -> D = u^{n+2}, E = u^{n+3}; C: where flagged tiles leave their u^{n+1} (null: nowhere)
-   void launch_tb3(hipStream_t s, int64_t n, const Real *A, const Real *B, Real *C, Real *D, Real *E, bool sample = false) {
-      if (tb_xr.empty() || tb_nclean <= 0) return;
+   // The blocked kernels take a whole pass (Engine::Pass) and read its grids only: A = g[0] = u^{n-1}, B = g[1] = u^n -> C, D, E = g[2], g[3], g[4].
+   pf::Tb2Params tile_params(const Pass &p, int ns) const {
       pf::Tb2Params tp = tile_params();
-      tp.A = A; tp.B = B; tp.C = C; tp.D = D; tp.E = E;
+      tp.A = p.g[0]; tp.B = p.g[1]; tp.C = p.g[2]; tp.D = p.g[3]; tp.E = ns == 3 ? p.g[4] : nullptr;
+      return tp;
+   }
+   // three steps of the clean tiles: -> D = u^{n+2}, E = u^{n+3}; C: where flagged tiles leave their u^{n+1} (null: nowhere)
+   void launch_tb3(hipStream_t s, int64_t n, const Pass &p, bool sample = false) {
+      if (tb_xr.empty() || tb_nclean <= 0) return;
+      pf::Tb2Params tp = tile_params(p, 3);
       if (!(op.slab_first && op.slab_last)) tp.band |= 2; // a slab: the planes beside the box read the u^{n+1} of its first and last plane
       sample = sample && tb_sample && tb_nsample > 0;
-      const bool forked = !sample && fork_tb3_src<3>(s, n, A, B, C, D, E);
+      const bool forked = !sample && fork_tb3_src<3>(s, n, p);
       tp.tiles = sample ? tb_sample : tb_clean;
       const dim3 g((uint32_t)(sample ? tb_nsample : tb_nclean)), b(64 * tb3_wt);
       if (sg) {
@@ -38,17 +42,16 @@
    //     launches them FIRST, on the wall regions' second stream, where they finish beside the regions (the rank that holds the source of
    //     an 8-rank chain: 0.250 -> 0.245 ms/step, its neighbours 0.241).
    // n: the step the pass starts at.
-   template <int NS> bool fork_tb3_src(hipStream_t s, int64_t n, const Real *A, const Real *B, Real *C, Real *D, Real *E) {
+   template <int NS> bool fork_tb3_src(hipStream_t s, int64_t n, const Pass &p) {
       if (!src_in_kernel() || tb2_probe || !(op.slab_first && op.slab_last) || s == s_edge) return false;
       HIPCHK_V(hipEventRecord(ev_src0, s)); HIPCHK_V(hipStreamWaitEvent(s_edge, ev_src0, 0));
-      launch_tb3_src<NS>(s_edge, n, A, B, C, D, E);
+      launch_tb3_src<NS>(s_edge, n, p);
       HIPCHK_V(hipEventRecord(ev_src1, s_edge));
       return true;
    }
-   template <int NS> void launch_tb3_src(hipStream_t se, int64_t n, const Real *A, const Real *B, Real *C, Real *D, Real *E) {
+   template <int NS> void launch_tb3_src(hipStream_t se, int64_t n, const Pass &p) {
       if (!src_in_kernel() || tb2_probe) return;
-      pf::Tb2Params tp = tile_params();
-      tp.A = A; tp.B = B; tp.C = C; tp.D = D; tp.E = E;
+      pf::Tb2Params tp = tile_params(p, NS);
       if (!(op.slab_first && op.slab_last)) tp.band |= 2;
       tp.tiles = tb_srct;
       tp.src_idx = d_in; tp.src_sig = d_insig; tp.nsrc = (int32_t)Ns; tp.src_Nt = Nt;
@@ -57,17 +60,17 @@
       if (sg) hipLaunchKernelGGL((pf::k_tb3_src<Real, tb3_r, tb3_wt, true, NS>), g, b, 0, se, tp, a1, a2);
       else hipLaunchKernelGGL((pf::k_tb3_src<Real, tb3_r, tb3_wt, false, NS>), g, b, 0, se, tp, a1, a2);
    }
-   // the blocked kernel as the creation-time measurements see it: its four streams (k_tb3: two grids read, two written)
-   void launch_probe(hipStream_t s, int64_t n, const Real *A, const Real *B, Real *C, Real *D, bool sample = false) {
-      if (triples() || tb3_geom) launch_tb3(s, n, A, B, nullptr, C, D, sample);
-      else launch_tb2(s, n, A, B, C, D, sample);
+   // the blocked kernel as the creation-time measurements see it: its four streams, p = of_grids(read, read, written, written) (k_tb3: no u^{n+1} grid)
+   void launch_probe(hipStream_t s, int64_t n, const Pass &p, bool sample = false) {
+      if (triples() || tb3_geom) launch_tb3(s, n, Pass::of_grids(p.g[0], p.g[1], nullptr, p.g[2], p.g[3]), sample);
+      else launch_tb2(s, n, p, sample);
    }
-   void launch_tb2(hipStream_t s, int64_t n, const Real *A, const Real *B, Real *C, Real *D, bool sample = false) {
+   // two steps of the clean tiles
+   void launch_tb2(hipStream_t s, int64_t n, const Pass &p, bool sample = false) {
       if (triples()) { // a pair on the triples' tiles: k_tb3's two-step form (the last two steps of a run, Engine::run)
          if (tb_xr.empty() || tb_nclean <= 0) return;
-         pf::Tb2Params tp = tile_params();
-         tp.A = A; tp.B = B; tp.C = C; tp.D = D; tp.E = nullptr;
-         const bool forked = fork_tb3_src<2>(s, n, A, B, C, D, nullptr);
+         pf::Tb2Params tp = tile_params(p, 2);
+         const bool forked = fork_tb3_src<2>(s, n, p);
          tp.tiles = tb_clean;
          const dim3 g((uint32_t)tb_nclean), b(64 * tb3_wt);
          if (sg) hipLaunchKernelGGL((pf::k_tb3<Real, tb3_r, tb3_wt, true, false, 2>), g, b, 0, s, tp, a1, a2);
@@ -76,8 +79,7 @@
          return;
       }
       if (tb_xr.empty() || tb_nclean <= 0) return;
-      pf::Tb2Params tp = tile_params();
-      tp.A = A; tp.B = B; tp.C = C; tp.D = D;
+      pf::Tb2Params tp = tile_params(p, 2);
       tp.tiles = (tb_ndirty > 0 || tb_order_band) ? tb_clean : nullptr; // all clean: the dense order (identical to the list's)
       sample = sample && tb_sample && tb_nsample > 0;
       if (sample) tp.tiles = tb_sample;

@@ -77,7 +77,7 @@
       HIPCHK(hipStreamSynchronize(s_main));
       tune_ms[1] = timed([&] { launch_flips(s_main, g1); launch_air_march(s_main, g1, 1, (int)Nx - 1); });
       tune_ms[2] = 0.5f * timed([&] {
-         launch_tb2(s_main, 0, g1.old, g1.cur, bufC, bufD);
+         launch_tb2(s_main, 0, Pass::of_grids(u0, u1, bufC, bufD));
          launch_shell(s_main, g1);
          launch_shell(s_main, g2);
       });
@@ -114,8 +114,9 @@
       const float scale = sampled ? (float)(1.0 / tb_sample_frac) : 1.f; // sampled times are reported as whole-launch equivalents
       auto time_fwd = [&](Real *A, Real *B, Real *C, Real *D) -> float {
          hipEventRecord(e0, s_main);
-         launch_probe(s_main, 0, A, B, C, D, true);
-         launch_probe(s_main, 0, A, B, C, D, true);
+         const Pass p = Pass::of_grids(A, B, C, D);
+         launch_probe(s_main, 0, p, true);
+         launch_probe(s_main, 0, p, true);
          hipEventRecord(e1, s_main);
          hipEventSynchronize(e1);
          float ms = 0;
@@ -123,7 +124,7 @@
          return ms / 2 * scale;
       };
       auto grid = [&](int i, Real *fallback) { return i >= 0 ? pool[i] : fallback; };
-      for (int i = 0; i < 4; i++) launch_probe(s_main, 0, grid(first[0], u0), grid(first[1], u1), pool[first[2]], pool[first[3]]); // clocks up
+      for (int i = 0; i < 4; i++) launch_probe(s_main, 0, Pass::of_grids(grid(first[0], u0), grid(first[1], u1), pool[first[2]], pool[first[3]])); // clocks up
       struct Cand { int r[4]; float ms; };
       std::vector<Cand> cands;
       auto eval = [&](const int r[4]) {
@@ -196,7 +197,8 @@
             Real *A = grid(c.r[0], u0), *B = grid(c.r[1], u1), *C = pool[c.r[2]], *D = pool[c.r[3]];
             auto full = [&](Real *a, Real *b, Real *cc, Real *d) {
                hipEventRecord(e0, s_main);
-               launch_probe(s_main, 0, a, b, cc, d); launch_probe(s_main, 0, a, b, cc, d);
+               const Pass p = Pass::of_grids(a, b, cc, d);
+               launch_probe(s_main, 0, p); launch_probe(s_main, 0, p);
                hipEventRecord(e1, s_main); hipEventSynchronize(e1);
                float ms = 0; hipEventElapsedTime(&ms, e0, e1);
                return ms / 2;
@@ -366,7 +368,7 @@
             HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
             auto t4 = [&](Real *A, Real *B, Real *C, Real *D) {
                hipEventRecord(e0, s_main);
-               launch_probe(s_main, 0, A, B, C, D, true);
+               launch_probe(s_main, 0, Pass::of_grids(A, B, C, D), true);
                hipEventRecord(e1, s_main); hipEventSynchronize(e1);
                float ms = 0; hipEventElapsedTime(&ms, e0, e1);
                return ms;
@@ -406,7 +408,7 @@
    // five: idx has five entries and the engine may step in TRIPLES across three split-phase steps (idx[2], idx[3] = the grids k_tb3
    // writes, idx[4] = the u^{n+1} grid; idx[4] = -1: pairs or single steps as pf_engine_place_grids reports them)
    int place_grids_impl(void *const *grids, int n, int32_t *idx, bool five) {
-      if (in_step || pair_phase || steps_done > 0) return set_err(PF_ERR_STATE, "pf_engine_place_grids after the first step");
+      if (in_step || in_pass() || steps_done > 0) return set_err(PF_ERR_STATE, "pf_engine_place_grids after the first step");
       if (state_touched) return set_err(PF_ERR_STATE, "pf_engine_place_grids after pf_engine_set_grid: the placement search runs step kernels on the offered grids and zeroes them");
       if (own_grids) return set_err(PF_ERR_STATE, "pf_engine_place_grids: this engine allocated its own grids");
       if (!grids || !idx || n < 2) return set_err(PF_ERR_ARG, "pf_engine_place_grids: need a pool of at least two grids");
@@ -499,8 +501,7 @@
          return ms / 3;
       };
       const bool lean0 = lean, vg0 = vg;
-      Real *U0 = u0, *U1 = u1;
-      const Grids gs{U0, U1, scr}; // a single step into scratch: the state is not touched
+      const Grids gs{u0, u1, scr}; // a single step into scratch: the state is not touched
       lean = true; vg = false;
       // the device has been idle while the host built the lists: ramp its clocks first (~20 ms of work), or the first
       // candidate is measured -- and every launch here profiled -- at idle clocks (seen: +56 % per launch)
@@ -527,7 +528,9 @@
       if (hipGetLastError() != hipSuccess) { lean = lean0; vg = vg0; }
       else if (tune_ms[1] < 0.97f * tune_ms[0]) { lean = false; vg = true; }
       else if (tune_ms[0] < 0.97f * tune_ms[1]) { lean = true; vg = false; }
-      const Grids g1{U0, U1, bufC}, g2{U1, bufC, bufD}; // the first two steps of a blocked pass
+      // a blocked pass from the state, its node values in the three buffers and the branch state into its other copy, as the wall regions of a slab step
+      const Pass bp = pass_from_state(bufC, bufD, bufE, ub[1], ub[2], state_other());
+      const Grids g1 = bp.grids(0), g2 = bp.grids(1);
       const Bnd bn = bnd(0, 0);                         // (fields, node values and branch state are all zeros at creation and stay so: every boundary launch in place)
       if (tb3) {
          // three steps per pass, the boundary pass included: the single steps get theirs added (fields and branch state are all zeros
@@ -536,10 +539,10 @@
          tune_ms[0] += tb; tune_ms[1] += tb;
          tune_ms[2] = (1.f / 3.f) * timed([&] {
             launch_dirty_tiles(s_main, g1); launch_rigid(s_main, g1, bn.with(wl_rest), {0, wl_nrest});
-            launch_walls(s_main, s_main, U0, U1, bufC, bufD, ub[0], ub[1], ub[2], bn.in, {vh1b, gh1b});
-            launch_tb3(s_main, 0, U0, U1, bufC, bufD, bufE);
+            launch_walls_x(s_main, s_main, bp, 0, 2, 0xf);
+            launch_tb3(s_main, 0, bp);
             launch_dirty_tiles(s_main, g2); launch_rigid(s_main, g2, bn.with(wl_rest), {0, wl_nrest});
-            const Grids g3{bufC, bufD, bufE};
+            const Grids g3 = bp.grids(2);
             launch_shell(s_main, g3); launch_rigid(s_main, g3, bn, {0, Nb});
          });
       } else if (tb2 && wl_on) {
@@ -548,14 +551,14 @@
          const float tb = timed([&] { launch_rigid(s_main, gs, bn, {0, Nb}); });
          tune_ms[0] += tb; tune_ms[1] += tb;
          tune_ms[2] = 0.5f * timed([&] {
-            launch_tb2(s_main, 0, U0, U1, bufC, bufD);
+            launch_tb2(s_main, 0, bp);
             launch_dirty_tiles(s_main, g1); launch_rigid(s_main, g1, bn.with(wl_rest), {0, wl_nrest});
-            launch_walls(s_main, s_main, U0, U1, bufC, bufD, ub[0], ub[1], ub[2], bn.in, {vh1b, gh1b});
+            launch_walls_x(s_main, s_main, bp, 0, 2, 0xf);
             launch_dirty_tiles(s_main, g2); launch_rigid(s_main, g2, bn.with(wl_rest), {0, wl_nrest});
          });
       } else if (tb2) {
          tune_ms[2] = 0.5f * timed([&] {
-            launch_tb2(s_main, 0, U0, U1, bufC, bufD);
+            launch_tb2(s_main, 0, bp);
             launch_shell(s_main, g1);
             launch_shell(s_main, g2);
          });

@@ -1,5 +1,5 @@
 // pf_engine_walls.inc -- part of `template <typename Real> struct Engine` (pf_engine.hip includes it INSIDE the class body; not a translation unit):
-// wall regions: tables (Engine::init_walls) and launches (Engine::launch_walls) of k_wall2, pf_wall.h.
+// wall regions: tables (Engine::init_walls) and launches (Engine::launch_walls_x) of k_wall2, pf_wall.h.
    // ---------------- wall regions: the shell of a blocked pair in pairs (pf_wall.h) ----------------
    // Six regions around the box: two whole-plane slabs normal to x, two row strips normal to y (the box's planes), two
    // column strips normal to z (the box's planes and rows) -- every interior cell outside the box belongs to exactly one.
@@ -316,7 +316,7 @@
             if (kk >= reg[i].ko0 && kk < reg[i].ko1 && ll >= reg[i].l0 && ll < reg[i].l1 && mm >= reg[i].m0 && mm < reg[i].m1) { r = i; k = kk; lc = ll; m = mm; break; }
          }
          owner[nb] = (int8_t)r;
-         const Range &midr = tb3_geom ? bn_mid3 : bn_mid2;
+         const Range &midr = bn_cut[tb3_geom ? 3 : 2].mid;
          if (r == 8 && bricks && in_frame(ix, iy, iz)) r = 9; // a brick's
          owner[nb] = (int8_t)r;
          if (r == 8 && (!slab || (nb >= midr.b && nb < midr.e))) rest.push_back((int32_t)nb); // (a slab's edge planes: range launches)
@@ -528,23 +528,19 @@
                  tbx0, tbx1, tby0, tby1, tbz0, tbz1, (long)npen, (long)nrec, (long)wl_nrest, (long)Nb, dps.back(), zb, (long)nfast, (long)ngen, (long)wl_nbrk, blen, (long)hinfo.size(), (long)wl_nbown_dbg, wl_brk_lds);
       return PF_OK;
    }
-   // both steps of the wall regions: A = u^{n-1}, B = u^n -> C = u^{n+1}, D = u^{n+2}; branch state si -> so;
-   // node values: P2 = u^{n-1} and P1 = u^n are read, P0 <- u^{n+1}, P1 <- u^{n+2}
-   // (s_gen: the stream of the generic blocks -- edges, corners: few waves, each a long chain of dependent steps)
-   void launch_walls(hipStream_t s, hipStream_t s_gen, const Real *A, const Real *B, Real *C, Real *D, Real *P0, Real *P1, const Real *P2, BranchState si, BranchState so) {
-      launch_walls_x(s, s_gen, A, B, C, D, nullptr, P2, P1, P0, P1, nullptr, si, so, 2, 0xf); // (three node-value buffers: u^{n+2} of a node overwrites its u^n)
-   }
-   // the general form: node values x2 = u^{n-1}, x1 = u^n are read, o1 / o2 / o3 receive u^{n+1} / u^{n+2} / u^{n+3}; gmask: which launch groups
-   // (bit 0: the x / y regions, bits 1-3: the column strips); ns = 3: three steps in one pass (x / y regions with three-step tables: wl_ns3);
-   // ns = 1: ONE step, A, B -> C (the third step of a triple), x2 -> o1.  Branch state si -> so (ns = 1: one and the same; else the caller swaps its two copies)
-   void launch_walls_x(hipStream_t s, hipStream_t s_gen, const Real *A, const Real *B, Real *C, Real *D, Real *E, const Real *x2, const Real *x1, Real *o1, Real *o2, Real *o3,
-                       BranchState si, BranchState so, int ns, unsigned gmask) {
+   // The wall regions (k_wall2): `ns` steps in one launch that starts at step `first` of the pass.  Grids: g[first], g[first + 1] are read, the ns after them
+   // written (ns = 3: three steps in one pass, x / y regions with three-step tables: wl_ns3; ns = 1: ONE step, the third of a triple: first = 2);
+   // node values: x[first], x[first + 1] are read, the ns after them receive the steps' (three node-value buffers: u^{n+2} of a node overwrites
+   // its u^n); branch state: the pass's first step reads s0, every launch writes s1.  gmask: which launch groups (bit 0: the x / y regions,
+   // bits 1-3: the column strips); s_gen: the stream of the generic blocks -- edges, corners: few waves, each a long chain of dependent steps
+   void launch_walls_x(hipStream_t s, hipStream_t s_gen, const Pass &p, int first, int ns, unsigned gmask) {
       pf::WallParams<Real> wp{};
-      wp.A = A; wp.B = B; wp.C = C; wp.D = D; wp.E = E;
+      Real *const C = p.out_g(first, ns, 0);
+      wp.A = p.g[first]; wp.B = p.g[first + 1]; wp.C = C; wp.D = p.out_g(first, ns, 1); wp.E = p.out_g(first, ns, 2);
       wp.plane = plane; wp.Nx = (int)Nx; wp.Ny = (int)Ny; wp.Nz = (int)Nz; wp.P = (int)P; wp.first = op.slab_first; wp.last = op.slab_last;
       wp.pen = wl_pen; wp.rec = wl_rec;
-      wp.sv_in = si.v; wp.sg_in = si.g; wp.sv_out = so.v; wp.sg_out = so.g;
-      wp.x2 = x2; wp.x1 = x1; wp.o1 = o1; wp.o2 = o2; wp.o3 = o3;
+      wp.sv_in = p.in(first).v; wp.sg_in = p.in(first).g; wp.sv_out = p.s1.v; wp.sg_out = p.s1.g;
+      wp.x2 = p.x[first]; wp.x1 = p.x[first + 1]; wp.o1 = p.out_x(first, ns, 0); wp.o2 = p.out_x(first, ns, 1); wp.o3 = p.out_x(first, ns, 2);
       wp.ssaf = d_ssaf; wp.mat = d_mat; wp.Mb = d_Mb; wp.mq = d_mq; wp.beta = d_beta;
       wp.lo2 = lo2; wp.sl2 = sl2; wp.l = l; wp.mmax = mb_max; wp.nmat = sd.Nm;
       for (int gi = 0; gi < 4; gi++) {
@@ -562,17 +558,17 @@
          }
       }
    }
-   // the frame's bricks (pf_brick.h): `ns` steps in one launch, A = u^{n-1}, B = u^n -> G0 = u^{n+1}, G1 = u^{n+2} (, G2 = u^{n+3}); branch state
-   // si -> so (the caller swaps its two copies, as for the wall regions); node values x2 = u^{n-1}, x1 = u^n are read, those of the steps go
-   // to O0, O1 (, O2) -- buffers nobody reads during the pass.
-   void launch_bricks(hipStream_t s, const Real *A, const Real *B, Real *G0, Real *G1, Real *G2, const Real *x2, const Real *x1, Real *O0, Real *O1, Real *O2, BranchState si, BranchState so, int ns) {
+   // the frame's bricks (pf_brick.h): `ns` steps in one launch from step `first` of the pass, windows as in launch_walls_x -- the node values of the steps go
+   // to buffers nobody reads during the pass
+   void launch_bricks(hipStream_t s, const Pass &p, int first, int ns) {
       if (!wl_nbrk) return;
       pf::BrickParams<Real> bp{};
-      bp.x2 = x2; bp.x1 = x1;
-      bp.A = A; bp.B = B; bp.G[0] = G0; bp.G[1] = G1; bp.G[2] = G2; bp.O[0] = O0; bp.O[1] = O1; bp.O[2] = O2;
+      bp.x2 = p.x[first]; bp.x1 = p.x[first + 1];
+      bp.A = p.g[first]; bp.B = p.g[first + 1];
+      for (int j = 0; j < 3; j++) { bp.G[j] = p.out_g(first, ns, j); bp.O[j] = p.out_x(first, ns, j); }
       bp.plane = plane; bp.Nx = (int)Nx; bp.Ny = (int)Ny; bp.Nz = (int)Nz; bp.P = (int)P;
       bp.brk = wl_brk; bp.info = wl_binfo; bp.los = wl_blos;
-      bp.sv_in = si.v; bp.sg_in = si.g; bp.sv_out = so.v; bp.sg_out = so.g;
+      bp.sv_in = p.in(first).v; bp.sg_in = p.in(first).g; bp.sv_out = p.s1.v; bp.sg_out = p.s1.g;
       bp.ssaf = d_ssaf; bp.mat = d_mat; bp.Mb = d_Mb; bp.mq = d_mq; bp.beta = d_beta;
       bp.lo2 = lo2; bp.sl2 = sl2; bp.l = l; bp.nmat = (int)sd.Nm; bp.ns = ns;
       bp.first = op.slab_first; bp.last = op.slab_last;

@@ -417,6 +417,49 @@ def test_slabs_step_in_triples_across_three_split_phase_steps(prec, transport):
         assert np.array_equal(sd2.u_out, want), (devs, flags, hex(dbg))
 
 
+# ---- passes that start and stop at ring boundaries ---------------------------------------------------------------------------
+@pytest.mark.parametrize("devs,flags,dbg,spp", [([0, 0, 0], 0, 0, 3), ([0, 0, 0], 0, 0x80, 3), ([0, 0], engine.PF_MULTI_NO_TRIPLES, 0, 2),
+                                                ([0, 0, 0], engine.PF_MULTI_NO_TRIPLES, 0x10000000, 2)],
+                         ids=["triples", "triples_edges_separate", "pairs_wall_regions", "pairs_no_wall_regions"])
+def test_passes_start_and_stop_at_ring_boundaries(devs, flags, dbg, spp):
+    """A readout ring of seven steps: a triple fits at fill 0 and 3 and one single step ends the ring, a pair fits three times and one
+    single step -- so a chain of 41 steps run as 20 + 21 crosses every hand-over between the state a pass leaves and the single steps'
+    rotation (grids, node-value buffers, the two copies of the branch state) many times.  Triples with the edge planes fused and by
+    separate launches (debug 0x80), pairs with wall regions, pairs without (debug 0x10000000: the node buffers rotate in place): the
+    oracle's bits, every exchange checked, and the passes really are what steps."""
+    want = _ring_reference()
+    sd = sim_data.SimData.from_sim(synth.shoebox(**_RING_SCENE), "single")
+    sd.scale_input()
+    m = engine.HipMulti(sd, devs, multi_flags=engine.PF_MULTI_FORCE_PAIRS | flags, air_variant=40, verify_exchange=int(sd.Nt), readout_chunk=7, timing=1, debug=dbg)
+    m.run(0, 20)
+    m.run(20, 21)
+    info = m.info()
+    tms = [m.slab(g)["engine"].timing() for g in range(len(devs))]
+    m.close()
+    assert info["exchange_verified"] is True
+    assert all(t["tb_steps_per_pass"] == spp and t["tb2_launches"] > 0 for t in tms), [(t["tb_steps_per_pass"], t["tb2_launches"]) for t in tms]
+    assert all((sum(t["wall_blocks"]) > 0) == (dbg != 0x10000000) for t in tms), [t["wall_blocks"] for t in tms]
+    assert np.array_equal(sd.u_out, want), (devs, flags, hex(dbg))
+
+
+# (the scene of test_slabs_step_in_triples_across_three_split_phase_steps, fp32: the smallest known to engage triples on two and on three slabs)
+_RING_SCENE = dict(Nx=124, Ny=70, Nz=276, Nt=41, wall=3, Nm=2, Mb=[11, 3], src=[61, 30, 100],
+                   rcv=[[30, 25, 96], [70, 36, 110], [61, 4, 104], [62, 63, 101], [63, 30, 4], [60, 31, 269], [41, 4, 4], [82, 63, 269], [4, 30, 100], [117, 40, 120], [4, 4, 4],
+                        [118, 64, 269], [118, 20, 50], [5, 33, 90]])
+_ring_ref = []
+
+
+def _ring_reference():
+    """The oracle's receiver signals of _RING_SCENE, computed once for all the cases."""
+    if not _ring_ref:
+        sd = sim_data.SimData.from_sim(synth.shoebox(**_RING_SCENE), "single")
+        sd.scale_input()
+        oracle.run_sim(sd)
+        assert np.abs(sd.u_out).max() > 0 and np.abs(sd.u_out[2:]).max() > 0
+        _ring_ref.append(sd.u_out.copy())
+    return _ring_ref[0]
+
+
 # ---- round 5: the wall planes' weights of the balanced cut are measured when the chain is created ---------------------------
 def test_partition_weights_are_measured_at_creation_and_change_no_bits():
     """PF_MULTI_MEASURE_WEIGHTS: pf_multi_create on a scene with at least 2^24 cells per slab and an interior rank (three slabs or more) times three one-rank cost models (an interior

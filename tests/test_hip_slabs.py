@@ -281,3 +281,90 @@ def _run_blocked_pairs(G, Nt, src, prec):
         s.close()
     assert np.abs(ref.u_out).max() > 0
     assert np.array_equal(out, ref.u_out), f"max|d|={np.abs(out - ref.u_out).max()}"
+
+
+# ---- the field between the phases of a slab's pass ---------------------------------------------------------------------------
+def _exchange(st):
+    """the ghost planes of a chain of virtual slabs, stream-ordered behind the edge streams"""
+    planes = [s.halo_tensors() for s in st]
+    evs = []
+    for s in st:
+        e = torch.cuda.Event()
+        e.record(s.edge_stream)
+        evs.append(e)
+    for r in range(len(st) - 1):
+        with torch.cuda.stream(st[r + 1].edge_stream):
+            st[r + 1].edge_stream.wait_event(evs[r])
+            planes[r + 1][2].copy_(planes[r][1], non_blocking=True)
+        with torch.cuda.stream(st[r].edge_stream):
+            st[r].edge_stream.wait_event(evs[r + 1])
+            planes[r][3].copy_(planes[r + 1][0], non_blocking=True)
+
+
+@pytest.mark.parametrize("spares,spp", [(6, 3), (2, 2)], ids=["triples", "pairs"])
+def test_the_field_between_the_phases_of_a_pass(spares, spp):
+    """A slab's pass spans two or three split-phase steps.  Stepped beside the oracle, 18 steps (six triples / nine pairs: the role cycle of
+    the grids more than once): after the step that closes the FIRST phase of a pass pf_engine_get_grid(0) is u^n of the slab's owned cells
+    and pf_engine_state_grids is refused; after the step that closes the pass both state grids are the oracle's, pf_engine_state_grids
+    is accepted and names the grids pf_engine_get_grid reads.  (Owned cells without the ghost shell, whose memory copy is virtual with the
+    fused kernels; the u^{n+1} grid in the middle of a triple is not compared: k_tb3 never stores it inside the box.)"""
+    from pffdtd_amd import engine, sim_data, synth
+    nz = 276
+    kw = dict(Nx=124, Ny=70, Nz=nz, Nt=41, wall=3, Nm=2, Mb=[11, 3], src=[61, 30, 100],
+              rcv=[[30, 25, 96], [70, 36, 110], [61, 4, 104], [62, 63, 101], [63, 30, 4], [60, 31, nz - 7], [41, 4, 4], [82, 63, nz - 7], [4, 30, 100], [117, 40, 120], [4, 4, 4], [118, 64, nz - 7], [118, 20, 50], [5, 33, 90]])
+    ref = sim_data.SimData.from_sim(synth.shoebox(**kw), "single")
+    ref.scale_input()
+    orc = oracle.Engine(ref)
+    sd = sim_data.SimData.from_sim(synth.shoebox(**kw), "single", build_mask=False)
+    sd.scale_input()
+    G, K = 2, 18
+    parts = [slab.split(sd, G, r) for r in range(G)]
+    if spares == 6:  # (what HipSlabStepper offers by itself)
+        st = [pdist.HipSlabStepper(loc, info, 0, pairs=True, air_variant=40, timing=True) for loc, info in parts]
+    else:
+        st = [pdist.HipSlabStepper(loc, info, 0, pairs=False, air_variant=40, timing=True) for loc, info in parts]
+        for s in st:  # two spare grids: pairs at most
+            with torch.cuda.device(s.device):
+                pool = list(s.grids) + [torch.zeros_like(s.grids[0]) for _ in range(spares)]
+                torch.cuda.synchronize()
+            two, idx = s.eng.place_grids([g.data_ptr() for g in pool])
+            s.steps_per_pass = 2 if two else 0
+            s.grids = [pool[i] for i in idx if i >= 0]
+            s._by_ptr = {g.data_ptr(): g for g in s.grids}
+    assert [s.steps_per_pass for s in st] == [spp] * G
+    P = engine.grid_pitch(sd.Nz, 4)
+
+    def check(s, which, why):
+        got = s.eng.get_grid(which)[1:-1, 1:-1, 1:-1]
+        want = orc.grid(which)[s.info.xlo + 1:s.info.xhi - 1, 1:-1, 1:-1]
+        assert np.array_equal(got, want), (why, s.info.rank, which, float(np.abs(got - want).max()))
+        return got
+
+    seen = 0.0
+    for n in range(K):
+        for s in st:
+            s.step_begin(n)
+        _exchange(st)
+        for s in st:
+            s.step_end(n)
+        orc.step(n)
+        for s in st:
+            if n % spp == 0:  # the first phase of a pass is closed, the pass is not
+                check(s, 0, f"after phase 0, step {n}")
+                with pytest.raises(engine.PfError, match="inside a step"):
+                    s.eng.state_grids()
+            elif n % spp == spp - 1:  # the pass is closed
+                ptrs = s.eng.state_grids()
+                assert ptrs[0] != ptrs[1] and all(p in s._by_ptr for p in ptrs)
+                for which in (0, 1):
+                    got = check(s, which, f"after the pass, step {n}")
+                    s.eng.sync()
+                    mem = s._by_ptr[ptrs[which]].cpu().numpy().reshape(s.loc.Nx, s.loc.Ny, P)[1:-1, 1:-1, 1:sd.Nz - 1]
+                    assert np.array_equal(mem, got), (n, s.info.rank, which)
+                    seen = max(seen, float(np.abs(got).max()))
+    assert seen > 0
+    tms = [s.eng.timing() for s in st]
+    for s in st:
+        s.finish()
+        s.close()
+    assert all(t["tb_steps_per_pass"] == spp and t["tb2_launches"] > 0 for t in tms), [(t["tb_steps_per_pass"], t["tb2_launches"]) for t in tms]
