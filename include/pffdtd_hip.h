@@ -315,6 +315,37 @@ int  pf_engine_flush_outputs(pf_engine *e);          /* ring -> sd->u_out */
  * or NaN -- the internal switch PF_DBG_BND_FETCH_ALL (csrc/pf_debug.h) fetches every neighbour, the exact reference behaviour for such fields too. */
 int  pf_engine_get_grid(pf_engine *e, int32_t which, void *host);
 int  pf_engine_set_grid(pf_engine *e, int32_t which, const void *host);
+/* ---- checkpoint and resume: the whole state between two steps n-1 | n, in its canonical form ----
+ * Exactly what the reference's run_sim carries across its loop, in the FILE's terms -- independent of how an engine stores it (kernel family,
+ * storage layout, one domain or a chain of slabs): a state saved by one of them loads into any other of the same scene and precision and
+ * continues bit for bit.  No counterpart in the reference (its run_steps is re-entrant in memory only).
+ *   - The step index is the caller's: after a load it continues with pf_engine_run(e, n, ...) / pf_multi_run(m, n, ...).  Receiver rows of the
+ *     steps < n are the caller's as well (sd->u_out); both calls flush the receiver ring into sd->u_out first.
+ *   - Valid between runs only: PF_ERR_STATE inside a split-phase step or pass (between pf_engine_step_begin and the pf_engine_step_end that ends
+ *     a slab's pair or triple), and for an engine created with pf_opts.energy (its sums live with the caller).  PF_ERR_ARG for a null pointer;
+ *     with Nbl == 0 the four node arrays may be NULL.
+ *   - A load is allowed at any time between runs, also into an engine that has stepped already (a rewind).  Afterwards nothing of what went
+ *     before is read again: the engine behaves as a new engine that holds this state.
+ *   - Branch slots m >= Mb[mat] are written as 0 by a save and ignored by a load.
+ *   - A save materialises the ghost cells of u_cur as pf_engine_get_grid(1) does.  A load into a whole domain does not depend on the ghost cells
+ *     or the folded row of either field (the engines re-derive them every step); the edge planes of an interior slab of a chain are real data,
+ *     which pf_multi_load_state fills from the global arrays.
+ *   - u1b / u2b are the node values the reference carries from step to step (cpu_engine.h:322-325), saved and restored as they are, not
+ *     gathered from the fields: in the first two steps after pf_engine_set_grid they differ from them (the reference starts them at zero).
+ *   - Device memory: the fields move through a staging buffer of a fixed number of planes where the engine stores the axes exchanged, and by
+ *     pitched copies otherwise -- never through a second grid; the node arrays through a device copy of their own size for the call's duration. */
+typedef struct pf_state {      /* all HOST pointers, caller-owned; Real = float | double by pf_simdata.real_bytes */
+   void *u_prev, *u_cur;       /* [Npts]  u^{n-1}, u^n in FILE order (ix*Ny*Nz + iy*Nz + iz), as pf_engine_get_grid(0 / 1) */
+   void *u1b, *u2b;            /* [Nbl]   node values of the last two steps, in the order of sd->bnl_ixyz (cpu_engine.h:322-325) */
+   void *vh1, *gh1;            /* [Nbl * PF_MMB]  branch state, [nb * PF_MMB + m] as cpu_engine.h:363-402 */
+} pf_state;
+int  pf_engine_save_state(pf_engine *e, pf_state *st);
+int  pf_engine_load_state(pf_engine *e, const pf_state *st);
+/* The same for a chain: the global arrays of the WHOLE scene (the sd given to pf_multi_create).  Every slab saves / loads its part on its own
+ * device and host thread; a load leaves the chain ready for pf_multi_run(m, n, ...), and the exchange self-check (pf_opts.verify_exchange)
+ * covers the first exchanges after it again.  PF_ERR_STATE for a one-rank cost model (pf_opts.only_slab). */
+int  pf_multi_save_state(pf_multi *m, pf_state *st);
+int  pf_multi_load_state(pf_multi *m, const pf_state *st);
 int  pf_engine_timing(pf_engine *e, pf_timing *t, int32_t reset);
 /* switch the per-launch HIP events of pf_opts.timing on / off between runs (a host times its headline region without them
  * and collects kernel durations in a region of its own) */

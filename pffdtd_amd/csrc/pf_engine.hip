@@ -154,6 +154,8 @@ int pf_engine_sync(pf_engine *e) { PF_NEED(e); return e->impl->sync(); }
 int pf_engine_flush_outputs(pf_engine *e) { PF_NEED(e); return e->impl->flush(); }
 int pf_engine_get_grid(pf_engine *e, int32_t which, void *host) { PF_NEED(e); return e->impl->get_grid(which, host); }
 int pf_engine_set_grid(pf_engine *e, int32_t which, const void *host) { PF_NEED(e); return e->impl->set_grid(which, host); }
+int pf_engine_save_state(pf_engine *e, pf_state *st) { PF_NEED(e); return e->impl->save_state(st); }
+int pf_engine_load_state(pf_engine *e, const pf_state *st) { PF_NEED(e); return e->impl->load_state(st); }
 int pf_engine_timing(pf_engine *e, pf_timing *t, int32_t reset) { PF_NEED(e); return e->impl->timing(t, reset); }
 int pf_engine_set_timing(pf_engine *e, int32_t on) { PF_NEED(e); return e->impl->set_timing(on); }
 int pf_engine_energy_cfg(pf_engine *e, double h, double c, double Ts, const double *DEF) { PF_NEED(e); if (!DEF) return set_err(PF_ERR_ARG, "null DEF"); return e->impl->energy_cfg(h, c, Ts, DEF); }

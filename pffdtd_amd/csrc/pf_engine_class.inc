@@ -24,6 +24,7 @@
 #include "pf_wall.h"
 #include "pf_brick.h"
 #include "pf_brick_fcc.h"
+#include "pf_state.h"
 
 // shared between the two units (defined in pf_engine.hip)
 extern "C" void pf__set_error(const char *msg);
@@ -48,6 +49,8 @@ struct EngineBase {
    virtual int place_grids5(void *const *grids, int n, int32_t *idx) = 0;
    virtual int get_grid(int which, void *host) = 0;
    virtual int set_grid(int which, const void *host) = 0;
+   virtual int save_state(pf_state *st) = 0;
+   virtual int load_state(const pf_state *st) = 0;
    virtual int timing(pf_timing *t, int reset) = 0;
    virtual int set_timing(int on) = 0;
    virtual void *stream(int which) = 0;
@@ -153,6 +156,7 @@ template <typename Real> struct Engine : EngineBase {
    int lean_nzt = 0;
    int64_t *d_bn = nullptr, *d_bnl = nullptr, *d_bna = nullptr, *d_in = nullptr, *d_out = nullptr;
    uint16_t *d_adj = nullptr;
+   int64_t *d_lperm = nullptr;   // per lossy node, in the engine's sorted order: its row in sd.bnl_ixyz (pf_state.h: the canonical state goes by those rows)
    int32_t *d_lossy = nullptr;   // per boundary node: index into the lossy-node arrays or -1 (fused boundary pass)
    bool fuse_boundary = false;
    int8_t *d_Q = nullptr, *d_mat = nullptr, *d_Mb = nullptr;
@@ -343,7 +347,7 @@ template <typename Real> struct Engine : EngineBase {
       for (Real *g : own_list) F(g); // state grids this engine allocated (u0/u1 unless external, the temporal-blocking spares)
       own_list.clear();
       free_fcc_bricks();
-      F(wl_pen); F(wl_rec); F(wl_rest); F(wl_blk); F(wl_brk); F(wl_binfo); F(wl_blos); F(ubx[0]); F(ubx[1]); F(edge_sel3); F(vh1b); F(gh1b); F(d_lossy); F(mask); F(zs_map); F(zs_adj); F(zs_li); F(zs_rest); F(zs_fd); F(tb_clean); F(tb_dirty); F(tb_srct); F(tb_sample); F(sh_tiles); F(Lu); F(vh_old); F(u2in); F(d_acc); F(d_DEF); F(d_bn); F(d_bnl); F(d_bna); F(d_in); F(d_out); F(d_adj); F(d_Q); F(d_mat); F(d_Mb); F(d_ssaf);
+      F(wl_pen); F(wl_rec); F(wl_rest); F(wl_blk); F(wl_brk); F(wl_binfo); F(wl_blos); F(ubx[0]); F(ubx[1]); F(edge_sel3); F(vh1b); F(gh1b); F(d_lossy); F(d_lperm); F(mask); F(zs_map); F(zs_adj); F(zs_li); F(zs_rest); F(zs_fd); F(tb_clean); F(tb_dirty); F(tb_srct); F(tb_sample); F(sh_tiles); F(Lu); F(vh_old); F(u2in); F(d_acc); F(d_DEF); F(d_bn); F(d_bnl); F(d_bna); F(d_in); F(d_out); F(d_adj); F(d_Q); F(d_mat); F(d_Mb); F(d_ssaf);
       F(d_beta); F(d_insig); F(d_mq); F(ub[0]); F(ub[1]); F(ub[2]); F(u2ba); F(vh1); F(gh1); F(ring);
       if (h_ring) hipHostFree(h_ring);
       for (auto &p : air_ev) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
@@ -620,6 +624,7 @@ template <typename Real> struct Engine : EngineBase {
             if (mat[i] < 0 || mat[i] >= sd.Nm) return set_err(PF_ERR_ARG, "mat_bnl[%ld]=%d out of range", (long)perm[i], mat[i]);
          }
          if ((rc = upload(&d_bnl, idx.data(), Nbl))) return rc;
+         if ((rc = upload(&d_lperm, perm.data(), Nbl))) return rc;
          if ((rc = upload(&d_ssaf, ssaf.data(), Nbl))) return rc;
          if ((rc = upload(&d_mat, mat.data(), Nbl))) return rc;
          for (int w = 1; w <= 3; w++) bnl_cut[w] = plane_ranges(idx, w);
@@ -1022,6 +1027,7 @@ template <typename Real> struct Engine : EngineBase {
       HIPCHK(hipMemcpy2D(dst, P * sizeof(Real), host, Nz * sizeof(Real), Nz * sizeof(Real), Nx * Ny, hipMemcpyHostToDevice));
       return PF_OK;
    }
+#include "pf_engine_state.inc"
    void *stream(int which) override { return which == 1 ? (void *)s_edge : (void *)s_main; }
 };
 

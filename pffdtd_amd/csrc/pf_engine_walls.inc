@@ -411,6 +411,9 @@
          HIPCHK(hipMemcpy(d_bnl, bl2.data(), Nbl * sizeof(int64_t), hipMemcpyHostToDevice));
          HIPCHK(hipMemcpy(d_ssaf, sf2.data(), Nbl * sizeof(Real), hipMemcpyHostToDevice));
          HIPCHK(hipMemcpy(d_mat, mt2.data(), Nbl * sizeof(int8_t), hipMemcpyHostToDevice));
+         HIPCHK(hipMemcpy(bl.data(), d_lperm, Nbl * sizeof(int64_t), hipMemcpyDeviceToHost)); // (each node's row in sd.bnl_ixyz moves with it: pf_engine_state.inc)
+         for (int64_t j = 0; j < Nbl; j++) bl2[newli[j]] = bl[j];
+         HIPCHK(hipMemcpy(d_lperm, bl2.data(), Nbl * sizeof(int64_t), hipMemcpyHostToDevice));
          for (int64_t nb = 0; nb < Nb; nb++) if (hl[nb] >= 0) hl[nb] = newli[hl[nb]];
          HIPCHK(hipMemcpy(d_lossy, hl.data(), Nb * sizeof(int32_t), hipMemcpyHostToDevice));
       }

@@ -51,6 +51,7 @@
 #include "pffdtd_hip.h"
 #include "pf_debug.h" // pf_opts_x: the public options + the development / test switches
 #include "pf_slab_cut.h" // Slab, partition, cut_slab: the cut itself, host code that needs no device
+#include "pf_state_cut.h" // scatter_state, gather_state: the canonical state cut to the slabs and put together again
 
 extern "C" void pf__set_error(const char *msg); // pf_engine.hip (feeds pf_last_error)
 extern "C" int pf__axis_exchange_pays(const pf_simdata *sd, int64_t *counts); // pf_engine.hip
@@ -571,6 +572,22 @@ void phase_end(Shared &S, int g, int64_t n) {
    S.steps_done[g]++;
 }
 
+// checkpoint: slab g's part of the scene's canonical state, saved from / loaded into its engine on its own device (pf_state_cut.h says which part)
+void state_slab(Shared &S, int g, const pf_simdata *sd, pf_state *st, bool load) {
+   if (S.err.load() || !S.eng[g]) return;
+   MCHK(g, hipSetDevice(S.dev[g]));
+   pf_cut::LocalState l;
+   try { pf_cut::alloc_state(S.slabs[g], l); } catch (const std::bad_alloc &) { S.set_error(PF_ERR_ARG, "no host memory for a slab's part of the state"); return; }
+   if (load) {
+      pf_cut::scatter_state(sd, st, S.slabs[g], S.along_z, l);
+      ECHK(g, pf_engine_load_state(S.eng[g], &l.st));
+      S.steps_done[g] = 0; // the exchange self-check covers the first exchanges after a load again
+   } else {
+      ECHK(g, pf_engine_save_state(S.eng[g], &l.st));
+      pf_cut::gather_state(sd, l, S.slabs[g], S.along_z, st); // (the slabs' owned planes and node rows are disjoint: no two threads write one byte)
+   }
+}
+
 void finish_slab(Shared &S, int g) {
    if (!S.eng[g]) return;
    hipSetDevice(S.dev[g]);
@@ -654,7 +671,8 @@ struct pf_multi {
    std::mutex mu;
    std::condition_variable cv_cmd, cv_done;
    int64_t cmd_seq = 0, cmd_n0 = 0, cmd_ns = 0;
-   int cmd_kind = 0;                 // 1 run, 2 quit
+   int cmd_kind = 0;                 // 1 run, 2 quit, 3 save the state, 4 load it
+   pf_state *cmd_state = nullptr;    // ... from / into these global arrays
    int done = 0;
    bool created = false;
    double last_seconds = 0;
@@ -682,7 +700,8 @@ void worker(pf_multi *m, int g) {
          seen = m->cmd_seq; kind = m->cmd_kind; n0 = m->cmd_n0; ns = m->cmd_ns;
       }
       if (kind == 2) break;
-      run_slabs(S, g, g + 1, local, n0, ns);
+      if (kind == 3 || kind == 4) state_slab(S, g, m->sd, m->cmd_state, kind == 4);
+      else run_slabs(S, g, g + 1, local, n0, ns);
       S.bar.wait(local, S.err, S.bar_timeout);
       { std::lock_guard<std::mutex> lk(m->mu); m->done++; }
       m->cv_done.notify_all();
@@ -710,14 +729,14 @@ void wait_done(pf_multi *m) {
    }
 }
 
-void scatter_outputs(pf_multi *m) { // receivers: every slab filled its own rows (gpu_engine.h:1066-1075)
+void scatter_outputs(pf_multi *m, int64_t n0, int64_t ns) { // receivers: every slab filled its own rows (gpu_engine.h:1066-1075), the steps of this run (the rows before them are the caller's: a resumed run)
    Shared &S = m->S;
    pf_simdata *sd = m->sd;
    if (!sd->u_out) return;
    for (int g = 0; g < S.G; g++) {
       const Slab &sl = S.slabs[g];
       for (size_t r = 0; r < sl.out_rows.size(); r++)
-         memcpy(sd->u_out + sl.out_rows[r] * sd->Nt, sl.u_out.data() + r * (size_t)sd->Nt, sizeof(double) * (size_t)sd->Nt);
+         memcpy(sd->u_out + sl.out_rows[r] * sd->Nt + n0, sl.u_out.data() + r * (size_t)sd->Nt + n0, sizeof(double) * (size_t)ns);
    }
 }
 
@@ -942,9 +961,37 @@ int pf_multi_run(pf_multi *m, int64_t n0, int64_t nsteps) {
    }
    m->last_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
    if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   scatter_outputs(m);
+   scatter_outputs(m, n0, nsteps);
    return PF_OK;
 }
+
+static int multi_state(pf_multi *m, pf_state *st, bool load, const char *what) {
+   if (!m) return fail("%s: null object", what);
+   if (!st) return fail("%s: null pf_state", what);
+   Shared &S = m->S;
+   if (S.G == 1) return load ? pf_engine_load_state(S.eng[0], st) : pf_engine_save_state(S.eng[0], st);
+   if (S.only >= 0) { fail("%s: a one-rank cost model (pf_opts.only_slab) has no state of the scene", what); return PF_ERR_STATE; }
+   if (!st->u_prev || !st->u_cur) return fail("%s: null field array", what);
+   if (m->sd->Nbl > 0 && (!st->u1b || !st->u2b || !st->vh1 || !st->gh1)) return fail("%s: null node array", what);
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   if (m->one_thread) { for (int g = 0; g < S.G; g++) state_slab(S, g, m->sd, st, load); }
+   else {
+      { std::lock_guard<std::mutex> lk(m->mu); m->cmd_state = st; }
+      post(m, load ? 4 : 3, 0, 0);
+      wait_done(m);
+      if (m->broken && !S.err.load()) S.set_error(PF_ERR_HIP, "slab chain hung: a slab's host thread never came back");
+   }
+   if (S.err.load()) {
+      // a refusal (PF_ERR_STATE, PF_ERR_ARG) leaves every engine as it was: the chain stays usable
+      const int code = S.err.load();
+      pf__set_error(S.err_msg.c_str());
+      if (code == PF_ERR_STATE || code == PF_ERR_ARG) S.err.store(0);
+      return code;
+   }
+   return PF_OK;
+}
+int pf_multi_save_state(pf_multi *m, pf_state *st) { return multi_state(m, st, false, "pf_multi_save_state"); }
+int pf_multi_load_state(pf_multi *m, const pf_state *st) { return multi_state(m, const_cast<pf_state *>(st), true, "pf_multi_load_state"); }
 
 int pf_multi_get_info(pf_multi *m, pf_multi_info *info) {
    if (!m || !info) return fail("pf_multi_get_info: null argument");

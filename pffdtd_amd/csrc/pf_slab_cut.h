@@ -17,6 +17,7 @@ struct Slab {
    bool first = false, last = false;
    // host arrays of the local pf_simdata
    std::vector<int64_t> bn, bnl, bna, in, out, out_reorder, out_rows;
+   std::vector<int64_t> bnl_rows; // per local lossy entry: its row in the scene's bnl_ixyz (pf_state_cut.h: the canonical node state goes by those rows)
    std::vector<uint16_t> adj;
    std::vector<int8_t> K, matl, Q;
    std::vector<uint8_t> ssaf; // Real bytes
@@ -149,6 +150,7 @@ inline const char *cut_slab(const pf_simdata *sd, const std::vector<int64_t> &cu
       const int64_t ii = sd->bnl_ixyz[i];
       if (!updates(ii)) continue;
       s.bnl.push_back(local(ii));
+      s.bnl_rows.push_back(i);
       s.matl.push_back(sd->mat_bnl[i]);
       const uint8_t *p = (const uint8_t *)sd->ssaf_bnl + (size_t)i * rb;
       s.ssaf.insert(s.ssaf.end(), p, p + rb);

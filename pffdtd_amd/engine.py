@@ -56,14 +56,41 @@ class PfMultiInfo(ctypes.Structure):
                 ("transport_note", ctypes.c_char * 256), ("wall_scale", ctypes.c_double), ("wall_measured", ctypes.c_int32)]
 
 
+class PfState(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("u_prev", "u_cur", "u1b", "u2b", "vh1", "gh1")]
+
+
+STATE_KEYS = tuple(k for k, _ in PfState._fields_)
+PF_MMB = 12
+
+
 class PfError(RuntimeError):
-    pass
+    code = None  # the pf_status behind it, where a library call returned one (4 = PF_ERR_STATE: call sequence violated)
+
+
+def _state_arrays(sd, state=None):
+    """The six arrays of a pf_state for scene sd (new ones, or `state`'s checked and made contiguous) and the struct that names them."""
+    dt = np.float32 if sd.real_bytes == 4 else np.float64
+    shapes = {"u_prev": (sd.Nx, sd.Ny, sd.Nz), "u_cur": (sd.Nx, sd.Ny, sd.Nz), "u1b": (sd.Nbl,), "u2b": (sd.Nbl,),
+              "vh1": (sd.Nbl, PF_MMB), "gh1": (sd.Nbl, PF_MMB)}
+    arr = {}
+    for k in STATE_KEYS:
+        if state is None:
+            arr[k] = np.zeros(shapes[k], dtype=dt)
+        else:
+            a = np.ascontiguousarray(state[k], dtype=dt)
+            if a.size != int(np.prod(shapes[k])):
+                raise PfError(f"state[{k!r}] has {a.size} elements, the scene needs {int(np.prod(shapes[k]))}")
+            arr[k] = a.reshape(shapes[k])
+    st = PfState(**{k: arr[k].ctypes.data_as(ctypes.c_void_p) if arr[k].size else None for k in STATE_KEYS})
+    return arr, st
 
 
 EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_grid_bytes", "pf_grid_pitch", "pf_opts_default",
            "pf_run_sim", "pf_engine_create", "pf_engine_destroy", "pf_engine_run", "pf_engine_step_begin",
            "pf_engine_halo_ptrs", "pf_engine_step_end", "pf_engine_state_grids", "pf_engine_layout", "pf_engine_place_grids", "pf_engine_place_grids5", "pf_engine_set_spares", "pf_engine_stream", "pf_engine_sync",
-           "pf_engine_flush_outputs", "pf_engine_get_grid", "pf_engine_set_grid", "pf_engine_timing", "pf_engine_set_timing",
+           "pf_engine_flush_outputs", "pf_engine_get_grid", "pf_engine_set_grid", "pf_engine_save_state", "pf_engine_load_state",
+           "pf_multi_save_state", "pf_multi_load_state", "pf_engine_timing", "pf_engine_set_timing",
            "pf_engine_energy_cfg", "pf_engine_run_energy", "pf_run_sim_devices", "pf_slab_partition", "pf_slab_partition_w", "pf_slab_partition_axis", "pf_slab_wall_scale",
            "pf_multi_create", "pf_multi_run", "pf_multi_get_info", "pf_multi_get_slab", "pf_multi_destroy",
            "pf_rccl_unique_id", "pf_rccl_comm_create", "pf_rccl_exchange", "pf_rccl_comm_destroy"]
@@ -144,6 +171,8 @@ def lib():
         L.pf_engine_get_grid.argtypes = [vp, i32, vp]
         L.pf_engine_set_grid.argtypes = [vp, i32, vp]
         L.pf_engine_timing.argtypes = [vp, ctypes.POINTER(PfTiming), i32]
+        for f in (L.pf_engine_save_state, L.pf_engine_load_state, L.pf_multi_save_state, L.pf_multi_load_state):
+            f.argtypes = [vp, ctypes.POINTER(PfState)]
         L.pf_engine_set_timing.argtypes = [vp, i32]
         dp = ctypes.POINTER(ctypes.c_double)
         L.pf_engine_energy_cfg.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, dp]
@@ -173,7 +202,9 @@ def lib():
 
 def _check(rc):
     if rc != 0:
-        raise PfError(f"pffdtd_hip error {rc}: {lib().pf_last_error().decode()}")
+        e = PfError(f"pffdtd_hip error {rc}: {lib().pf_last_error().decode()}")
+        e.code = int(rc)
+        raise e
 
 
 def device_count():
@@ -247,6 +278,18 @@ class HipMulti:
                 "exchange_nonzero": bool(i.exchange_nonzero), "cut_along_z": bool(i.cut_along_z), "plane_bytes": i.plane_bytes,
                 "last_run_seconds": i.last_run_seconds, "transport_note": i.transport_note.decode(),
                 "wall_scale": i.wall_scale, "wall_measured": bool(i.wall_measured)}
+
+    def save_state(self):
+        """The whole scene's state between two steps in its canonical form (pf_multi_save_state): a dict of numpy arrays,
+        u_prev / u_cur (Nx, Ny, Nz), u1b / u2b (Nbl,), vh1 / gh1 (Nbl, 12)."""
+        arr, st = _state_arrays(self.sd)
+        _check(lib().pf_multi_save_state(self._h, ctypes.byref(st)))
+        return arr
+
+    def load_state(self, state):
+        """pf_multi_load_state: continue with run(n, ...) from the step the state was saved at."""
+        arr, st = _state_arrays(self.sd, state)
+        _check(lib().pf_multi_load_state(self._h, ctypes.byref(st)))
 
     def slab(self, g):
         """-> dict(x0, x1, device, paired, steps_per_pass, engine): engine = a non-owning HipEngine view of slab g's engine (state_grids, timing)"""
@@ -394,6 +437,20 @@ class HipEngine:
         a = np.ascontiguousarray(a, dtype=self.dtype)
         assert a.size == self.sd.Npts
         _check(lib().pf_engine_set_grid(self._h, int(which), a.ctypes.data_as(ctypes.c_void_p)))
+
+    def save_state(self):
+        """The whole state between two steps in its canonical form (pf_engine_save_state): a dict of numpy arrays, u_prev / u_cur
+        (Nx, Ny, Nz) in file order, u1b / u2b (Nbl,) and vh1 / gh1 (Nbl, 12) in the order of sd.bnl_ixyz.  The step index and
+        the receiver rows before it (sd.u_out) are the caller's."""
+        arr, st = _state_arrays(self.sd)
+        _check(lib().pf_engine_save_state(self._h, ctypes.byref(st)))
+        return arr
+
+    def load_state(self, state):
+        """pf_engine_load_state: this engine now holds `state` (from any engine or chain of the same scene and precision);
+        continue with run(n, ...)."""
+        arr, st = _state_arrays(self.sd, state)
+        _check(lib().pf_engine_load_state(self._h, ctypes.byref(st)))
 
     def energy_cfg(self, h, c, Ts, DEF_list):
         """DEF_list: the materials' (Mb,3) arrays (sim_mats.h5 mat_XX_DEF)."""

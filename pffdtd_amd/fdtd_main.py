@@ -19,13 +19,20 @@ exchanges over RCCL through torch.distributed; rank 0 gathers the receiver rows 
 `--progress [K]` prints the reference's progress fields (fdtd_common.h:106-190: T / I / TPW / IPW / TA / IA / TB / IB Mvox/s
 and the air share, "I" = over the last K steps, default 200) as one plain line per report -- the reference redraws six
 lines per STEP, which would cost a device synchronisation per step here.
+
+Checkpoint and resume (no counterpart in the reference, whose run_steps is re-entrant in memory only): `--checkpoint FILE` names a
+checkpoint file (pffdtd_amd/checkpoint.py), written every `--checkpoint-every K` steps and when `--stop-after N` ends the run after
+its first N steps (steps 0 .. N-1; exit status 0, no sim_outs.h5); `--resume FILE` continues from such a file and produces the
+sim_outs.h5 of a run in one piece, bit for bit.  A chain whose slabs step in blocked pairs or triples can only be saved between
+passes: the checkpoint is then taken up to five steps later, at the first step every slab's pass has ended (the file records its step).
+One process with one device or a chain of them; the one-process-per-GPU launcher refuses these arguments.
 """
 import argparse
 import os
 import time
 from pathlib import Path
 
-from . import engine, sim_data
+from . import checkpoint, engine, sim_data
 
 
 def _summary(sd, tm, el):
@@ -59,9 +66,28 @@ def _progress(sd, n, nt, t_all, t_chunk, k, air_all, air_chunk, bn_all, bn_chunk
           f"T: {100.0 * air_all / max(t_all, 1e-12):02.1f}% - I: {100.0 * air_chunk / max(t_chunk, 1e-12):02.1f}%", flush=True)
 
 
+def _save_checkpoint(a, sd, m, n):
+    """the checkpoint at step n -- or, where a slab is inside a blocked pass there, at the first step after it at which none is; -> that step"""
+    while True:
+        try:
+            state = m.save_state()
+            break
+        except engine.PfError as e:
+            if e.code != 4 or n >= sd.Nt:  # (PF_ERR_STATE: inside a pass)
+                raise
+        m.run(n, 1)
+        n += 1
+    checkpoint.write(a.checkpoint, sd, n, state)
+    print(f"--checkpoint at step {n} of {sd.Nt}: {a.checkpoint}", flush=True)
+    return n
+
+
 def _run_chain(a, sd, m):
-    """all Nt steps of a chain object, in one go or in chunks with progress reports; returns (seconds, timing of the busiest slab)"""
+    """all Nt steps of a chain object, in one go or in chunks with progress reports; returns (seconds, timing of the busiest slab).
+    With --resume / --checkpoint / --stop-after: from the resumed step, to the step the run stops after (a.stopped_at: less than Nt then)."""
     live = range(m.nslabs)
+    if a.resume or a.checkpoint:
+        return _run_chain_checkpointed(a, sd, m)
     t0 = time.perf_counter()
     if not a.progress:
         m.run(0, sd.Nt)
@@ -87,6 +113,57 @@ def _run_chain(a, sd, m):
     return time.perf_counter() - t0, {"air_ms_total": air_all * 1e3, "step_ms_total": step_all * 1e3}
 
 
+def _run_chain_checkpointed(a, sd, m):
+    live = range(m.nslabs)
+    n = 0
+    if a.resume:
+        try:
+            n, state, u_out = checkpoint.read(a.resume, sd)
+        except (checkpoint.CheckpointMismatch, KeyError, IOError) as e:
+            raise SystemExit(f"cannot resume: {e}")
+        sd.u_out[...] = u_out  # (in place: the library writes into this array)
+        m.load_state(state)
+        print(f"--resumed at step {n} of {sd.Nt}: {a.resume}", flush=True)
+    end = sd.Nt if a.stop_after is None else min(max(a.stop_after, n), sd.Nt)
+    every = a.checkpoint_every if a.checkpoint else 0
+    t0 = time.perf_counter()
+    air_all = step_all = 0.0
+    while n < end:
+        k = end - n
+        if a.progress:
+            k = min(k, a.progress)
+        if every:
+            k = min(k, every - n % every)
+        tc = time.perf_counter()
+        m.run(n, k)
+        n += k
+        if a.checkpoint and n < sd.Nt and ((every and n % every == 0) or n == end):
+            n = _save_checkpoint(a, sd, m, n)
+            end = max(end, n)
+        now = time.perf_counter()
+        tms = [m.slab(g)["engine"].timing(reset=True) for g in live]
+        air = max(t["air_ms_total"] for t in tms) * 1e-3
+        step = max(t["step_ms_total"] for t in tms) * 1e-3
+        if step <= 0:
+            step = now - tc
+        air_all += air
+        step_all += step
+        if a.progress:
+            _progress(sd, n, sd.Nt, now - t0, now - tc, k, air_all, air, max(step_all - air_all, 1e-12), max(step - air, 1e-12), m.nslabs)
+    a.stopped_at = n
+    return time.perf_counter() - t0, {"air_ms_total": air_all * 1e3, "step_ms_total": step_all * 1e3}
+
+
+def _stopped_early(a, sd):
+    """--stop-after ended the run before Nt: the checkpoint is the result, no sim_outs.h5"""
+    n = getattr(a, "stopped_at", sd.Nt)
+    if n >= sd.Nt:
+        return False
+    print(f"--stopped after {n} of {sd.Nt} steps; continue with --resume {a.checkpoint}")
+    print(f"--Date and time: {time.ctime()}")
+    return True
+
+
 def run_single(a):
     """One device.  Rooms (scenes the library stores with the x and z axes exchanged) run as TWO slabs on it, like pf_run_sim:
     the halves' kernels overlap (CTK church 313 against 288 Gvox/s); box rooms as one domain."""
@@ -103,6 +180,8 @@ def run_single(a):
     if tm["step_ms_total"] <= 0:  # (slab engines time their interior launches only)
         tm["step_ms_total"] = el * 1e3
     m.close()
+    if _stopped_early(a, sd):
+        return
     _summary(sd, tm, el)
     _finish(sd, a.data_dir)
 
@@ -126,6 +205,8 @@ def run_devices(a, devices):
     m.close()
     if info["exchange_verified"] is False:
         raise SystemExit("slab exchange self-check failed: a ghost plane does not hold what the neighbour sent")
+    if _stopped_early(a, sd):
+        return
     _summary(sd, tm, el)
     _finish(sd, a.data_dir)
 
@@ -189,8 +270,19 @@ def main():
     p.add_argument("--devices", default="", help="comma-separated device chain instead of 0 .. N-1, e.g. 0,1,2,3 (ids may repeat)")
     p.add_argument("--progress", type=int, nargs="?", const=200, default=0, metavar="K",
                    help="report the reference's progress fields (fdtd_common.h:106-190) every K steps (default 200)")
+    p.add_argument("--checkpoint", default="", metavar="FILE", help="checkpoint file to write (--checkpoint-every, --stop-after)")
+    p.add_argument("--checkpoint-every", type=int, default=0, metavar="K", help="write the checkpoint every K steps")
+    p.add_argument("--stop-after", type=int, default=None, metavar="N",
+                   help="take the first N steps (0 .. N-1), write the checkpoint and exit with status 0, without sim_outs.h5")
+    p.add_argument("--resume", default="", metavar="FILE", help="continue from this checkpoint file")
     a = p.parse_args()
+    if (a.checkpoint_every or a.stop_after is not None) and not a.checkpoint:
+        p.error("--checkpoint-every / --stop-after need --checkpoint FILE")
+    if a.checkpoint_every < 0 or (a.stop_after is not None and a.stop_after < 0):
+        p.error("--checkpoint-every / --stop-after: not negative")
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1 and (a.checkpoint or a.resume) and not a.devices:
+        raise SystemExit("--checkpoint / --resume: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
     if a.devices:
         return run_devices(a, [int(v) for v in a.devices.split(",")])
     if world > 1:
