@@ -11,10 +11,8 @@
    void drop_blocking() {
       tb2 = tb3 = false;
       free_walls();
-      for (Real **g : {&bufC, &bufD, &bufE})
-         if (*g) { own_list.erase(std::remove(own_list.begin(), own_list.end(), *g), own_list.end()); hipFree(*g); *g = nullptr; }
-      auto F = [](auto *&p) { if (p) hipFree((void *)p); p = nullptr; };
-      F(zs_map); F(zs_adj); F(zs_li); F(zs_rest); F(zs_fd);
+      mem.release(bufC); mem.release(bufD); mem.release(bufE);
+      mem.release(zs_map); mem.release(zs_adj); mem.release(zs_li); mem.release(zs_rest); mem.release(zs_fd);
       zs_mode = 0;
    }
    // Three steps per pass where they can be had: single-domain 7-point engines in file-order storage, 64-lane row segments, the
@@ -229,8 +227,7 @@
          }
          tb_nclean = (int64_t)cl.size(); tb_ndirty = (int64_t)di.size(); tb_clean_cells = vol;
          int rc;
-         if (tb_clean) { hipFree(tb_clean); tb_clean = nullptr; }
-         if (tb_dirty) { hipFree(tb_dirty); tb_dirty = nullptr; }
+         mem.release(tb_clean); mem.release(tb_dirty); // (a second geometry: both tables go before either is replaced -- the order of a creation's allocations is part of where its grids land)
          {
             // k_tb3 keeps u^{n+1} on the chip: the clean neighbours of a tile that steps singly (26-neighbourhood) are flagged to
             // store theirs, which that tile's second step reads
@@ -250,7 +247,7 @@
             std::vector<int32_t> clf(cl);
             flag_rims(clf);
             if ((rc = upload(&tb_clean, clf.data(), tb_nclean))) return rc;
-            if (tb_srct) { hipFree(tb_srct); tb_srct = nullptr; }
+            mem.release(tb_srct);
             tb_nsrct = (int64_t)sr.size();
             if (tb_nsrct > 0) {
                flag_rims(sr);
@@ -274,7 +271,7 @@
                svol += (int64_t)(std::min(tbx0 + (xc + 1) * tb_chunk, tbx1) - (tbx0 + xc * tb_chunk)) *
                        (std::min(tby0 + (yt + 1) * TR, tby1) - (tby0 + yt * TR)) * (std::min(tbz0 + (zt + 1) * TC, tbz1) - (tbz0 + zt * TC));
             }
-            if (tb_sample) { hipFree(tb_sample); tb_sample = nullptr; }
+            mem.release(tb_sample);
             tb_nsample = 0; tb_sample_frac = 1.0;
             if (k > 1 && !sm.empty() && vol > 0) {
                tb_nsample = (int64_t)sm.size(); tb_sample_frac = (double)svol / (double)vol;
@@ -307,7 +304,6 @@
                      if (need) sh.push_back((int32_t)(((int64_t)xc * sh_nyt + yt) * sh_nzt + zt));
                   }
             sh_ntiles = (int64_t)sh.size();
-            if (sh_tiles) { hipFree(sh_tiles); sh_tiles = nullptr; }
             if ((rc = upload(&sh_tiles, sh.data(), sh_ntiles))) return rc;
          }
       }
@@ -325,16 +321,13 @@
       bufC = try_dzalloc<Real>(npad);
       bufD = bufC ? try_dzalloc<Real>(npad) : nullptr;
       if (!bufD) { // no room for two more grids (state > ~45 % of the device memory): keep stepping singly
-         if (bufC) hipFree(bufC);
-         bufC = bufD = nullptr;
+         mem.release(bufC);
          tb2_geom = false;
          return PF_OK;
       }
-      own_list.push_back(bufC); own_list.push_back(bufD);
       if (triple) {
          bufE = try_dzalloc<Real>(npad);
          if (!bufE) return PF_OK; // (no room for a fifth grid: init_tb2 falls back to pairs)
-         own_list.push_back(bufE);
       }
       tb2 = true;
       { int rcw = init_walls(); if (rcw) return rcw; }

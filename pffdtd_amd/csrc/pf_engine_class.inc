@@ -16,6 +16,7 @@
 
 #include "pffdtd_hip.h"
 #include "pf_debug.h"
+#include "pf_devmem.h"
 #include "pf_kernels.h"
 #include "pf_air_fused.h"
 #include "pf_energy.h"
@@ -99,6 +100,37 @@ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // (median 3.15) against 2.975 ... 3.65 without (median 3.23).)
 int64_t grid_pitch(int64_t Nz, int32_t real_bytes) { return round_up(Nz, 128 / real_bytes); }
 
+void dev_free(void *p) { hipFree(p); } // the one free function: the engines' owners (pf_devmem.h) are handed it
+
+// The creation-time measurements' clock: two events, created once per measurement function and destroyed with it
+struct Stopwatch {
+   hipEvent_t e0 = nullptr, e1 = nullptr;
+   hipError_t err; // of the creation
+   Stopwatch() { err = hipEventCreate(&e0); if (err == hipSuccess) err = hipEventCreate(&e1); }
+   Stopwatch(const Stopwatch &) = delete;
+   Stopwatch &operator=(const Stopwatch &) = delete;
+   ~Stopwatch() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
+   // ms that `reps` runs of fn take on stream s, after `warm` untimed ones
+   template <typename Fn> float ms(hipStream_t s, int warm, int reps, Fn &&fn) {
+      for (int i = 0; i < warm; i++) fn();
+      hipEventRecord(e0, s);
+      for (int i = 0; i < reps; i++) fn();
+      hipEventRecord(e1, s);
+      hipEventSynchronize(e1);
+      float t = 0;
+      hipEventElapsedTime(&t, e0, e1);
+      return t;
+   }
+};
+
+// a field set for a scope (measurement mode: Engine::tb2_probe, op.timing): every return path puts the old value back
+template <typename T> struct Restore {
+   T &ref; const T old;
+   Restore(T &r, T v) : ref(r), old(r) { r = v; }
+   Restore(const Restore &) = delete;
+   ~Restore() { ref = old; }
+};
+
 // DPP wave-shift semantics verified once per process on the device
 int dpp_ok_cached = -1;
 int check_dpp(hipStream_t s) {
@@ -108,7 +140,7 @@ int check_dpp(hipStream_t s) {
    hipLaunchKernelGGL(pf::k_dpp_selftest, dim3(1), dim3(64), 0, s, d);
    hipMemcpyAsync(&h, d, sizeof(int), hipMemcpyDeviceToHost, s);
    hipStreamSynchronize(s);
-   hipFree(d);
+   dev_free(d);
    dpp_ok_cached = h;
    return h;
 }
@@ -142,7 +174,7 @@ template <typename Real> struct Engine : EngineBase {
    bool own_grids = true;
    std::vector<float> place_ms;                           // sample_placement: ms per launch of every candidate
    bool tb2_probe = false;                                // launch_tb2 under its creation-time name (k_tb2_reg<..., PROBE>)
-   std::vector<Real *> own_list;
+   pf::DevMem mem{dev_free};                              // everything this engine allocated on the device (upload, dalloc, dzalloc, try_dzalloc), temporaries included
    uint8_t *mask = nullptr;      // skip-mask (boundary nodes + ghost z + pad + parity)
    int lw_force = 0;             // autotune: lanes per row segment of the barrier-free kernels (0 = pick_lw's rule)
    int order_force = -1;         // autotune: tile order of the marching kernels (-1 = swizzle_mode's rule; 0 plain, 2 XCD-banded)
@@ -343,12 +375,7 @@ template <typename Real> struct Engine : EngineBase {
    void destroy() {
       if (s_main) hipStreamSynchronize(s_main);
       if (s_edge) hipStreamSynchronize(s_edge);
-      auto F = [](void *p) { if (p) hipFree(p); };
-      for (Real *g : own_list) F(g); // state grids this engine allocated (u0/u1 unless external, the temporal-blocking spares)
-      own_list.clear();
-      free_fcc_bricks();
-      F(wl_pen); F(wl_rec); F(wl_rest); F(wl_blk); F(wl_brk); F(wl_binfo); F(wl_blos); F(ubx[0]); F(ubx[1]); F(edge_sel3); F(vh1b); F(gh1b); F(d_lossy); F(d_lperm); F(mask); F(zs_map); F(zs_adj); F(zs_li); F(zs_rest); F(zs_fd); F(tb_clean); F(tb_dirty); F(tb_srct); F(tb_sample); F(sh_tiles); F(Lu); F(vh_old); F(u2in); F(d_acc); F(d_DEF); F(d_bn); F(d_bnl); F(d_bna); F(d_in); F(d_out); F(d_adj); F(d_Q); F(d_mat); F(d_Mb); F(d_ssaf);
-      F(d_beta); F(d_insig); F(d_mq); F(ub[0]); F(ub[1]); F(ub[2]); F(u2ba); F(vh1); F(gh1); F(ring);
+      mem.release_all();
       if (h_ring) hipHostFree(h_ring);
       for (auto &p : air_ev) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
       for (auto &p : step_ev) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
@@ -361,7 +388,6 @@ template <typename Real> struct Engine : EngineBase {
       if (ev_src1) hipEventDestroy(ev_src1);
       ev_src0 = ev_src1 = nullptr;
       if (gexec) hipGraphExecDestroy(gexec);
-      if (d_ctr) hipFree(d_ctr);
       if (s_wall) hipStreamDestroy(s_wall);
       if (s_wall2) hipStreamDestroy(s_wall2);
       if (ev_wall0) hipEventDestroy(ev_wall0);
@@ -384,13 +410,22 @@ template <typename Real> struct Engine : EngineBase {
       return (ix * Ny + iy) * P + iz;
    }
 
-   template <typename T> int upload(T **dst, const T *src, int64_t n) {
+   // Device memory: whatever *dst owned before is released first (a re-upload frees the table it replaces), what is allocated is mem's.
+   template <typename T> int dalloc(T **dst, int64_t n) { // uninitialised
+      mem.release(*dst);
       *dst = nullptr;
       HIPCHK(hipMalloc((void **)dst, std::max<int64_t>(n, 1) * sizeof(T)));
+      mem.take(*dst);
+      return PF_OK;
+   }
+   template <typename T> int upload(T **dst, const T *src, int64_t n) {
+      int rc = dalloc(dst, n);
+      if (rc) return rc;
       if (n > 0) HIPCHK(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
       return PF_OK;
    }
    template <typename T> int dzalloc(T **dst, int64_t n) {
+      mem.release(*dst);
       *dst = nullptr;
       size_t bytes = std::max<int64_t>(n, 1) * sizeof(T);
       { // (a full device is the one failure a caller can act on: say how much was asked for and how much there was)
@@ -402,6 +437,7 @@ template <typename Real> struct Engine : EngineBase {
             return set_err(PF_ERR_HIP, "HIP error %s allocating %zu bytes of engine state (%zu of %zu bytes free on device %d): %s", hipGetErrorName(e), bytes, fr, tot, op.device, hipGetErrorString(e));
          }
       }
+      mem.take(*dst);
       HIPCHK(hipMemset(*dst, 0, bytes));
       return PF_OK;
    }
@@ -411,7 +447,8 @@ template <typename Real> struct Engine : EngineBase {
       T *p = nullptr;
       const size_t bytes = std::max<int64_t>(n, 1) * sizeof(T);
       if (hipMalloc((void **)&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-      if (hipMemset(p, 0, bytes) != hipSuccess) { (void)hipGetLastError(); hipFree(p); return nullptr; }
+      mem.take(p);
+      if (hipMemset(p, 0, bytes) != hipSuccess) { (void)hipGetLastError(); mem.release(p); return nullptr; }
       return p;
    }
    // split a sorted padded-index list into the ranges of planes 1..w / w+1..Nx-2-w / Nx-1-w..Nx-2
@@ -527,7 +564,6 @@ template <typename Real> struct Engine : EngineBase {
          int rc;
          if ((rc = dzalloc(&u0, npad))) return rc;
          if ((rc = dzalloc(&u1, npad))) return rc;
-         own_list.push_back(u0); own_list.push_back(u1);
       }
 
       // ---- sorted, re-based node lists ----
@@ -684,17 +720,18 @@ template <typename Real> struct Engine : EngineBase {
       }
       std::lock_guard<std::mutex> tune_lock(pf__tune_mu[op.device & 63]);
       { int rc = init_tb2(); if (rc) return rc; }
-      tb2_probe = true;
-      // pairs or single steps?  A first measurement on the grids as allocated drops pairs that are hopeless (rooms whose clean
-      // tiles are few: CTK, Musikverein) before any placement search is spent on them -- placement is worth up to ~10 %, so a
-      // pair path more than 12 % behind the single steps cannot win; the survivors get their grids placed and are measured again
-      pair_margin = 1.12f;
-      { int rc = autotune(); if (rc) { tb2_probe = false; return rc; } }
-      { int rc = sample_placement(); if (rc) { tb2_probe = false; return rc; } }
-      pair_margin = 0.99f;
-      if (tb2) { int rc = autotune(); if (rc) { tb2_probe = false; return rc; } }
-      else if (fcc) { int rc = autotune_fcc_lw(); if (rc) { tb2_probe = false; return rc; } } // (pairs dropped or never offered)
-      tb2_probe = false;
+      {
+         const Restore<bool> probe(tb2_probe, true);
+         // pairs or single steps?  A first measurement on the grids as allocated drops pairs that are hopeless (rooms whose clean
+         // tiles are few: CTK, Musikverein) before any placement search is spent on them -- placement is worth up to ~10 %, so a
+         // pair path more than 12 % behind the single steps cannot win; the survivors get their grids placed and are measured again
+         pair_margin = 1.12f;
+         { int rc = autotune(); if (rc) return rc; }
+         { int rc = sample_placement(); if (rc) return rc; }
+         pair_margin = 0.99f;
+         if (tb2) { int rc = autotune(); if (rc) return rc; }
+         else if (fcc) { int rc = autotune_fcc_lw(); if (rc) return rc; } // (pairs dropped or never offered)
+      }
       if (fb_want) { int rc = init_fcc_bricks(); if (rc) return rc; }
       if (tb3) tb3_remember_home();
       if (!tb2 && op.slab_first && op.slab_last) { int rc = sample_placement_single(); if (rc) return rc; }
@@ -723,7 +760,7 @@ template <typename Real> struct Engine : EngineBase {
 #include "pf_engine_launch.inc"
    // ---- graph replay of the single-stream step loop ----
    int build_graph() {
-      if (!d_ctr) HIPCHK(hipMalloc((void **)&d_ctr, 2 * sizeof(int64_t)));
+      if (!d_ctr) { int rc = dalloc(&d_ctr, 2); if (rc) return rc; }
       hipGraph_t g = nullptr;
       HIPCHK(hipStreamBeginCapture(s_main, hipStreamCaptureModeThreadLocal));
       Real *ua = u0, *uc = u1, *x[3] = {ub[0], ub[1], ub[2]};
@@ -997,11 +1034,11 @@ template <typename Real> struct Engine : EngineBase {
       }
       if (swz) { // storage -> file order through a device-side transposition
          Real *tmp = nullptr;
-         HIPCHK(hipMalloc((void **)&tmp, (size_t)sd.Npts * sizeof(Real)));
+         if ((rc = dalloc(&tmp, sd.Npts))) return rc;
          hipLaunchKernelGGL((pf::k_storage_to_file<Real>), dim3((unsigned)cdiv(sd.Npts, 256)), dim3(256), 0, s_main, src, tmp, fNx, fNy, fNz, Ny, P);
          const hipError_t e = hipMemcpyAsync(host, tmp, (size_t)sd.Npts * sizeof(Real), hipMemcpyDeviceToHost, s_main);
          hipStreamSynchronize(s_main);
-         hipFree(tmp);
+         mem.release(tmp);
          HIPCHK(e);
          return PF_OK;
       }
@@ -1016,11 +1053,11 @@ template <typename Real> struct Engine : EngineBase {
       state_touched = true;
       if (swz) {
          Real *tmp = nullptr;
-         HIPCHK(hipMalloc((void **)&tmp, (size_t)sd.Npts * sizeof(Real)));
+         if ((rc = dalloc(&tmp, sd.Npts))) return rc;
          hipError_t e = hipMemcpyAsync(tmp, host, (size_t)sd.Npts * sizeof(Real), hipMemcpyHostToDevice, s_main);
          hipLaunchKernelGGL((pf::k_file_to_storage<Real>), dim3((unsigned)cdiv(sd.Npts, 256)), dim3(256), 0, s_main, tmp, dst, fNx, fNy, fNz, Ny, P);
          hipStreamSynchronize(s_main);
-         hipFree(tmp);
+         mem.release(tmp);
          HIPCHK(e);
          return PF_OK;
       }

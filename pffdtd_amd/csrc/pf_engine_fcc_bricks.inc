@@ -10,8 +10,7 @@
    int64_t fb_nbrk = 0, fb_nrest = 0, fb_ntiles = 0;
    size_t fb_lds = 0;
    void free_fcc_bricks() {
-      auto F = [](auto *&p) { if (p) hipFree((void *)p); p = nullptr; };
-      F(fb_brk); F(fb_info); F(fb_los); F(fb_rest); F(fb_tiles);
+      mem.release(fb_brk); mem.release(fb_info); mem.release(fb_los); mem.release(fb_rest); mem.release(fb_tiles);
       fb_nbrk = fb_nrest = fb_ntiles = 0; fb_lds = 0; fb_on = false;
    }
    // what air_variant 42 needs beyond 40, checked before anything is built (init): a folded 13-point grid, a single domain, file order

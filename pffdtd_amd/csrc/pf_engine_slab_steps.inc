@@ -8,7 +8,7 @@
       if (!wl_xw[0]) for (int64_t i = bn_cut[3].lo.b; i < bn_cut[3].lo.e; i++) sel.push_back((int32_t)i); // (wl_xw: that side is no cut -- a region's and the bricks')
       if (!wl_xw[1]) for (int64_t i = bn_cut[3].hi.b; i < bn_cut[3].hi.e; i++) sel.push_back((int32_t)i);
       n_edge_sel3 = (int64_t)sel.size();
-      if (upload(&edge_sel3, sel.data(), n_edge_sel3) != PF_OK) { edge_sel3 = nullptr; edge_sel3_failed = true; (void)hipGetLastError(); return false; }
+      if (upload(&edge_sel3, sel.data(), n_edge_sel3) != PF_OK) { mem.release(edge_sel3); edge_sel3_failed = true; (void)hipGetLastError(); return false; }
       return true;
    }
    int wall_streams() { // a slab's wall regions run on two streams of their own (created on first use)

@@ -35,12 +35,14 @@
    }
    // what both calls allocate for their duration: the fields' staging buffer (exchanged axes only) and the canonical node arrays on the device
    struct StateScratch {
+      pf::DevMem &mem;
       Real *stage = nullptr, *node = nullptr;
-      ~StateScratch() { if (stage) hipFree(stage); if (node) hipFree(node); }
+      ~StateScratch() { mem.release(stage); mem.release(node); }
    };
    int state_scratch(StateScratch &sc) {
-      if (swz) HIPCHK(hipMalloc((void **)&sc.stage, (size_t)(std::min<int64_t>(pf::STATE_STAGE_PLANES, fNx) * fNy * fNz) * sizeof(Real)));
-      if (Nbl) HIPCHK(hipMalloc((void **)&sc.node, (size_t)Nbl * (2 * PF_MMB + 2) * sizeof(Real))); // vh1 | gh1 | u1b | u2b
+      int rc;
+      if (swz && (rc = dalloc(&sc.stage, std::min<int64_t>(pf::STATE_STAGE_PLANES, fNx) * fNy * fNz))) return rc;
+      if (Nbl && (rc = dalloc(&sc.node, Nbl * (2 * PF_MMB + 2)))) return rc; // vh1 | gh1 | u1b | u2b
       return PF_OK;
    }
    int state_args(const pf_state *st, const char *what) {
@@ -56,7 +58,7 @@
       HIPCHK(hipSetDevice(op.device));
       if ((rc = flush())) return rc;
       if ((rc = sync())) return rc;
-      StateScratch sc;
+      StateScratch sc{mem};
       if ((rc = state_scratch(sc))) return rc;
       if (lean || vg) { launch_flips(s_main, grids()); HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(s_main)); } // the virtual ghost shell of u^n, as get_grid(1)
       if ((rc = state_field(u0, (Real *)st->u_prev, true, sc.stage))) return rc;
@@ -84,7 +86,7 @@
       HIPCHK(hipSetDevice(op.device));
       if ((rc = flush())) return rc; // rows of the steps before: the caller's (sd->u_out)
       if ((rc = sync())) return rc;
-      StateScratch sc;
+      StateScratch sc{mem};
       if ((rc = state_scratch(sc))) return rc;
       state_touched = true;
       // the targets of the blocked passes (the triples' u^{n+1} grid among them)

@@ -15,9 +15,10 @@
       constexpr int V = pf::VecOf<Real>::V;
       Real *scr = try_dzalloc<Real>(npad);
       if (!scr) return PF_OK;
-      hipEvent_t e0, e1;
-      HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+      Stopwatch sw;
+      HIPCHK(sw.err);
       const Grids g{u0, u1, scr}; // (out of place: the state is not touched)
+      auto march3 = [&] { return sw.ms(s_main, 1, 3, [&] { launch_air_march(s_main, g, 1, (int)Nx - 1); }); }; // (compared undivided)
       int best_lw = 0;
       float best = 0;
       int64_t seen = -1;
@@ -26,52 +27,28 @@
          if (w == seen) continue; // same padded width as the wider segment: the wider one wins anyway
          seen = w;
          lw_force = lw;
-         launch_air_march(s_main, g, 1, (int)Nx - 1);
-         hipEventRecord(e0, s_main);
-         for (int i = 0; i < 3; i++) launch_air_march(s_main, g, 1, (int)Nx - 1);
-         hipEventRecord(e1, s_main);
-         hipEventSynchronize(e1);
-         float ms = 0;
-         hipEventElapsedTime(&ms, e0, e1);
+         const float ms = march3();
          if (best_lw == 0 || ms < 0.98f * best) { best = ms; best_lw = lw; }
       }
       lw_force = best_lw;
       // ... and the tile order: XCD-banded (the rule for large planes) against the plain order.  Rooms stored along their longest
       // axis have long rows (Musikverein: 23 segments of 128 columns) and run 1-3 % faster, and steadier, in the plain order
       // (345.0-345.3 against 335-342 Gvox/s in alternating runs); cubes keep the banded one (2.32 against 2.46 ms at 1024^3).
-      for (int mode : {0}) {
-         order_force = mode;
-         launch_air_march(s_main, g, 1, (int)Nx - 1);
-         hipEventRecord(e0, s_main);
-         for (int i = 0; i < 3; i++) launch_air_march(s_main, g, 1, (int)Nx - 1);
-         hipEventRecord(e1, s_main);
-         hipEventSynchronize(e1);
-         float ms = 0;
-         hipEventElapsedTime(&ms, e0, e1);
-         if (ms < 0.985f * best) best = ms; else order_force = -1;
-      }
+      order_force = 0;
+      const float ms = march3();
+      if (ms < 0.985f * best) best = ms; else order_force = -1;
       tune_ms[1] = best / 3;
-      hipEventDestroy(e0); hipEventDestroy(e1);
       HIPCHK(hipStreamSynchronize(s_main));
-      hipFree(scr);
+      mem.release(scr);
       return hipGetLastError() == hipSuccess ? PF_OK : set_err(PF_ERR_HIP, "13-point segment-width measurement: kernel launch failed");
    }
    int autotune_fcc() {
       if (!tb2) return autotune_fcc_lw();
       if (vbase != 0 || (op.debug & PF_DBG_NO_AUTOTUNE)) return PF_OK;
-      hipEvent_t e0, e1;
-      HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+      Stopwatch sw;
+      HIPCHK(sw.err);
       HIPCHK(hipDeviceSynchronize());
-      auto timed = [&](auto &&fn) -> float {
-         fn();
-         hipEventRecord(e0, s_main);
-         for (int i = 0; i < 3; i++) fn();
-         hipEventRecord(e1, s_main);
-         hipEventSynchronize(e1);
-         float ms = 0;
-         hipEventElapsedTime(&ms, e0, e1);
-         return ms / 3;
-      };
+      auto timed = [&](auto &&fn) { return sw.ms(s_main, 1, 3, fn) / 3; };
       const Grids g1{u0, u1, bufC}, g2{u1, bufC, bufD}; // the two steps of a pair
       for (int i = 0; i < 8 && (double)i * (double)(Nx * Ny * Nz) < 8.0e9; i++) launch_air_march(s_main, g1, 1, (int)Nx - 1); // clocks up
       HIPCHK(hipStreamSynchronize(s_main));
@@ -83,14 +60,12 @@
       });
       if (!(tune_ms[2] < pair_margin * tune_ms[1])) { // not worth it: drop the pair path and its two grids
          tb2 = false;
-         for (Real *g : {bufC, bufD}) { own_list.erase(std::remove(own_list.begin(), own_list.end(), g), own_list.end()); hipFree(g); }
-         bufC = bufD = nullptr;
+         mem.release(bufC); mem.release(bufD);
       } else {
          HIPCHK(hipMemsetAsync(bufC, 0, npad * sizeof(Real), s_main));
          HIPCHK(hipMemsetAsync(bufD, 0, npad * sizeof(Real), s_main));
       }
       HIPCHK(hipDeviceSynchronize());
-      hipEventDestroy(e0); hipEventDestroy(e1);
       return PF_OK;
    }
    // ---- where do the pair's four grids live?  The pair kernel streams four grids at once, and its speed depends on how
@@ -108,21 +83,16 @@
    // two spares are drawn; both: the reverse direction of the four-grid cycle is timed as well (writes every member)
    int search_placement(const std::vector<Real *> &pool, bool fixed_ab, bool both, int evals, const int first[4], int chosen[4]) {
       const bool verbose = getenv("PFFDTD_VERBOSE") && atoi(getenv("PFFDTD_VERBOSE")) > 0;
-      hipEvent_t e0, e1;
-      HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+      Stopwatch sw;
+      HIPCHK(sw.err);
       const bool sampled = tb_sample && tb_nsample > 0;
       const float scale = sampled ? (float)(1.0 / tb_sample_frac) : 1.f; // sampled times are reported as whole-launch equivalents
-      auto time_fwd = [&](Real *A, Real *B, Real *C, Real *D) -> float {
-         hipEventRecord(e0, s_main);
+      // ms per launch of the pass A, B -> C, D: two launches, on the sample of the tiles or on all of them
+      auto time2 = [&](Real *A, Real *B, Real *C, Real *D, bool sample) {
          const Pass p = Pass::of_grids(A, B, C, D);
-         launch_probe(s_main, 0, p, true);
-         launch_probe(s_main, 0, p, true);
-         hipEventRecord(e1, s_main);
-         hipEventSynchronize(e1);
-         float ms = 0;
-         hipEventElapsedTime(&ms, e0, e1);
-         return ms / 2 * scale;
+         return sw.ms(s_main, 0, 2, [&] { launch_probe(s_main, 0, p, sample); }) / 2;
       };
+      auto time_fwd = [&](Real *A, Real *B, Real *C, Real *D) { return time2(A, B, C, D, true) * scale; };
       auto grid = [&](int i, Real *fallback) { return i >= 0 ? pool[i] : fallback; };
       for (int i = 0; i < 4; i++) launch_probe(s_main, 0, Pass::of_grids(grid(first[0], u0), grid(first[1], u1), pool[first[2]], pool[first[3]])); // clocks up
       struct Cand { int r[4]; float ms; };
@@ -195,16 +165,8 @@
          for (size_t k = 0; k < check.size(); k++) {
             Cand &c = cands[check[k]];
             Real *A = grid(c.r[0], u0), *B = grid(c.r[1], u1), *C = pool[c.r[2]], *D = pool[c.r[3]];
-            auto full = [&](Real *a, Real *b, Real *cc, Real *d) {
-               hipEventRecord(e0, s_main);
-               const Pass p = Pass::of_grids(a, b, cc, d);
-               launch_probe(s_main, 0, p); launch_probe(s_main, 0, p);
-               hipEventRecord(e1, s_main); hipEventSynchronize(e1);
-               float ms = 0; hipEventElapsedTime(&ms, e0, e1);
-               return ms / 2;
-            };
-            float ms = full(A, B, C, D);
-            if (both) ms = 0.5f * (ms + full(C, D, A, B));
+            float ms = time2(A, B, C, D, false);
+            if (both) ms = 0.5f * (ms + time2(C, D, A, B, false));
             if (verbose) fprintf(stderr, "pffdtd_hip:   candidate %zu on all tiles: %.3f ms per launch (sample said %.3f)\n", check[k], ms, c.ms);
             c.ms = ms;
             if (k == 0 || ms < best_full) { best_full = ms; best = check[k]; }
@@ -218,22 +180,17 @@
          fprintf(stderr, " ms per launch\n");
       }
       for (int i = 0; i < 4; i++) chosen[i] = cands[best].r[i];
-      hipEventDestroy(e0); hipEventDestroy(e1);
       return hipGetLastError() == hipSuccess ? PF_OK : set_err(PF_ERR_HIP, "placement search: kernel launch failed");
    }
-   int place_evals() const {
-      int evals = 48;
-      return evals;
-   }
+   static constexpr int place_evals = 48; // the budget of one search_placement
    // the single-step paths stream two grids (u^n read, u^{n-1} read and overwritten): the same question with a smaller answer
    // (Musikverein, 13-point, 1.3e9 cells: 4.36-4.61 ms per step over the pairs of a pool of six; small grids: 1-3 %);
    // every unordered pair of the pool is timed on a whole step (both role assignments, the grids swap roles every step)
    int search_pair(const std::vector<Real *> &pool, int &bi, int &bj) {
       const bool verbose = getenv("PFFDTD_VERBOSE") && atoi(getenv("PFFDTD_VERBOSE")) > 0;
-      hipEvent_t e0, e1;
-      HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-      const int tsave = op.timing;
-      op.timing = 0;
+      Stopwatch sw;
+      HIPCHK(sw.err);
+      const Restore<int> untimed(op.timing, 0);
       auto one_step = [&](Real *a, Real *b) { // u^{n-1} in a, u^n in b, in place; all-zero state: every kernel writes zeros
          const Grids g{a, b, a};
          const Bnd bn = bnd(0, 0);
@@ -243,15 +200,7 @@
          launch_rigid(s_main, g, bn, {0, Nb});
          launch_fd(s_main, g, bn, {0, Nbl});
       };
-      auto time_pair = [&](Real *a, Real *b) -> float {
-         hipEventRecord(e0, s_main);
-         one_step(a, b); one_step(b, a); one_step(a, b); one_step(b, a);
-         hipEventRecord(e1, s_main);
-         hipEventSynchronize(e1);
-         float ms = 0;
-         hipEventElapsedTime(&ms, e0, e1);
-         return ms / 4;
-      };
+      auto time_pair = [&](Real *a, Real *b) { return sw.ms(s_main, 0, 1, [&] { one_step(a, b); one_step(b, a); one_step(a, b); one_step(b, a); }) / 4; };
       for (int i = 0; i < 6; i++) one_step(pool[0], pool[1]); // clocks up
       const int n = (int)pool.size();
       bi = 0; bj = 1;
@@ -265,12 +214,10 @@
             if (ms < best) { best = ms; bi = i; bj = j; }
             worst = std::max(worst, ms);
          }
-      op.timing = tsave;
       if (verbose) fprintf(stderr, "pffdtd_hip: grid placement (single steps), %d pairs of a pool of %d: as allocated %.4f, chosen %.4f, slowest %.4f ms per step\n",
                            (int)place_ms.size(), n, first, best, worst);
       for (int i = 0; i < n; i++) HIPCHK(hipMemsetAsync(pool[i], 0, npad * sizeof(Real), s_main)); // (zeros from zeros; be explicit)
       HIPCHK(hipStreamSynchronize(s_main));
-      hipEventDestroy(e0); hipEventDestroy(e1);
       return hipGetLastError() == hipSuccess ? PF_OK : set_err(PF_ERR_HIP, "placement search: kernel launch failed");
    }
    // Candidate grids beyond the engine's own: at most `want`, never more than fit the free memory (less 3 % of the device), and
@@ -286,32 +233,32 @@
       return std::max(0, std::min(want, std::min(cap, fit)));
    }
    bool place_single_ok() const { return !(op.debug & PF_DBG_NO_AUTOTUNE) && !op.energy && vbase == 0 && npad * (int64_t)sizeof(Real) >= ((int64_t)64 << 20); }
-   int sample_placement_single() {
-      if (!own_grids || !place_single_ok()) return PF_OK;
-      int extra = 4;
-      extra = pool_extra(extra, 2);
-      if (extra == 0) return PF_OK;
-      std::vector<Real *> pool = {u0, u1};
-      for (int i = 0; i < extra; i++) {
+   // up to n more zero-filled candidate grids at the pool's end; returns how many there was room for
+   int add_candidates(std::vector<Real *> &pool, int n) {
+      int got = 0;
+      for (; got < n; got++) {
          Real *p = try_dzalloc<Real>(npad);
-         if (!p) break;
+         if (!p) break; // no room for another candidate
          pool.push_back(p);
       }
+      return got;
+   }
+   int sample_placement_single() {
+      if (!own_grids || !place_single_ok()) return PF_OK;
+      const int extra = pool_extra(4, 2);
+      if (extra == 0) return PF_OK;
+      std::vector<Real *> pool = {u0, u1};
+      add_candidates(pool, extra);
       int bi, bj;
       int rc = search_pair(pool, bi, bj);
       if (rc) return rc;
       u0 = pool[bi]; u1 = pool[bj];
-      for (int i = 0; i < (int)pool.size(); i++) {
-         own_list.erase(std::remove(own_list.begin(), own_list.end(), pool[i]), own_list.end());
-         if (i != bi && i != bj) hipFree(pool[i]);
-      }
-      own_list.push_back(u0); own_list.push_back(u1);
+      mem.release_rest(pool, {u0, u1});
       return PF_OK;
    }
    int sample_placement() {
       if (!tb2 || tb2_slab || !bufC || !bufD || (op.debug & PF_DBG_NO_AUTOTUNE) || vbase == 41) return PF_OK;
-      int extra = tb3 ? 3 : 4;
-      extra = pool_extra(extra, tb3 ? 5 : 4);
+      const int extra = pool_extra(tb3 ? 3 : 4, tb3 ? 5 : 4);
       if (extra == 0 && !own_grids) return PF_OK;
       std::vector<Real *> pool;
       if (own_grids) { pool.push_back(u0); pool.push_back(u1); }
@@ -319,14 +266,10 @@
          if (!bufE) return PF_OK;
          pool.push_back(bufD); pool.push_back(bufE); pool.push_back(bufC);
       } else { pool.push_back(bufC); pool.push_back(bufD); }
-      for (int i = 0; i < extra; i++) {
-         Real *p = try_dzalloc<Real>(npad);
-         if (!p) break; // no room for another candidate
-         pool.push_back(p);
-      }
+      add_candidates(pool, extra);
       const int first_own[4] = {0, 1, 2, 3}, first_ext[4] = {-1, -1, 0, 1};
       int w[4];
-      int rc = search_placement(pool, !own_grids, own_grids, place_evals(), own_grids ? first_own : first_ext, w);
+      int rc = search_placement(pool, !own_grids, own_grids, place_evals, own_grids ? first_own : first_ext, w);
       if (rc) return rc;
       // Some pools hold no fast assignment at all (seen once in ~15 boxes: best 3.37 ms of 47 candidates where 2.95 is the
       // rule; round 5, k_tb3: 3.40 of 42 on a box where the next process found 2.99).  For the 7-point kernels the fast level is
@@ -340,16 +283,10 @@
          // the growth path on any box and any size)
          const bool big = npad * (int64_t)sizeof(Real) >= ((int64_t)256 << 20);
          if ((!big || best <= 1.05f * target) && !getenv("PFFDTD_PLACE_FORCE_GROW")) break;
-         size_t grown = 0;
-         for (int i = 0, more = pool_extra(4, (int)pool.size()); i < more; i++) {
-            Real *p = try_dzalloc<Real>(npad);
-            if (!p) break;
-            pool.push_back(p); grown++;
-         }
-         if (!grown) break;
+         if (!add_candidates(pool, pool_extra(4, (int)pool.size()))) break;
          const int cur[4] = {w[0], w[1], w[2], w[3]};
          const std::vector<float> before = place_ms;
-         if ((rc = search_placement(pool, false, true, place_evals(), cur, w))) return rc;
+         if ((rc = search_placement(pool, false, true, place_evals, cur, w))) return rc;
          place_ms.insert(place_ms.begin(), as_allocated); // (the statistics keep the very first candidate in front ...
          place_ms.insert(place_ms.end(), before.begin() + (before.empty() ? 0 : 1), before.end()); // ... and every candidate of the earlier rounds)
       }
@@ -363,40 +300,35 @@
          // stream combinations off the measured cycle, S1 -> (C, D), (C, D) -> S1, S2 -> (C, A), (C, A) -> S2.  A host that
          // steps in regions of 20 (bench.py as the driver runs it) meets them every region: the candidate that is fastest on
          // their sum becomes the fifth grid.
-         {
-            hipEvent_t e0, e1;
-            HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-            auto t4 = [&](Real *A, Real *B, Real *C, Real *D) {
-               hipEventRecord(e0, s_main);
-               launch_probe(s_main, 0, Pass::of_grids(A, B, C, D), true);
-               hipEventRecord(e1, s_main); hipEventSynchronize(e1);
-               float ms = 0; hipEventElapsedTime(&ms, e0, e1);
-               return ms;
-            };
-            float best = 0;
-            const bool verbose = getenv("PFFDTD_VERBOSE") && atoi(getenv("PFFDTD_VERBOSE")) > 0;
-            for (Real *g : pool) {
-               if (g == u0 || g == u1 || g == bufD || g == bufE) continue;
-               const float ms = t4(u0, u1, g, bufD) + t4(g, bufD, u0, u1) + t4(bufD, bufE, g, u0) + t4(g, u0, bufD, bufE);
-               if (verbose) fprintf(stderr, "pffdtd_hip:   fifth grid candidate: %.3f ms over the four off-cycle launches\n", ms);
-               if (!bufC || ms < best) { best = ms; bufC = g; }
-            }
-            hipEventDestroy(e0); hipEventDestroy(e1);
+         Stopwatch sw;
+         HIPCHK(sw.err);
+         auto t4 = [&](Real *A, Real *B, Real *C, Real *D) { return sw.ms(s_main, 0, 1, [&] { launch_probe(s_main, 0, Pass::of_grids(A, B, C, D), true); }); };
+         float best = 0;
+         const bool verbose = getenv("PFFDTD_VERBOSE") && atoi(getenv("PFFDTD_VERBOSE")) > 0;
+         for (Real *g : pool) {
+            if (g == u0 || g == u1 || g == bufD || g == bufE) continue;
+            const float ms = t4(u0, u1, g, bufD) + t4(g, bufD, u0, u1) + t4(bufD, bufE, g, u0) + t4(g, u0, bufD, bufE);
+            if (verbose) fprintf(stderr, "pffdtd_hip:   fifth grid candidate: %.3f ms over the four off-cycle launches\n", ms);
+            if (!bufC || ms < best) { best = ms; bufC = g; }
          }
          if (!bufC) return set_err(PF_ERR_STATE, "placement search: no fifth grid left"); // (the pool holds the engine's five)
          keep.push_back(bufC); keep.push_back(bufD); keep.push_back(bufE);
       } else {
-      bufC = pool[w[2]]; bufD = pool[w[3]];
-      keep.push_back(bufC); keep.push_back(bufD);
+         bufC = pool[w[2]]; bufD = pool[w[3]];
+         keep.push_back(bufC); keep.push_back(bufD);
       }
-      for (Real *g : pool) {
-         own_list.erase(std::remove(own_list.begin(), own_list.end(), g), own_list.end());
-         if (std::find(keep.begin(), keep.end(), g) == keep.end()) hipFree(g);
-      }
-      for (Real *g : keep) {
-         own_list.push_back(g);
-         HIPCHK(hipMemsetAsync(g, 0, npad * sizeof(Real), s_main)); // (the pair kernel wrote zeros computed from zeros; be explicit)
-      }
+      mem.release_rest(pool, keep);
+      for (Real *g : keep) HIPCHK(hipMemsetAsync(g, 0, npad * sizeof(Real), s_main)); // (the pair kernel wrote zeros computed from zeros; be explicit)
+      HIPCHK(hipStreamSynchronize(s_main));
+      return PF_OK;
+   }
+   // the search over a caller's pool, from the members as offered; its launches wrote every member: all zeros again afterwards
+   int search_offered(const std::vector<Real *> &pool, int w[4]) {
+      const int first[4] = {0, 1, 2, 3};
+      const Restore<bool> probe(tb2_probe, true);
+      int rc = search_placement(pool, false, true, place_evals, first, w);
+      if (rc) return rc;
+      for (Real *g : pool) HIPCHK(hipMemsetAsync(g, 0, npad * sizeof(Real), s_main));
       HIPCHK(hipStreamSynchronize(s_main));
       return PF_OK;
    }
@@ -417,7 +349,8 @@
          for (int j = 0; j < i; j++) if (grids[i] == grids[j]) return set_err(PF_ERR_ARG, "pf_engine_place_grids: grid offered twice");
       }
       HIPCHK(hipSetDevice(op.device));
-      u0 = (Real *)grids[0]; u1 = (Real *)grids[1];
+      const std::vector<Real *> pool((Real *const *)grids, (Real *const *)grids + n);
+      u0 = pool[0]; u1 = pool[1];
       idx[0] = 0; idx[1] = 1; idx[2] = idx[3] = -1;
       if (five) idx[4] = -1;
       if (five && n >= 5 && tb3_geom && tb2_geom && !(op.slab_first && op.slab_last)) {
@@ -425,18 +358,8 @@
          tb2_slab = true;
          if (!(op.debug & PF_DBG_NO_WALL_REGIONS)) { int rcw = init_walls(true); if (rcw) return rcw; }
          if (wl_on) {
-            std::vector<Real *> pool;
-            for (int i = 0; i < n; i++) pool.push_back((Real *)grids[i]);
             int w[4] = {0, 1, 2, 3};
-            if (n > 5 && !(op.debug & PF_DBG_NO_AUTOTUNE)) {
-               const int first[4] = {0, 1, 2, 3};
-               tb2_probe = true;
-               int rc = search_placement(pool, false, true, place_evals(), first, w);
-               tb2_probe = false;
-               if (rc) return rc;
-               for (int i = 0; i < n; i++) HIPCHK(hipMemsetAsync(pool[i], 0, npad * sizeof(Real), s_main));
-               HIPCHK(hipStreamSynchronize(s_main));
-            }
+            if (n > 5 && !(op.debug & PF_DBG_NO_AUTOTUNE)) { int rc = search_offered(pool, w); if (rc) return rc; }
             int c = -1;
             for (int i = 0; i < n && c < 0; i++) if (i != w[0] && i != w[1] && i != w[2] && i != w[3]) c = i;
             u0 = pool[w[0]]; u1 = pool[w[1]]; bufD = pool[w[2]]; bufE = pool[w[3]]; bufC = pool[c];
@@ -451,8 +374,6 @@
       if (steps_done == 0) { int rcg = pairs_geometry(); if (rcg) return rcg; }
       if (n < 4 || !tb2_geom || (op.slab_first && op.slab_last)) { // keeps stepping singly: on the fastest pair of the pool
          if (n > 2 && place_single_ok()) {
-            std::vector<Real *> pool;
-            for (int i = 0; i < n; i++) pool.push_back((Real *)grids[i]);
             int bi, bj;
             int rc = search_pair(pool, bi, bj);
             if (rc) return rc;
@@ -461,18 +382,8 @@
          }
          return PF_OK;
       }
-      std::vector<Real *> pool;
-      for (int i = 0; i < n; i++) pool.push_back((Real *)grids[i]);
       int w[4] = {0, 1, 2, 3};
-      if (n > 4 && !(op.debug & PF_DBG_NO_AUTOTUNE)) {
-         const int first[4] = {0, 1, 2, 3};
-         tb2_probe = true;
-         int rc = search_placement(pool, false, true, place_evals(), first, w);
-         tb2_probe = false;
-         if (rc) return rc;
-         for (int i = 0; i < n; i++) HIPCHK(hipMemsetAsync(pool[i], 0, npad * sizeof(Real), s_main));
-         HIPCHK(hipStreamSynchronize(s_main));
-      }
+      if (n > 4 && !(op.debug & PF_DBG_NO_AUTOTUNE)) { int rc = search_offered(pool, w); if (rc) return rc; }
       u0 = pool[w[0]]; u1 = pool[w[1]]; bufC = pool[w[2]]; bufD = pool[w[3]];
       for (int i = 0; i < 4; i++) idx[i] = w[i];
       tb2_slab = true;
@@ -481,53 +392,44 @@
    }
    int autotune() {
       if (fcc) return autotune_fcc();
-      if (vbase != 0 || fcc || op.energy || (op.debug & PF_DBG_NO_AUTOTUNE) || !use_dpp || !(lean || vg)) return PF_OK;
+      if (vbase != 0 || op.energy || (op.debug & PF_DBG_NO_AUTOTUNE) || !use_dpp || !(lean || vg)) return PF_OK;
       if (Nx * Ny * Nz < ((int64_t)1 << 22)) return PF_OK; // tiny grids: launch-bound either way
-      Real *scr = bufC;
-      bool own = false;
-      int rc;
-      if (!scr) { scr = try_dzalloc<Real>(npad); if (!scr) return PF_OK; own = true; } // no room to measure: the static rules stand
-      hipEvent_t e0, e1;
-      HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+      Real *own = nullptr; // the scratch grid where there is no bufC to write to
+      Real *const scr = bufC ? bufC : (own = try_dzalloc<Real>(npad));
+      if (!scr) return PF_OK; // no room to measure: the static rules stand
+      Stopwatch sw;
+      HIPCHK(sw.err);
       HIPCHK(hipDeviceSynchronize());
-      auto timed = [&](auto &&fn) -> float {
-         fn();
-         hipEventRecord(e0, s_main);
-         for (int i = 0; i < 3; i++) fn();
-         hipEventRecord(e1, s_main);
-         hipEventSynchronize(e1);
-         float ms = 0;
-         hipEventElapsedTime(&ms, e0, e1);
-         return ms / 3;
-      };
-      const bool lean0 = lean, vg0 = vg;
+      auto timed = [&](auto &&fn) { return sw.ms(s_main, 1, 3, fn) / 3; };
       const Grids gs{u0, u1, scr}; // a single step into scratch: the state is not touched
-      lean = true; vg = false;
-      // the device has been idle while the host built the lists: ramp its clocks first (~20 ms of work), or the first
-      // candidate is measured -- and every launch here profiled -- at idle clocks (seen: +56 % per launch)
-      for (int i = 0; i < 8 && (double)i * (double)(Nx * Ny * Nz) < 8.0e9; i++) launch_air_lean(s_main, gs, 1, (int)Nx - 1);
-      HIPCHK(hipStreamSynchronize(s_main));
-      tune_ms[0] = timed([&] { launch_air_lean(s_main, gs, 1, (int)Nx - 1); });
-      lean = false; vg = true;
-      { // the barrier-free kernel, with 64 / 32 / 16 lanes per row segment where those pad the rows differently
-         constexpr int V = pf::VecOf<Real>::V;
-         int best_lw = 0;
-         int64_t seen[3] = {0, 0, 0};
-         int k = 0;
-         for (int lw : {64, 32, 16}) {
-            const int64_t w = cdiv(P, (int64_t)lw * V) * lw * V;
-            if (k > 0 && w == seen[k - 1]) continue; // same padded width as the wider segment: the wider one wins anyway
-            seen[k++] = w;
-            lw_force = lw;
-            const float t = timed([&] { launch_air_march(s_main, gs, 1, (int)Nx - 1); });
-            if (best_lw == 0 || t < 0.98f * tune_ms[1]) { tune_ms[1] = t; best_lw = lw; }
+      {
+         const Restore<bool> lean0(lean, true), vg0(vg, false); // (the launchers read them: back as they were after the two candidates)
+         // the device has been idle while the host built the lists: ramp its clocks first (~20 ms of work), or the first
+         // candidate is measured -- and every launch here profiled -- at idle clocks (seen: +56 % per launch)
+         for (int i = 0; i < 8 && (double)i * (double)(Nx * Ny * Nz) < 8.0e9; i++) launch_air_lean(s_main, gs, 1, (int)Nx - 1);
+         HIPCHK(hipStreamSynchronize(s_main));
+         tune_ms[0] = timed([&] { launch_air_lean(s_main, gs, 1, (int)Nx - 1); });
+         lean = false; vg = true;
+         { // the barrier-free kernel, with 64 / 32 / 16 lanes per row segment where those pad the rows differently
+            constexpr int V = pf::VecOf<Real>::V;
+            int best_lw = 0;
+            int64_t seen[3] = {0, 0, 0};
+            int k = 0;
+            for (int lw : {64, 32, 16}) {
+               const int64_t w = cdiv(P, (int64_t)lw * V) * lw * V;
+               if (k > 0 && w == seen[k - 1]) continue; // same padded width as the wider segment: the wider one wins anyway
+               seen[k++] = w;
+               lw_force = lw;
+               const float t = timed([&] { launch_air_march(s_main, gs, 1, (int)Nx - 1); });
+               if (best_lw == 0 || t < 0.98f * tune_ms[1]) { tune_ms[1] = t; best_lw = lw; }
+            }
+            lw_force = best_lw;
          }
-         lw_force = best_lw;
       }
-      lean = lean0; vg = vg0;
-      if (hipGetLastError() != hipSuccess) { lean = lean0; vg = vg0; }
-      else if (tune_ms[1] < 0.97f * tune_ms[0]) { lean = false; vg = true; }
-      else if (tune_ms[0] < 0.97f * tune_ms[1]) { lean = true; vg = false; }
+      if (hipGetLastError() == hipSuccess) { // (a failed launch: the static rules stand)
+         if (tune_ms[1] < 0.97f * tune_ms[0]) { lean = false; vg = true; }
+         else if (tune_ms[0] < 0.97f * tune_ms[1]) { lean = true; vg = false; }
+      }
       // a blocked pass from the state, its node values in the three buffers and the branch state into its other copy, as the wall regions of a slab step
       const Pass bp = pass_from_state(bufC, bufD, bufE, ub[1], ub[2], state_other());
       const Grids g1 = bp.grids(0), g2 = bp.grids(1);
@@ -565,7 +467,6 @@
       }
       if (tb2) {
          if (!(tune_ms[2] < pair_margin * std::min(tune_ms[0], tune_ms[1]))) { // not worth it: drop the blocked path and its extra grids
-            if (scr == bufC) scr = nullptr;
             drop_blocking();
          } else {
             HIPCHK(hipMemsetAsync(bufC, 0, npad * sizeof(Real), s_main));
@@ -574,7 +475,6 @@
          }
       }
       HIPCHK(hipDeviceSynchronize());
-      hipEventDestroy(e0); hipEventDestroy(e1);
-      if (own && scr) hipFree(scr);
+      mem.release(own);
       return PF_OK;
    }

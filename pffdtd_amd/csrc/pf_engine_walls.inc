@@ -28,8 +28,8 @@
       return wide_ok ? 3 : 0;
    }
    void free_walls() {
-      auto F = [](auto *&p) { if (p) hipFree((void *)p); p = nullptr; };
-      F(wl_pen); F(wl_rec); F(wl_rest); F(wl_blk); F(wl_brk); F(wl_binfo); F(wl_blos); F(vh1b); F(gh1b); F(ubx[0]); F(ubx[1]);
+      mem.release(wl_pen); mem.release(wl_rec); mem.release(wl_rest); mem.release(wl_blk); mem.release(wl_brk); mem.release(wl_binfo); mem.release(wl_blos);
+      mem.release(vh1b); mem.release(gh1b); mem.release(ubx[0]); mem.release(ubx[1]);
       wl_nbrk = 0; wl_brk_lds = 0; wl_ns3 = wl_ns3z = false; wl_uni = 0; wl_rcv = 0;
       for (int &p : wl_prof) p = 0;
       wl_xw[0] = wl_xw[1] = false;
