@@ -176,6 +176,8 @@ typedef struct pf_timing {
                                0: the guarded form ran (mixed counts, other counts) or no such region */
    int64_t wall_unread_skipped; /* triples: wall regions (bits as in wall_three_steps) that do not store u^{n+1} of their cells because nothing reads it:
                                no receiver in their cells, no tile or node that steps singly */
+   int64_t wall_strips_staged; /* triples: 1 = the column strips' three-step kernel moves its planes through LDS, so that memory sees whole rows
+                               (pf_strip_map.h: the bodies with a uniform branch count); 0: every lane loads and stores its own pencil, or no such strips */
    int64_t fcc_shell_bricks;/* air_variant 42: bricks this engine launches per pair (the whole 13-point shell, pf_brick_fcc.h); 0 otherwise */
 } pf_timing;
 

@@ -22,7 +22,8 @@ int pf__engine_create_x(const pf_simdata *sd, const pf_opts_x *o, pf_engine **ou
 enum : int {
    PF_DBG_BRANCH_SELECTS = 0x1,       // three-step wall regions: fd_regs' select form (a branch count per lane) even where every material has the same count
    PF_DBG_STORE_UNREAD = 0x2,         // three-step wall regions: u^{n+1} of their cells goes to the scratch grid even where nothing reads it
-   PF_DBG_RUNTIME_NODES = 0x20,       // three-step wall regions: the bodies that read the node words from their blocks, never the ones with a wall profile compiled in
+   PF_DBG_STRIPS_PER_LANE = 0x4,      // three-step column strips with a uniform branch count: every lane loads and stores its own pencil, no staging through LDS (pf_strip_map.h)
+   PF_DBG_RUNTIME_NODES = 0x20,      // three-step wall regions: the bodies that read the node words from their blocks, never the ones with a wall profile compiled in
    PF_DBG_LW32 = 0x100,               // 32-lane row segments (0x200: 16-lane, 0x400: 64-lane) instead of the measured choice
    PF_DBG_LW16 = 0x200,
    PF_DBG_LW64 = 0x400,

@@ -347,7 +347,9 @@ template <typename Real> struct Engine : EngineBase {
    // those cells); second: the x / y regions' second block list, the chunks of a two-step launch on three-step tables (init_walls: blk0b, mchunk2)
    struct WallChoice { const pf::WallKernel *k; bool skip_c, second; };
    WallChoice wall_choice(int gi, int q, int ns) const {
-      const pf::WallKernel *k = pf::wall_choose<sizeof(Real) == 8>(gi, q, ns, mb_max, wl_ns3, wl_ns3z, wl_geo[gi], wl_prof[gi], wl_uni);
+      // (the staged strip bodies reach into a plane with 32-bit byte offsets: planes of 2 GiB and more keep the per-lane form)
+      const bool per_lane = (op.debug & PF_DBG_STRIPS_PER_LANE) != 0 || plane * (int64_t)sizeof(Real) >= ((int64_t)1 << 31);
+      const pf::WallKernel *k = pf::wall_choose<sizeof(Real) == 8>(gi, q, ns, mb_max, wl_ns3, wl_ns3z, wl_geo[gi], wl_prof[gi], wl_uni, per_lane);
       return {k, k && k->ub > 0 && op.slab_first && op.slab_last && tb_ndirty == 0 && wl_nrest == 0 && !((wl_rcv >> gi) & 1u) && !(op.debug & (PF_DBG_STORE_UNREAD | PF_DBG_THIRD_STEP_LISTS)),
               gi == 0 && q == 0 && wl_ns3 && ns == 2 && wl_grp[0].nblkb > 0};
    }
@@ -1005,11 +1007,12 @@ template <typename Real> struct Engine : EngineBase {
       tm.wall_bricks = wl_on ? wl_nbrk : 0;
       tm.fcc_shell_bricks = fb_on ? fb_nbrk : 0;
       tm.wall_three_steps = (wl_on && (tb3 || (tb3_slab && slab_all3()))) ? (int)(wall_g3() | (wl_xw[0] ? 0x10u : 0u) | (wl_xw[1] ? 0x20u : 0u)) : 0;
-      tm.wall_profile = 0; tm.wall_uniform_branches = 0; tm.wall_unread_skipped = 0;
+      tm.wall_profile = 0; tm.wall_uniform_branches = 0; tm.wall_unread_skipped = 0; tm.wall_strips_staged = 0;
       for (int gi = 0; gi < 4; gi++) if ((tm.wall_three_steps >> gi) & 1) { // what a triple launches for the alike blocks of these groups
          const WallChoice c = wall_choice(gi, 0, 3);
          tm.wall_profile |= (int64_t)(c.k && c.k->pr > 0) << gi; tm.wall_unread_skipped |= (int64_t)c.skip_c << gi;
          if (c.k && c.k->ub > 0) tm.wall_uniform_branches = wl_uni;
+         if (c.k && c.k->vec && c.k->ub > 0 && !c.k->pl) tm.wall_strips_staged = 1;
       }
       if (t) *t = tm;
       if (reset) tm = pf_timing{};

@@ -252,9 +252,12 @@
       // The column strips.  A strip of up to 10 columns is one region with pencils of 12 cells; a wider one (a sliver of the box went
       // to it) has pencils of 20 cells (fp32; ~350 registers, one wave per SIMD).  Cutting such a strip in two -- the 7 columns next
       // to the face with the wall layers, 12-cell pencils, and the rest, plain air, 16-cell pencils without any node code, two
-      // waves per SIMD each -- was measured and LOSES (1024^3: 0.54 + 0.31 ms against 0.59 ms per pair; the strips' cost is the
-      // 64 separate lines behind every load and store instruction, not the occupancy): only where the wide pencils do not fit (odd
-      // widths, fp64) or with debug 0x2000000 (tests).
+      // waves per SIMD each -- was measured and LOSES (1024^3: 0.54 + 0.31 ms against 0.59 ms per pair): only where the wide pencils
+      // do not fit (odd widths, fp64) or with debug 0x2000000 (tests).  What that pointed at -- every load and store instruction of a
+      // strip reaches 64 separate lines, a lane per row -- is measured now: the three-step bodies with a uniform branch count move their
+      // tile row by row and turn rows into pencils in LDS (pf_strip_map.h, pf_wall.h STG), and the strip launch of a 1024^3 triple fell
+      // from 393-406 to 337-353 us (medians of three processes each, profiles/strips_staged.txt).  A part of the gap to the x / y
+      // regions, not all of it: the strips' 18 cells of air update per stage and their 170 accumulation registers stay.
       int zb = 0;
       bool zok = true;
       { // low side
@@ -520,7 +523,8 @@
          }
       }
       wl_ns3 = ns3; wl_ns3z = ns3z;
-      if ((ns3 && wl_grp[0].nblk[1] > 0) || (ns3z && wl_grp[3].nblk[1] > 0)) { // some x / y block is not alike (a room that is no plain box): those regions keep two steps + one
+      if ((ns3 && wl_grp[0].nblk[1] > 0) || (ns3z && (wl_grp[3].nblk[1] > 0 || wl_grp[3].nblk[2] > 0))) { // some block is not alike (a room that is no plain box), or a strip block holds
+         // no node (the three-step strip launch takes list 0 only: list 2 would go unstepped): those regions keep two steps + one
          wl_no_ns3 = true;
          return init_walls(slab);
       }

@@ -41,6 +41,7 @@
 #include <type_traits>
 #include <utility>
 #include "pf_kernels.h"
+#include "pf_strip_map.h"
 
 namespace pf {
 
@@ -264,14 +265,21 @@ template <int B, int E, typename F> __device__ __forceinline__ void wall_static_
 // UB > 0 (bodies with a frequency-dependent wall profile only): the scene's materials all have the same number of branches -- UB of them,
 // or (USK) wp.mmax <= UB of them -- : fd_regs' uniform form, UB slots of branch state per node fetched, rotated and stored, and u^{n+1} of the owned
 // cells is stored only where the host passes a grid for it (wp.C: null when nobody reads it, Engine::wall_choice).
+// STG (= the column strips' bodies with UB > 0, unless PL): staged loads and stores.  A lane of a strip owns a pencil along z and the lanes run along y, so
+// every vector load and store of the per-lane form reaches 64 rows, 16 bytes of a line each.  The staged body issues the same addresses row by row --
+// instruction i, lane l moves element 64 i + l of the 64 x DP tile, consecutive lanes consecutive 16 bytes (pf_strip_map.h) --, keeps what it prefetched in that
+// order (Bq, Aq), and turns rows into pencils, and the pencils it stores into rows, through tiles in LDS at the rotation of the march step.  The same cells in
+// the same arithmetic: the same bits.
 template <typename Real, int DP, int MODE, bool FAST, bool NODES, int MC, bool SG, int NS = 2, int GD = 0, bool HI = false, int PR = 0, int UB = 0, bool USK = false,
-          typename LDS = WallLds<Real>>
+          typename LDS = WallLds<Real>, bool PL = false>
 __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const WallRegion &R, const int j, const int c, const Real a1, const Real a2,
-                                          const LDS *ldsp, const uint32_t dsx, const uint32_t dsz, const uint32_t dsw, WallJobs<Real> *jobs = nullptr) {
+                                          const LDS *ldsp, const uint32_t dsx, const uint32_t dsz, const uint32_t dsw, WallJobs<Real> *jobs = nullptr, void *stg = nullptr) {
    constexpr bool VEC = MODE == 2;
    typedef typename VecOf<Real>::type vec;
    constexpr int V = VecOf<Real>::V;
    static_assert(!VEC || DP % V == 0, "vector pencils hold whole vectors");
+   constexpr bool STG = VEC && UB > 0 && !PL; // the staged strip body (pf_strip_map.h)
+   constexpr int NVT = VEC ? DP / V : 1;      // vectors per row of the tile
    const int lane = threadIdx.x;
    constexpr bool mx = MODE != 0;                                  // the march axis is x
    const int NL = VEC ? wp.Ny : wp.Nz;                             // extent of the lane axis
@@ -317,12 +325,63 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
    const int64_t lbase = (int64_t)lsrc * sl + (int64_t)rnbase * sn;
    const int ql = (lc == 1 || lc == NL - 2) ? 1 : 0;
    const bool tile_ql = !FAST && __ballot(ql != 0) != 0ull;
+   // STG: the planes cross LDS between the rows' order, in which memory is reached, and the pencils' (pf_strip_map.h).  Four tiles: u^n and u^{n-1} coming in,
+   // two fields going out -- one fence per march step between everything written and everything read; a block is one wave and LDS serves a wave's
+   // instructions in order.  sln = the lane, made opaque once per march step: the places in the tiles and the store map are a few instructions from it and
+   // stay in the step, instead of half a dozen more registers living through the loop.
+   const int tl0 = R.l0 - hl + lt * j; // lane-axis coordinate of the tile's row 0
+   int sln = lane;
+   // lob: where load instruction i reaches into a plane, in bytes -- its element's vector, in the source row of its element's row.  The same in every march step,
+   // and a division and two reflections each: worked out once, parked in LDS beside the tiles and fetched back ahead of a step's loads (five registers live through
+   // the march loop otherwise, in a kernel that has none to spare).
+   uint32_t lob[NVT];
+#pragma unroll
+   for (int i = 0; i < NVT; i++) {
+      const int e = strip_elem(i, lane);
+      lob[i] = STG ? (uint32_t)(strip_lane_src(tl0 + strip_row(e, NVT), NL) * wp.P + strip_vec(e, NVT) * V) * (uint32_t)sizeof(Real) : 0u;
+   }
+   vec *const T0 = (vec *)stg;
+   constexpr int TV = strip_lds_vectors(NVT); // vectors per tile
+   uint32_t *const LOB = (uint32_t *)(T0 + 4 * TV);
+   if constexpr (STG) {
+#pragma unroll
+      for (int i = 0; i < NVT; i++) LOB[i * STRIP_ROWS + lane] = lob[i];
+   }
+   constexpr int SQ0 = strip_q0(HI ? DP - GD : 1, V), SNVO = strip_nvo(HI ? DP - GD : 1, HI ? DP - 1 : GD, V); // the vectors a store writes (STG: constant geometry)
+   static_assert(!STG || (GD > 0 && SNVO >= 1 && SQ0 + SNVO <= NVT), "staged strips: the owned vectors lie in the pencil");
+   auto stage_put = [&](vec *T, const Real(&b)[DP]) __attribute__((always_inline)) { // mapped form -> LDS, element order
+#pragma unroll
+      for (int i = 0; i < NVT; i++) {
+         vec t;
+#pragma unroll
+         for (int q = 0; q < V; q++) t[q] = b[i * V + q];
+         T[strip_lds_elem(strip_elem(i, sln))] = t;
+      }
+   };
+   auto stage_get = [&](const vec *T, Real(&b)[DP]) __attribute__((always_inline)) { // LDS -> this lane's pencil
+#pragma unroll
+      for (int v = 0; v < NVT; v++) {
+         const vec t = T[strip_lds_pencil(sln, v, NVT)];
+#pragma unroll
+         for (int q = 0; q < V; q++) b[v * V + q] = t[q];
+      }
+   };
 
    // Loads are unconditional (a cell outside [kb0, kb1) re-reads the nearest one inside) and nothing touches what they return
    // before the end of the march step: the mirror of the ghost cell and the masking of the entries happen at the rotation.
    auto load_pencil = [&](const Real *G, int m, Real(&b)[DP]) __attribute__((always_inline)) {
       const Real *pl = G + (int64_t)msrc(m) * sm + lbase;
-      if constexpr (VEC) {
+      if constexpr (STG) { // the plane in MAPPED form: b[i V ..] = element 64 i + lane of the tile, 16 consecutive bytes of one row per lane
+         // (a wave-uniform base and a 32-bit byte offset within the plane per lane -- the host checks that a plane is no longer, Engine::wall_choice --: one address
+         // register per instruction, the same for both grids)
+         const char *pr = (const char *)(G + (int64_t)msrc(m) * sm + (int64_t)rnbase * sn);
+#pragma unroll
+         for (int i = 0; i < NVT; i++) {
+            const vec t = *(const vec *)(pr + lob[i]);
+#pragma unroll
+            for (int q = 0; q < V; q++) b[i * V + q] = t[q];
+         }
+      } else if constexpr (VEC) {
 #pragma unroll
          for (int v = 0; v < DP / V; v++) {
             const vec t = *(const vec *)(pl + v * V);
@@ -370,6 +429,35 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
          for (int k = 0; k < DP; k++)
             if (k >= rko0 && k < rko1) pl[(int64_t)k * sn] = v[k];
       }
+   };
+   // STG: store_pencil in two halves.  Every lane parks the vectors of its pencil a store writes (store_pencil's own pad rule applied) ...
+   auto stage_put_owned = [&](vec *T, const Real(&v)[DP]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int q = SQ0; q < SQ0 + SNVO; q++) {
+         vec t;
+#pragma unroll
+         for (int i = 0; i < V; i++) t[i] = (rkg > 0 && q * V + i > rkg) ? Real(0) : v[q * V + i];
+         T[strip_lds_pencil(sln, q, NVT)] = t;
+      }
+   };
+   // ... and instruction i, lane l stores element 64 i + l of the tile's owned vectors, row by row: whole runs of 4 V bytes of a row, where the row is an owned
+   // one.  The places are the same for every field a march step stores (store_map: once per step), and the tiles are read before anything is stored:
+   // one LDS round trip per step, not one per instruction.
+   const int nown = strip_owned_rows(tl0, hl, R.l1);
+   // (a whole number of rows per instruction: instruction i is instruction 0 moved on by RPI rows -- one place in the plane and one in the tile per lane, the
+   // rest compile-time and wave-uniform steps)
+   static_assert(!STG || STRIP_ROWS % SNVO == 0, "staged strips: a store instruction covers whole rows");
+   constexpr int RPI = STG ? STRIP_ROWS / SNVO : 1;
+   struct StoreMap { uint32_t ob; int at, row; };
+   auto store_map = [&]() __attribute__((always_inline)) {
+      const int row = strip_row(strip_elem(0, sln), SNVO), q = SQ0 + strip_vec(strip_elem(0, sln), SNVO);
+      return StoreMap{(uint32_t)((tl0 + row) * wp.P + q * V) * (uint32_t)sizeof(Real), strip_lds_pencil(row, q, NVT), row};
+   };
+   auto store_rows = [&](Real *G, int m, const StoreMap &s, const vec (&t)[SNVO]) __attribute__((always_inline)) {
+      char *pr = (char *)(G + (int64_t)m * sm + (int64_t)rnbase * sn);
+#pragma unroll
+      for (int i = 0; i < SNVO; i++)
+         if (strip_row_owned(s.row + i * RPI, hl, nown)) *(vec *)(pr + (int64_t)(i * RPI) * sl * (int64_t)sizeof(Real) + s.ob) = t[i];
    };
    // the branch state and parameters of a pencil's first frequency-dependent node, ahead of its stage 1
    auto fd_fetch = [&](const uint4 E, Real(&v)[12], Real(&g)[12], Real &sf, Real &u2, Real &x1v, int32_t &k) __attribute__((always_inline)) {
@@ -644,6 +732,12 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
    load_pencil(wp.B, mf, Bc);
    load_pencil(wp.B, mf + 1, Bn);
    load_pencil(wp.A, mf, Ac);
+   if constexpr (STG) { // (the four planes the first march step starts from: through the tiles at once)
+      stage_put(T0, Bm); stage_put(T0 + TV, Bc); stage_put(T0 + 2 * TV, Bn); stage_put(T0 + 3 * TV, Ac);
+      __syncthreads();
+      stage_get(T0, Bm); stage_get(T0 + TV, Bc); stage_get(T0 + 2 * TV, Bn); stage_get(T0 + 3 * TV, Ac);
+      __syncthreads();
+   }
    mirror(Bm); mirror(Bc); mirror(Bn);
    fd_fetch(Ec, F1v, F1g, F1sf, F1u2, F1x1, F1k);
 #pragma unroll
@@ -659,6 +753,7 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
    fd_fetch(En, Fqv, Fqg, Fqsf, Fqu2, Fqx1, Fqk);
    for (int m = mf; m <= ml; m++) {
       usx = dsx; usz = dsz; usw = dsw;
+      if constexpr (STG) asm volatile("" : "+v"(sln));
       if constexpr (PN) {} // (nothing to hide: the words are constants)
       else if constexpr (CG) asm volatile("" : "+s"(usx), "+s"(usz), "+s"(usw));
       else {
@@ -699,19 +794,54 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
       // Rotate.  What was loaded a march step ago is touched HERE, before anything is stored: gfx9 counts loads and stores in one
       // in-order counter, so a wait for those loads placed after this step's stores would wait for the stores as well (and
       // without the touch the copies below are mere renamings: the first real use, and the wait, would be in the next step).
+      const bool s2 = do2 && own_m2;
+      if constexpr (STG) {
+         // The staged strips: what was loaded is in the rows' order and goes to the tiles HERE (the wait for the loads), and with it whatever this march step
+         // stores; one fence between all that is written and all that is read.  (The fence before: the tiles' readers of the last march step are done -- long ago.)
 #pragma unroll
-      for (int k = 0; k < DP; k++) { Vm[k] = Vc[k]; Vc[k] = Vn[k]; Bm[k] = Bc[k]; Bc[k] = Bn[k]; Bn[k] = Bq[k]; Ac[k] = Aq[k]; }
+         for (int k = 0; k < DP; k++) { Vm[k] = Vc[k]; Vc[k] = Vn[k]; Bm[k] = Bc[k]; Bc[k] = Bn[k]; }
+         __syncthreads();
+         stage_put(T0, Bq); stage_put(T0 + TV, Aq);
+         if (s2) stage_put_owned(T0 + 2 * TV, W);
+         if (do3) stage_put_owned(T0 + 3 * TV, Y);
+         __syncthreads();
+      } else {
 #pragma unroll
-      for (int k = 0; k < DP; k++) { asm volatile("" : "+v"(Bn[k])); asm volatile("" : "+v"(Ac[k])); }
+         for (int k = 0; k < DP; k++) { Vm[k] = Vc[k]; Vc[k] = Vn[k]; Bm[k] = Bc[k]; Bc[k] = Bn[k]; Bn[k] = Bq[k]; Ac[k] = Aq[k]; }
+#pragma unroll
+         for (int k = 0; k < DP; k++) { asm volatile("" : "+v"(Bn[k])); asm volatile("" : "+v"(Ac[k])); }
+      }
 #pragma unroll
       for (int q = 0; q < NQ; q++) { asm volatile("" : "+v"(Fqv[q])); asm volatile("" : "+v"(Fqg[q])); }
       asm volatile("" : "+v"(Fqsf), "+v"(Fqu2), "+v"(Fqx1), "+v"(Fqk), "+v"(Eq.x), "+v"(Eq.y), "+v"(Eq.z), "+v"(Eq.w) : : "memory");
-      mirror(Bn);
+      if constexpr (!STG) mirror(Bn);
       // the stores of this march step ...
-      if constexpr (UB > 0) { if (own_m && wp.C) store_pencil(wp.C, m, Vc); } // (u^{n+1} of the region: only where somebody reads it)
-      else if (own_m) store_pencil(wp.C, m, Vc);
-      if (do2 && own_m2) store_pencil(wp.D, m - 1, W);
-      if constexpr (NS == 3) { if (do3) store_pencil(wp.E, m - 2, Y); }
+      if constexpr (STG) {
+         // (staged: u^{n+2}, u^{n+3} from the tiles they were parked in above, and only then the pencils of u^n and u^{n-1} read back -- the rows on their way out
+         // use the registers those will take, and nothing waits for the pencils here: LDS has a counter of its own, the next march step is their first use --;
+         // u^{n+1}, where somebody reads it, through a tile of its own turn after that)
+         const StoreMap sm_ = store_map();
+         vec td[SNVO], te[SNVO];
+#pragma unroll
+         for (int i = 0; i < SNVO; i++) { td[i] = T0[2 * TV + sm_.at + i * RPI * NVT]; te[i] = T0[3 * TV + sm_.at + i * RPI * NVT]; } // (both tiles, whether or not this step stores both: no branch around a read)
+         if (s2) store_rows(wp.D, m - 1, sm_, td);
+         if (do3) store_rows(wp.E, m - 2, sm_, te);
+         stage_get(T0, Bn); stage_get(T0 + TV, Ac);
+         mirror(Bn);
+         if (own_m && wp.C) {
+            __syncthreads();
+            stage_put_owned(T0 + 2 * TV, Vc);
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < SNVO; i++) td[i] = T0[2 * TV + sm_.at + i * RPI * NVT];
+            store_rows(wp.C, m, sm_, td);
+         }
+      } else {
+         if constexpr (UB > 0) { if (own_m && wp.C) store_pencil(wp.C, m, Vc); } // (u^{n+1} of the region: only where somebody reads it)
+         else if (own_m) store_pencil(wp.C, m, Vc);
+         if (do2 && own_m2) store_pencil(wp.D, m - 1, W);
+         if constexpr (NS == 3) { if (do3) store_pencil(wp.E, m - 2, Y); }
+      }
       if (st1) wp.o1[li1] = nv1;
       if (NS == 1 && st1) { // one step: the state after stage 1 is the state
 #pragma unroll
@@ -752,6 +882,10 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
       if (m + 1 <= ml) {
          Eq = load_ent(m + 3);
          if (m + 1 < ml) {
+            if constexpr (STG) {
+#pragma unroll
+               for (int i = 0; i < NVT; i++) lob[i] = LOB[i * STRIP_ROWS + sln];
+            }
             load_pencil(wp.B, m + 3, Bq);
             load_pencil(wp.A, m + 2, Aq);
             fd_fetch(En, Fqv, Fqg, Fqsf, Fqu2, Fqx1, Fqk);
@@ -769,7 +903,10 @@ __device__ __forceinline__ void wall_body(const WallParams<Real> &wp, const Wall
 // SG: the reference GPU engine's safeguarded arithmetic (pf_kernels.h: upd7 / upd_rigid / abc_loss<true>) instead of the C CPU engine's.
 // PR: the wall profile of the launch's blocks (with GD > 0; 0: their node structure arrives with the block).
 // UB / USK: the uniform-branch-count bodies (wall_body; PR = 1 only), their coefficient table in LDS prepared here.
-template <typename Real, int DP, bool VEC, bool FAST, bool NODES = true, int MC = 12, bool SG = false, int NS = 2, int GD = 0, int PR = 0, int UB = 0, bool USK = false>
+// PL (strips with UB > 0 only): their per-lane form -- every lane loads and stores its own pencil, as every other strip body does -- instead of the staged
+// one (debug switch PF_DBG_STRIPS_PER_LANE: tests, A/B measurements).
+template <typename Real, int DP> struct StripTiles { alignas(16) Real t[4][STRIP_ROWS * DP]; uint32_t ob[DP / VecOf<Real>::V][STRIP_ROWS]; }; // (pf_strip_map.h: u^n, u^{n-1} in, two fields out; wall_body: lob)
+template <typename Real, int DP, bool VEC, bool FAST, bool NODES = true, int MC = 12, bool SG = false, int NS = 2, int GD = 0, int PR = 0, int UB = 0, bool USK = false, bool PL = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FAST && !VEC && NS != 3 && sizeof(Real) == 4) ? 2 : 1))) void k_wall2(WallParams<Real> wp, Real a1, Real a2) {
    static_assert(FAST || NODES, "generic blocks have everything");
    const uint4 bd = wp.blk[blockIdx.x];
@@ -779,6 +916,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FAST && !VE
    __shared__ LDS lds;
    __shared__ typename std::conditional<FAST, int, WallJobs<Real>>::type jobs_mem; // (generic blocks only)
    WallJobs<Real> *jobs = nullptr;
+   constexpr bool STG = VEC && UB > 0 && !PL; // the staged strip bodies: four tiles for the planes on their way between rows and pencils
+   static_assert(!PL || (VEC && UB > 0), "per-lane strips: the alternative of the staged bodies only");
+   __shared__ typename std::conditional<STG, StripTiles<Real, DP>, int>::type stg_mem;
+   void *stg = nullptr;
+   if constexpr (STG) stg = &stg_mem;
    if constexpr (!FAST) {
       jobs = &jobs_mem;
       jobs->mask[threadIdx.x] = 0u;
@@ -795,19 +937,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FAST && !VE
    static_assert(PR == 0 || GD > 0, "wall profiles: with constant pencil geometry");
    if constexpr (GD > 0) { // constant pencil geometry: a low-side and a high-side body
       const bool hi = R.kg != 0;
-      if constexpr (VEC) { if (hi) wall_body<Real, DP, 2, FAST, NODES, MC, SG, NS, GD, true, PR, UB, USK, LDS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
-                           else wall_body<Real, DP, 2, FAST, NODES, MC, SG, NS, GD, false, PR, UB, USK, LDS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs); }
-      else if (R.mode == 1) { if (hi) wall_body<Real, DP, 1, FAST, NODES, MC, SG, NS, GD, true, PR, UB, USK, LDS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
-                              else wall_body<Real, DP, 1, FAST, NODES, MC, SG, NS, GD, false, PR, UB, USK, LDS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs); }
-      else { if (hi) wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS, GD, true, PR, UB, USK, LDS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
-             else wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS, GD, false, PR, UB, USK, LDS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs); }
+      if constexpr (VEC) { if (hi) wall_body<Real, DP, 2, FAST, NODES, MC, SG, NS, GD, true, PR, UB, USK, LDS, PL>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs, stg);
+                           else wall_body<Real, DP, 2, FAST, NODES, MC, SG, NS, GD, false, PR, UB, USK, LDS, PL>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs, stg); }
+      else if (R.mode == 1) { if (hi) wall_body<Real, DP, 1, FAST, NODES, MC, SG, NS, GD, true, PR, UB, USK, LDS, PL>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs, stg);
+                              else wall_body<Real, DP, 1, FAST, NODES, MC, SG, NS, GD, false, PR, UB, USK, LDS, PL>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs, stg); }
+      else { if (hi) wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS, GD, true, PR, UB, USK, LDS, PL>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs, stg);
+             else wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS, GD, false, PR, UB, USK, LDS, PL>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs, stg); }
    } else if constexpr (VEC) wall_body<Real, DP, 2, FAST, NODES, MC, SG, NS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
    else if (R.mode == 1) wall_body<Real, DP, 1, FAST, NODES, MC, SG, NS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
    else wall_body<Real, DP, 0, FAST, NODES, MC, SG, NS>(wp, R, j, c, a1, a2, &lds, bd.y, bd.z, bd.w, jobs);
 }
 
 // ---------------- which k_wall2 runs: the instantiations (one table), the choice among them, the launch ----------------
-struct WallKernel { int dp = 0; bool vec = false, fast = false, nodes = false; int mc = 0, ns = 0, gd = 0, pr = 0, ub = 0; bool usk = false; }; // k_wall2's template arguments after Real, SG apart (every row exists with both)
+struct WallKernel { int dp = 0; bool vec = false, fast = false, nodes = false; int mc = 0, ns = 0, gd = 0, pr = 0, ub = 0; bool usk = false, pl = false; }; // k_wall2's template arguments after Real, SG apart (every row exists with both)
 constexpr int WALL_MC[2] = {4, 12}; // the bounds of a scene's largest branch count the kernels exist for (MC of k_wall2 and k_brick), and the one that serves a count:
 constexpr int wall_mc(int mb_max) { return mb_max <= WALL_MC[0] ? WALL_MC[0] : WALL_MC[1]; }
 // What the library instantiates, said here and nowhere else.  Launch groups (Engine::WlGroup): 0 = the x / y regions, strided pencils of 8 cells, 10 with
@@ -815,7 +957,7 @@ constexpr int wall_mc(int mb_max) { return mb_max <= WALL_MC[0] ? WALL_MC[0] : W
 constexpr int WALL_DP[4] = {8, 12, 16, 20}, WALL_DP3 = 10;
 template <int N> struct WallKernelTable { WallKernel k[N]; int n = 0; static constexpr int cap = N; constexpr void add(const WallKernel &w) { k[n++] = w; } };
 template <bool F64> constexpr auto wall_kernels() {
-   WallKernelTable<F64 ? 28 : 60> t{};
+   WallKernelTable<F64 ? 28 : 63> t{};
    for (int gi = 0; gi < (F64 ? 3 : 4); gi++) for (int mc : WALL_MC) {
       const int dp = WALL_DP[gi], d3 = gi == 0 ? WALL_DP3 : dp, gd = gi == 0 ? 6 : 16; const bool vec = gi != 0, lo = mc == WALL_MC[0];
       for (int ns = 1; ns <= 2; ns++) { // one or two steps per pass: alike and generic blocks; strips: alike blocks free of nodes too (no branch state moves: one MC)
@@ -829,20 +971,24 @@ template <bool F64> constexpr auto wall_kernels() {
       t.add({d3, vec, true, true, mc, 3}); t.add({d3, vec, true, true, mc, 3, gd}); t.add({d3, vec, true, true, mc, 3, gd, 1});
       if (lo) { t.add({d3, vec, true, true, mc, 3, gd, 2}); t.add({d3, vec, true, true, mc, 3, gd, 1, mc, true}); }
       else { t.add({d3, vec, true, true, mc, 3, gd, 1, 11}); t.add({d3, vec, true, true, mc, 3, gd, 1, 12}); }
+      // (the strips' uniform bodies are the staged ones, pf_strip_map.h; each once more in the per-lane form)
+      if (vec && lo) t.add({d3, vec, true, true, mc, 3, gd, 1, mc, true, true});
+      else if (vec) { t.add({d3, vec, true, true, mc, 3, gd, 1, 11, false, true}); t.add({d3, vec, true, true, mc, 3, gd, 1, 12, false, true}); }
    }
    return t;
 }
 template <bool F64> inline constexpr auto WALL_KERNELS = wall_kernels<F64>();
 // The choice (a row; null: nothing is launched), a function of what Engine::init_walls found: launch group gi, block list q (0 alike, 1 generic, 2 alike and free of nodes), ns
 // steps in this pass; mb_max: the scene's largest branch count; ns3 / ns3z: the x / y regions / the strips have three-step tables; geo, prof, uni: the box margin / wall profile
-// / branch count all the group's pencils / all materials share (0: none).  Of the rows for these pencils, list and steps the one with most of the facts compiled in.
-template <bool F64> constexpr const WallKernel *wall_choose(int gi, int q, int ns, int mb_max, bool ns3, bool ns3z, int geo, int prof, int uni) {
+// / branch count all the group's pencils / all materials share (0: none); per_lane: the strips' uniform bodies in their per-lane form, not the staged one.  Of the rows
+// for these pencils, list and steps the one with most of the facts compiled in.
+template <bool F64> constexpr const WallKernel *wall_choose(int gi, int q, int ns, int mb_max, bool ns3, bool ns3z, int geo, int prof, int uni, bool per_lane = false) {
    constexpr auto &T = WALL_KERNELS<F64>;
    if (ns == 3 && !(gi == 0 ? ns3 : gi == 3 && ns3z)) return nullptr; // three steps per pass: on three-step tables only
    const int dp = gi == 0 && ns3 ? WALL_DP3 : WALL_DP[gi];
    const WallKernel *best = nullptr; int most = -1;
    for (const WallKernel &r : T.k) {
-      if (r.dp != dp || r.ns != ns || r.fast != (q != 1) || r.nodes != (q != 2)) continue;
+      if (r.dp != dp || r.ns != ns || r.fast != (q != 1) || r.nodes != (q != 2) || (r.vec && r.ub > 0 && r.pl != per_lane)) continue;
       const bool bound = r.nodes && r.ub == 0 && !(r.pr > 0 && !WALL_PROFILES[r.pr - 1].fd); // is MC the bound of the branch state the row moves?  (else: none moves, or UB is)
       const int facts = (r.gd > 0) + (r.pr > 0) + (r.ub > 0);
       if ((r.gd == 0 || r.gd == geo) && (r.pr == 0 || r.pr == prof) && (r.ub == 0 || (uni > 0 && (r.usk ? uni <= r.ub : uni == r.ub))) && (!bound || r.mc == wall_mc(mb_max)) && facts > most) { best = &r; most = facts; }
@@ -864,8 +1010,10 @@ template <bool F64> constexpr bool wall_choices_match_table() {
       const bool none = t3 ? (F64 || q != 0 || ns == 1) : (ns == 3 || (gi == 0 && q == 2) || (F64 && gi == 3));
       for (int mb = 0; mb <= WALL_MC[1]; mb++) for (int uni = 0; mv[mb] && uni <= (ns == 3 ? mb : 0); uni += mb ? mb : 1)
          for (int geo = 0; geo <= (ns == 3 ? WALL_DP[3] : 0); geo++) for (int prof = 0; gv[geo] && prof <= (ns == 3 ? WALL_NPROF : 0); prof++) {
-            const WallKernel *k = wall_choose<F64>(gi, q, ns, mb, t > 0, t > 1, geo, prof, uni);
-            if (none != !k) return false; else if (k) hit[k - T.k] = true;
+            for (int pl = 0; pl < (gi == 3 && ns == 3 ? 2 : 1); pl++) { // (both forms of the strips' uniform bodies: three-step strip launches only)
+               const WallKernel *k = wall_choose<F64>(gi, q, ns, mb, t > 0, t > 1, geo, prof, uni, pl != 0);
+               if (none != !k || (k && k->pl && !pl)) return false; else if (k) hit[k - T.k] = true;
+            }
          }
    }
    for (bool h : hit) if (!h) return false; // (a table that is not full: rows nobody chooses)
@@ -876,6 +1024,6 @@ static_assert(wall_choices_match_table<true>(), "k_wall2, fp64: the chooser and 
 // launches row k of its precision's table (null: nothing)
 template <typename Real, bool SG, int... I> void wall_launch(const WallKernel *k, dim3 grid, hipStream_t st, const WallParams<Real> &wp, Real a1, Real a2, std::integer_sequence<int, I...>) {
    constexpr auto &T = WALL_KERNELS<sizeof(Real) == 8>;
-   (void)((k == &T.k[I] && (k_wall2<Real, T.k[I].dp, T.k[I].vec, T.k[I].fast, T.k[I].nodes, T.k[I].mc, SG, T.k[I].ns, T.k[I].gd, T.k[I].pr, T.k[I].ub, T.k[I].usk><<<grid, dim3(64), 0, st>>>(wp, a1, a2), true)) || ...);
+   (void)((k == &T.k[I] && (k_wall2<Real, T.k[I].dp, T.k[I].vec, T.k[I].fast, T.k[I].nodes, T.k[I].mc, SG, T.k[I].ns, T.k[I].gd, T.k[I].pr, T.k[I].ub, T.k[I].usk, T.k[I].pl><<<grid, dim3(64), 0, st>>>(wp, a1, a2), true)) || ...);
 }
 } // namespace pf

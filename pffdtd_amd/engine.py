@@ -45,6 +45,7 @@ class PfTiming(ctypes.Structure):
                 ("tb2_dirty_tiles", ctypes.c_int64), ("place_candidates", ctypes.c_int64), ("place_ms", ctypes.c_double * 3),
                 ("wall_blocks", ctypes.c_int64 * 2), ("tb_steps_per_pass", ctypes.c_int64), ("wall_bricks", ctypes.c_int64), ("wall_three_steps", ctypes.c_int64),
                 ("wall_profile", ctypes.c_int64), ("wall_uniform_branches", ctypes.c_int64), ("wall_unread_skipped", ctypes.c_int64),
+                ("wall_strips_staged", ctypes.c_int64),
                 ("fcc_shell_bricks", ctypes.c_int64)]
 
 
@@ -476,7 +477,7 @@ class HipEngine:
                 "tune_ms": list(t.tune_ms), "air_path": t.air_path, "tb2_lw": t.tb2_lw, "tb2_dirty_tiles": t.tb2_dirty_tiles,
                 "place_candidates": t.place_candidates, "place_ms": list(t.place_ms), "wall_blocks": list(t.wall_blocks),
                 "tb_steps_per_pass": t.tb_steps_per_pass, "wall_bricks": t.wall_bricks, "wall_three_steps": t.wall_three_steps, "wall_profile": t.wall_profile,
-                "wall_uniform_branches": t.wall_uniform_branches, "wall_unread_skipped": t.wall_unread_skipped,
+                "wall_uniform_branches": t.wall_uniform_branches, "wall_unread_skipped": t.wall_unread_skipped, "wall_strips_staged": t.wall_strips_staged,
                 "fcc_shell_bricks": t.fcc_shell_bricks}
 
     def set_timing(self, on):

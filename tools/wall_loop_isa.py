@@ -29,6 +29,7 @@ csrc = Path(args.csrc)
 header = (csrc / "pf_wall.h").read_text()
 profiles = "int PR" in header  # (wall profiles: a trailing template parameter)
 uniform = "int UB" in header   # (uniform branch counts: two more)
+per_lane = "bool PL" in header # (the strips' uniform bodies are staged through LDS; PL = true: their per-lane form)
 
 # (Real, DP, VEC, FAST, NODES, MC, SG, NS, GD[, PR[, UB, USK]])
 kernels = []
@@ -41,6 +42,10 @@ for dp, vec, gd in ((10, "false", 6), (20, "true", 16)):
         kernels.append(f"float, {dp}, {vec}, true, true, 12, false, 3, {gd}, 1, 11, false")
         kernels.append(f"float, {dp}, {vec}, true, true, 12, false, 3, {gd}, 1, 12, false")
         kernels.append(f"float, {dp}, {vec}, true, true, 4, false, 3, {gd}, 1, 4, true")
+    if per_lane and vec == "true":
+        kernels.append(f"float, {dp}, {vec}, true, true, 12, false, 3, {gd}, 1, 11, false, true")
+        kernels.append(f"float, {dp}, {vec}, true, true, 12, false, 3, {gd}, 1, 12, false, true")
+        kernels.append(f"float, {dp}, {vec}, true, true, 4, false, 3, {gd}, 1, 4, true, true")
 src = '#include "pf_wall.h"\n' + "".join(f"template __global__ void pf::k_wall2<{k}>(pf::WallParams<float>, float, float);\n" for k in kernels)
 
 with tempfile.TemporaryDirectory() as d:
@@ -110,9 +115,11 @@ for line in text:
     funcs[cur]["lines"].append(line)
 
 names = subprocess.run(["c++filt"] + list(funcs), capture_output=True, text=True, stdin=subprocess.DEVNULL).stdout.splitlines()
-print("march loop of k_wall2<float, DP, VEC, FAST, NODES, MC, SG, NS, GD" + (", PR" if profiles else "") + (", UB, USK" if uniform else "") + ">, static instruction counts per body")
+print("march loop of k_wall2<float, DP, VEC, FAST, NODES, MC, SG, NS, GD" + (", PR" if profiles else "") + (", UB, USK" if uniform else "") + ("[, PL = true]" if per_lane else "") + ">, static instruction counts per body")
 for (mangled, f), name in zip(funcs.items(), names):
     name = re.sub(r"\(.*", "", name).replace("void pf::", "")
+    if per_lane:  # (the last argument is printed where it is set only: the other kernels keep the names they had)
+        name = re.sub(r", false>$", ">", name)
     # instructions in order, labels remembered by the index of the instruction that follows them
     ins, labels = [], {}
     for line in f["lines"]:
