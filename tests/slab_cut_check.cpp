@@ -9,7 +9,12 @@
 //     originals' IN ORDER;
 //   * every kept entry is interior to its slab along the cut axis (receivers: in its owned planes), and its local index maps back to
 //     the global one;
-//   * the slabs' out_rows together are 0 .. Nr-1 exactly once.
+//   * the slabs' out_rows together are 0 .. Nr-1 exactly once;
+//   * the cuts increase strictly, at least two planes apart.
+// Scenes of 100 x 9 x 100 cells whose sources leave the balanced split no plane CUT_CLEAR = 8 planes from all of them, or only a few -- a source
+// in every interior plane; on every 6th plane (closer together than 2 * CUT_CLEAR); one band of 66 consecutive planes --, each list shuffled
+// and with four nodes listed twice, for G = 2, 3, 8: the same conditions, so the slabs' source lists partition the scene's in file order
+// (duplicates keep their order) and each signal row travels with its node.
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -32,7 +37,8 @@ void check(bool ok, const char *fmt, ...) {
 }
 
 struct Scene {
-   static constexpr int64_t Nx = 12, Ny = 9, Nz = 14, Nt = 6;
+   static constexpr int64_t Nt = 6;
+   const int64_t Nx, Ny, Nz;
    std::vector<int64_t> bn, bnl, bna, in, out, reorder;
    std::vector<uint16_t> adj;
    std::vector<int8_t> K, mat, Q, Mb{3, 11, 5};
@@ -43,7 +49,16 @@ struct Scene {
    uint64_t rnd() { state = state * 6364136223846793005ull + 1442695040888963407ull; return state >> 33; }
    int64_t cell(int64_t x, int64_t y, int64_t z) const { return x * Ny * Nz + y * Nz + z; }
    int64_t interior() { return cell(1 + (int64_t)(rnd() % (Nx - 2)), (int64_t)(rnd() % Ny), 1 + (int64_t)(rnd() % (Nz - 2))); }
-   explicit Scene(int real_bytes) {
+   enum Sources { TWO, EVERY_PLANE, EVERY_6TH, BAND_66 };
+   // node k of a spread list sits in plane p of x AND of z, so either axis can be cut through the same arrangement
+   void spread(Sources mode) {
+      in.clear();
+      const int64_t p0 = mode == EVERY_6TH ? 7 : (mode == BAND_66 ? 17 : 1), p1 = mode == BAND_66 ? 17 + 66 : Nx - 1, dp = mode == EVERY_6TH ? 6 : 1;
+      for (int64_t p = p0; p < p1; p += dp) in.push_back(cell(p, 1 + (int64_t)(rnd() % (Ny - 2)), p));
+      for (int k = 0; k < 4; k++) in.push_back(in[rnd() % in.size()]); // four nodes a second time
+      for (size_t i = in.size() - 1; i > 0; i--) std::swap(in[i], in[rnd() % (i + 1)]); // out of order
+   }
+   explicit Scene(int real_bytes, Sources mode = TWO, int64_t nx = 12, int64_t ny = 9, int64_t nz = 14) : Nx(nx), Ny(ny), Nz(nz) {
       bn.resize(300); bnl.resize(200); bna.resize(250);
       for (auto *l : {&bn, &bnl, &bna}) for (auto &v : *l) v = interior(); // (random order: unsorted)
       adj.resize(bn.size()); K.resize(bn.size()); mat.resize(bnl.size()); Q.resize(bna.size()); ssaf.resize(bnl.size() * (size_t)real_bytes);
@@ -53,6 +68,7 @@ struct Scene {
       for (auto &v : Q) v = (int8_t)(1 + rnd() % 3);
       for (auto &v : ssaf) v = (uint8_t)rnd();
       in = {cell(6, 4, 7), cell(2, 1, 11)};
+      if (mode != TWO) spread(mode);
       out = {cell(7, 4, 8), cell(11, 3, 0) /* a global ghost plane of x and of z */, cell(1, 8, 12), cell(5, 0, 1), cell(6, 4, 7)};
       reorder = {0, 1, 2, 3, 4};
       sigs.resize(in.size() * (size_t)Nt);
@@ -98,12 +114,14 @@ void check_chain(const Scene &sc, int G, bool along_z, bool even) {
    const pf_simdata *sd = &sc.sd;
    const int64_t N = along_z ? sc.Nz : sc.Nx, Nt = sc.Nt;
    const int rb = sd->real_bytes;
-   snprintf(g_ctx, sizeof g_ctx, "fp%d, G = %d, cut along %s, %s split", rb * 8, G, along_z ? "z" : "x", even ? "even" : "balanced");
+   snprintf(g_ctx, sizeof g_ctx, "fp%d, %ld sources, G = %d, cut along %s, %s split", rb * 8, (long)sd->Ns, G, along_z ? "z" : "x", even ? "even" : "balanced");
    std::vector<int64_t> cuts;
    const char *msg = pf_cut::partition(sd, G, even, cuts, along_z);
    check(!msg, "partition: %s", msg ? msg : "");
    if (msg) return;
    check((int)cuts.size() == G + 1 && cuts[0] == 0 && cuts[G] == N, "cuts do not span [0, %ld]", (long)N);
+   for (int g = 0; g < G && (int)cuts.size() == G + 1; g++)
+      check(cuts[g + 1] - cuts[g] >= 2, "cut %d at %ld, cut %d at %ld: not two planes apart", g, (long)cuts[g], g + 1, (long)cuts[g + 1]);
    std::vector<int> seen_bn(sd->Nb, 0), seen_bnl(sd->Nbl, 0), seen_bna(sd->Nba, 0), seen_in(sd->Ns, 0), seen_out(sd->Nr, 0), seen_row(sd->Nr, 0);
    for (int g = 0; g < G; g++) {
       pf_cut::Slab s;
@@ -155,6 +173,14 @@ int main() {
          for (bool along_z : {false, true})
             for (bool even : {true, false}) check_chain(sc, G, along_z, even);
    }
+   // sources that leave no cut, or hardly any, clear
+   for (int rb : {4, 8})
+      for (Scene::Sources mode : {Scene::EVERY_PLANE, Scene::EVERY_6TH, Scene::BAND_66}) {
+         const Scene sc(rb, mode, 100, 9, 100);
+         for (int G : {2, 3, 8})
+            for (bool along_z : {false, true})
+               for (bool even : {true, false}) check_chain(sc, G, along_z, even);
+      }
    // what cannot be cut says so
    const Scene sc(4);
    std::vector<int64_t> cuts;

@@ -272,8 +272,9 @@ def test_a_cut_pushed_aside_by_a_source_does_not_leave_a_thick_rank():
 
 def test_the_c_chains_cut_under_sanitizers(tmp_path):
     """csrc/pf_slab_cut.h -- what pf_multi_create cuts a scene with -- has no device in it: tests/slab_cut_check.cpp drives it on a small
-    unsorted scene (G = 2, 3, 5, both axes, both split rules, fp32 and fp64) as a program of its own, built with the host compiler under
-    the address and undefined-behaviour sanitizers; it names every violated condition on stderr."""
+    unsorted scene (G = 2, 3, 5, both axes, both split rules, fp32 and fp64) and on scenes whose sources leave the split no plane clear of
+    them, or few (a source in every plane, on every 6th, a band of 66; G = 2, 3, 8), as a program of its own, built with the host compiler
+    under the address and undefined-behaviour sanitizers; it names every violated condition on stderr."""
     import shutil
     import subprocess
     cxx = shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")

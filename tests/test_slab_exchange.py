@@ -3,7 +3,6 @@ slab stepped by the CPU ORACLE (test infrastructure standing in for the HIP step
 single-domain oracle bit for bit.  This covers the partition, the index re-basing, the exchange schedule and the
 output merge -- everything of the N>1 path except the HIP kernels themselves (covered by -m gpu tests).
 """
-import contextlib
 import os
 
 import numpy as np
@@ -16,46 +15,7 @@ import cases
 import oracle
 from pffdtd_amd import dist as pdist
 from pffdtd_amd import slab
-
-
-class OracleSlabStepper:
-    """Same interface as pffdtd_amd.dist.HipSlabStepper, backed by oracle.Engine (CPU, tests only)."""
-
-    def __init__(self, loc, info):
-        self.loc, self.info = loc, info
-        self.zcut = bool(getattr(info, "along_z", False))  # a chain cut along file z: the exchanged "planes" are z columns
-        self.e = oracle.Engine(loc, slab_first=info.first, slab_last=info.last, along_z=self.zcut)
-        self._staged = None
-
-    def step_begin(self, n):
-        self.e.step(n)  # whole step; the new state is u1 after the rotation
-        self._staged = None
-
-    def halo_tensors(self):
-        g = self.e.grid(1)
-        if self.zcut:  # strided in the file layout: staged through contiguous buffers, written back in step_end
-            if self._staged is None:
-                Nz = self.loc.Nz
-                c = lambda a: torch.from_numpy(np.ascontiguousarray(a).reshape(-1))  # noqa: E731
-                self._staged = (c(g[:, :, 1]), c(g[:, :, Nz - 2]), c(g[:, :, 0]), c(g[:, :, Nz - 1]))
-            return self._staged
-        Nx = self.loc.Nx
-        f = lambda a: torch.from_numpy(a.reshape(-1))  # noqa: E731  (views: irecv writes in place)
-        return f(g[1]), f(g[Nx - 2]), f(g[0]), f(g[Nx - 1])
-
-    def comm_context(self):
-        return contextlib.nullcontext()
-
-    def step_end(self, n):
-        if self.zcut and self._staged is not None:
-            g = self.e.grid(1)
-            if not self.info.first:
-                g[:, :, 0] = self._staged[2].numpy().reshape(g.shape[0], g.shape[1])
-            if not self.info.last:
-                g[:, :, -1] = self._staged[3].numpy().reshape(g.shape[0], g.shape[1])
-
-    def finish(self):
-        pass
+from slab_harness import OracleSlabStepper, run_in_process
 
 
 def _reference(name, prec):
@@ -72,18 +32,7 @@ def test_in_process_slabs_equal_single_domain(name, prec, G, along_z):
     FILE Z (what rooms get: their engines store the x and z axes exchanged)."""
     ref = _reference(name, prec)
     sd = cases.make_sd(name, prec)
-    parts = [slab.split(sd, G, r, balance=(G == 3), along_z=along_z) for r in range(G)]
-    st = [OracleSlabStepper(loc, info) for loc, info in parts]
-    for n in range(sd.Nt):
-        for s in st:
-            s.step_begin(n)
-        planes = [s.halo_tensors() for s in st]
-        for r in range(G - 1):
-            planes[r + 1][2].copy_(planes[r][1])      # my last updated plane -> right neighbour's low ghost
-            planes[r][3].copy_(planes[r + 1][0])      # right neighbour's first updated plane -> my high ghost
-        for s in st:
-            s.step_end(n)
-    out = slab.merge_outputs(sd, [p[0] for p in parts])
+    out = run_in_process(sd, G, along_z)  # (balance=(G == 3): the cost-balanced cut for three slabs, the even one for two)
     assert np.array_equal(out, ref)
 
 
