@@ -348,6 +348,29 @@ int  pf_engine_load_state(pf_engine *e, const pf_state *st);
  * covers the first exchanges after it again.  PF_ERR_STATE for a one-rank cost model (pf_opts.only_slab). */
 int  pf_multi_save_state(pf_multi *m, pf_state *st);
 int  pf_multi_load_state(pf_multi *m, const pf_state *st);
+/* ---- field regions: a plane or a box of the field during a run, without copying the grid ----
+ * The data behind the reference's plots (python/fdtd/sim_fdtd.py: gather_slice), which pf_engine_get_grid serves only by a copy of the whole grid.
+ * A region is a strided box in FILE coordinates x, y, z: the cells lo[a] + k * stride[a] < hi[a].  `host` receives counts[0] * counts[1] * counts[2]
+ * Reals, dense, z fastest: ((i * counts[1] + j) * counts[2] + k).  which: 0 = u^{n-1}, 1 = u^n, as pf_engine_get_grid.
+ *   - Every cell -- ghost cells and the folded row included -- holds bit for bit what pf_engine_get_grid(which) gives for it; for a chain, what
+ *     pf_multi_save_state writes into u_prev / u_cur.  The ghost shell of u^n is materialised (as pf_engine_get_grid(1) does) only when the region
+ *     holds a cell of a face of the grid.
+ *   - PF_ERR_ARG, with a message that names the field, for a null pointer, which outside 0 / 1, lo < 0, hi > N, lo >= hi, stride < 1.
+ *   - PF_ERR_STATE inside a split-phase step, inside a slab's pair or triple (u^{n+1} is not complete in memory there: a chain whose slabs step in
+ *     passes answers it at the steps in between, the caller advances a step and asks again) and for a one-rank cost model (pf_opts.only_slab).
+ *     A refusal leaves the engine or chain as it was.
+ *   - Works on an engine created with pf_opts.energy.  The receiver ring is not flushed, and nothing a later step reads changes.
+ *   - Device memory: ONE staging buffer for the call's duration, no larger than min(the region's bytes, 32 MiB) (csrc/pf_state.h:
+ *     PF_REGION_STAGE_BYTES); larger regions move in pieces along their slowest axis -- or, where they are evenly pitched rows of file-order storage
+ *     (unit strides, whole columns of y), by one pitched copy without any buffer, as pf_engine_get_grid.  Never a second grid, whatever the layout.
+ *   - A chain cuts the region to its slabs (csrc/pf_region_cut.h): every slab copies the part it owns on its own device and host thread into that
+ *     part's cells of `host`; a slab the region misses does nothing.
+ * pf_region_count: counts[a] = ceil((hi[a] - lo[a]) / stride[a]) (counts may be NULL); returns their product, or < 0 for a region that is not
+ * well-formed (pf_last_error says why; hi <= N is the engine's to check).  No counterpart in the reference. */
+typedef struct pf_region { int64_t lo[3], hi[3], stride[3]; } pf_region;
+int64_t pf_region_count(const pf_region *r, int64_t counts[3]);
+int  pf_engine_get_region(pf_engine *e, int32_t which, const pf_region *r, void *host);
+int  pf_multi_get_region(pf_multi *m, int32_t which, const pf_region *r, void *host);
 int  pf_engine_timing(pf_engine *e, pf_timing *t, int32_t reset);
 /* switch the per-launch HIP events of pf_opts.timing on / off between runs (a host times its headline region without them
  * and collects kernel durations in a region of its own) */

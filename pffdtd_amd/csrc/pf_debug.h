@@ -19,6 +19,7 @@ struct pf_opts_x : pf_opts {
 extern "C" void pf_internal_hooks(int32_t debug, int32_t test_drop_exchange, int32_t test_faults);
 pf_opts_x pf__take_hooks(const pf_opts *o); // *o (NULL: the defaults) + the calling thread's pending switches + PFFDTD_DEBUG
 int pf__engine_create_x(const pf_simdata *sd, const pf_opts_x *o, pf_engine **out);
+int pf__engine_get_region_x(pf_engine *e, int32_t which, const pf_region *r, void *host, int64_t pitch); // pf_engine_get_region with the output's rows `pitch` elements apart (0: dense)
 enum : int {
    PF_DBG_BRANCH_SELECTS = 0x1,       // three-step wall regions: fd_regs' select form (a branch count per lane) even where every material has the same count
    PF_DBG_STORE_UNREAD = 0x2,         // three-step wall regions: u^{n+1} of their cells goes to the scratch grid even where nothing reads it

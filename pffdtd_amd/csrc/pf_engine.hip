@@ -127,6 +127,12 @@ int pf__engine_create_x(const pf_simdata *sd, const pf_opts_x *opts, pf_engine *
    return PF_OK;
 }
 
+// internal (pf_multi.hip): the region's rows land `pitch` elements apart in `host` -- a slab's columns of a chain's dense output
+int pf__engine_get_region_x(pf_engine *e, int32_t which, const pf_region *r, void *host, int64_t pitch) {
+   if (!e || !e->impl) return set_err(PF_ERR_ARG, "null engine");
+   return e->impl->get_region(which, r, host, pitch);
+}
+
 extern "C" {
 
 void pf_engine_destroy(pf_engine *e) {
@@ -154,6 +160,13 @@ int pf_engine_sync(pf_engine *e) { PF_NEED(e); return e->impl->sync(); }
 int pf_engine_flush_outputs(pf_engine *e) { PF_NEED(e); return e->impl->flush(); }
 int pf_engine_get_grid(pf_engine *e, int32_t which, void *host) { PF_NEED(e); return e->impl->get_grid(which, host); }
 int pf_engine_set_grid(pf_engine *e, int32_t which, const void *host) { PF_NEED(e); return e->impl->set_grid(which, host); }
+int64_t pf_region_count(const pf_region *r, int64_t counts[3]) {
+   char msg[256];
+   const int64_t n = pf_cut::region_counts(r, counts, msg, sizeof msg);
+   if (n < 0) set_err(PF_ERR_ARG, "pf_region_count: %s", msg);
+   return n;
+}
+int pf_engine_get_region(pf_engine *e, int32_t which, const pf_region *r, void *host) { PF_NEED(e); return e->impl->get_region(which, r, host, 0); }
 int pf_engine_save_state(pf_engine *e, pf_state *st) { PF_NEED(e); return e->impl->save_state(st); }
 int pf_engine_load_state(pf_engine *e, const pf_state *st) { PF_NEED(e); return e->impl->load_state(st); }
 int pf_engine_timing(pf_engine *e, pf_timing *t, int32_t reset) { PF_NEED(e); return e->impl->timing(t, reset); }

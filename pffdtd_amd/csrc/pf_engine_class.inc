@@ -26,6 +26,8 @@
 #include "pf_brick.h"
 #include "pf_brick_fcc.h"
 #include "pf_state.h"
+#include "pf_region.h"
+#include "pf_region_cut.h"
 
 // shared between the two units (defined in pf_engine.hip)
 extern "C" void pf__set_error(const char *msg);
@@ -50,6 +52,7 @@ struct EngineBase {
    virtual int place_grids5(void *const *grids, int n, int32_t *idx) = 0;
    virtual int get_grid(int which, void *host) = 0;
    virtual int set_grid(int which, const void *host) = 0;
+   virtual int get_region(int which, const pf_region *r, void *host, int64_t pitch) = 0;
    virtual int save_state(pf_state *st) = 0;
    virtual int load_state(const pf_state *st) = 0;
    virtual int timing(pf_timing *t, int reset) = 0;
@@ -1068,6 +1071,7 @@ template <typename Real> struct Engine : EngineBase {
       return PF_OK;
    }
 #include "pf_engine_state.inc"
+#include "pf_engine_region.inc"
    void *stream(int which) override { return which == 1 ? (void *)s_edge : (void *)s_main; }
 };
 

@@ -52,6 +52,7 @@
 #include "pf_debug.h" // pf_opts_x: the public options + the development / test switches
 #include "pf_slab_cut.h" // Slab, partition, cut_slab: the cut itself, host code that needs no device
 #include "pf_state_cut.h" // scatter_state, gather_state: the canonical state cut to the slabs and put together again
+#include "pf_region_cut.h" // region_check, region_part: a region of the field cut to the slabs
 
 extern "C" void pf__set_error(const char *msg); // pf_engine.hip (feeds pf_last_error)
 extern "C" int pf__axis_exchange_pays(const pf_simdata *sd, int64_t *counts); // pf_engine.hip
@@ -588,6 +589,17 @@ void state_slab(Shared &S, int g, const pf_simdata *sd, pf_state *st, bool load)
    }
 }
 
+// a region of a field: slab g cuts the part it OWNS on its own device, straight into that part's cells of the caller's dense array (pf_region_cut.h says
+// which: the slabs' parts are disjoint, no two threads write one byte); a slab the region misses does nothing
+void region_slab(Shared &S, int g, int which, const pf_region &r, const int64_t rc[3], void *host) {
+   if (S.err.load() || !S.eng[g]) return;
+   const pf_cut::RegionPart p = pf_cut::region_part(r, rc, S.slabs[g], S.along_z);
+   if (p.empty) return;
+   MCHK(g, hipSetDevice(S.dev[g]));
+   uint8_t *out = (uint8_t *)host + (size_t)p.out_off * (size_t)S.slabs[g].sd.real_bytes;
+   ECHK(g, pf__engine_get_region_x(S.eng[g], which, &p.local, out, p.out_pitch));
+}
+
 void finish_slab(Shared &S, int g) {
    if (!S.eng[g]) return;
    hipSetDevice(S.dev[g]);
@@ -671,8 +683,12 @@ struct pf_multi {
    std::mutex mu;
    std::condition_variable cv_cmd, cv_done;
    int64_t cmd_seq = 0, cmd_n0 = 0, cmd_ns = 0;
-   int cmd_kind = 0;                 // 1 run, 2 quit, 3 save the state, 4 load it
+   int cmd_kind = 0;                 // 1 run, 2 quit, 3 save the state, 4 load it, 5 cut a region of a field
    pf_state *cmd_state = nullptr;    // ... from / into these global arrays
+   pf_region cmd_region{};           // 5: the region (checked), its counts, the field, the caller's dense array
+   int64_t cmd_rc[3] = {0, 0, 0};
+   int cmd_which = 0;
+   void *cmd_host = nullptr;
    int done = 0;
    bool created = false;
    double last_seconds = 0;
@@ -701,6 +717,7 @@ void worker(pf_multi *m, int g) {
       }
       if (kind == 2) break;
       if (kind == 3 || kind == 4) state_slab(S, g, m->sd, m->cmd_state, kind == 4);
+      else if (kind == 5) region_slab(S, g, m->cmd_which, m->cmd_region, m->cmd_rc, m->cmd_host);
       else run_slabs(S, g, g + 1, local, n0, ns);
       S.bar.wait(local, S.err, S.bar_timeout);
       { std::lock_guard<std::mutex> lk(m->mu); m->done++; }
@@ -992,6 +1009,37 @@ static int multi_state(pf_multi *m, pf_state *st, bool load, const char *what) {
 }
 int pf_multi_save_state(pf_multi *m, pf_state *st) { return multi_state(m, st, false, "pf_multi_save_state"); }
 int pf_multi_load_state(pf_multi *m, const pf_state *st) { return multi_state(m, const_cast<pf_state *>(st), true, "pf_multi_load_state"); }
+
+int pf_multi_get_region(pf_multi *m, int32_t which, const pf_region *r, void *host) {
+   const char *what = "pf_multi_get_region";
+   if (!m) return fail("%s: null object", what);
+   if (!r) return fail("%s: null pf_region", what);
+   if (!host) return fail("%s: null host array", what);
+   if (which != 0 && which != 1) return fail("%s: which must be 0 (u^{n-1}) or 1 (u^n)", what);
+   Shared &S = m->S;
+   if (S.G == 1) return pf_engine_get_region(S.eng[0], which, r, host);
+   if (S.only >= 0) { fail("%s: a one-rank cost model (pf_opts.only_slab) has no field of the scene", what); return PF_ERR_STATE; }
+   const int64_t N[3] = {m->sd->Nx, m->sd->Ny, m->sd->Nz};
+   int64_t rc[3];
+   char msg[256], full[320];
+   if (pf_cut::region_check(r, N, rc, msg, sizeof msg) < 0) { snprintf(full, sizeof full, "%s: %s", what, msg); return fail("%s", full); }
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   if (m->one_thread) { for (int g = 0; g < S.G; g++) region_slab(S, g, which, *r, rc, host); }
+   else {
+      { std::lock_guard<std::mutex> lk(m->mu); m->cmd_region = *r; m->cmd_which = which; m->cmd_host = host; for (int a = 0; a < 3; a++) m->cmd_rc[a] = rc[a]; }
+      post(m, 5, 0, 0);
+      wait_done(m);
+      if (m->broken && !S.err.load()) S.set_error(PF_ERR_HIP, "slab chain hung: a slab's host thread never came back");
+   }
+   if (S.err.load()) {
+      // a refusal (PF_ERR_STATE: a slab inside its pair or triple) leaves every engine as it was: the chain stays usable
+      const int code = S.err.load();
+      pf__set_error(S.err_msg.c_str());
+      if (code == PF_ERR_STATE || code == PF_ERR_ARG) S.err.store(0);
+      return code;
+   }
+   return PF_OK;
+}
 
 int pf_multi_get_info(pf_multi *m, pf_multi_info *info) {
    if (!m || !info) return fail("pf_multi_get_info: null argument");

@@ -16,7 +16,8 @@
 namespace pf {
 
 constexpr int STATE_STAGE_PLANES = 32; // file planes per chunk of a field: the staging buffer holds this many, whatever the grid's size
-constexpr int STATE_LDS_ROW = 13;      // a node's 12 branches, padded: the two access patterns of a tile both spread over the banks
+constexpr int64_t PF_REGION_STAGE_BYTES = (int64_t)32 << 20; // pf_engine_get_region (pf_region.h): its staging buffer holds at most this much, whatever the region's size
+constexpr int STATE_LDS_ROW = 13;     // a node's 12 branches, padded: the two access patterns of a tile both spread over the banks
 
 // perm[li] = row of sd->bnl_ixyz that the engine's lossy node li is (duplicates of an index keep a row each); mat / Mb: the node's material,
 // its branch count.  Branch slots m >= Mb[mat] are written as 0.  One block = one wave = one tile of 64 nodes.

@@ -61,6 +61,10 @@ class PfState(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("u_prev", "u_cur", "u1b", "u2b", "vh1", "gh1")]
 
 
+class PfRegion(ctypes.Structure):
+    _fields_ = [("lo", ctypes.c_int64 * 3), ("hi", ctypes.c_int64 * 3), ("stride", ctypes.c_int64 * 3)]
+
+
 STATE_KEYS = tuple(k for k, _ in PfState._fields_)
 PF_MMB = 12
 
@@ -91,7 +95,7 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_grid_bytes", "p
            "pf_run_sim", "pf_engine_create", "pf_engine_destroy", "pf_engine_run", "pf_engine_step_begin",
            "pf_engine_halo_ptrs", "pf_engine_step_end", "pf_engine_state_grids", "pf_engine_layout", "pf_engine_place_grids", "pf_engine_place_grids5", "pf_engine_set_spares", "pf_engine_stream", "pf_engine_sync",
            "pf_engine_flush_outputs", "pf_engine_get_grid", "pf_engine_set_grid", "pf_engine_save_state", "pf_engine_load_state",
-           "pf_multi_save_state", "pf_multi_load_state", "pf_engine_timing", "pf_engine_set_timing",
+           "pf_multi_save_state", "pf_multi_load_state", "pf_region_count", "pf_engine_get_region", "pf_multi_get_region", "pf_engine_timing", "pf_engine_set_timing",
            "pf_engine_energy_cfg", "pf_engine_run_energy", "pf_run_sim_devices", "pf_slab_partition", "pf_slab_partition_w", "pf_slab_partition_axis", "pf_slab_wall_scale",
            "pf_multi_create", "pf_multi_run", "pf_multi_get_info", "pf_multi_get_slab", "pf_multi_destroy",
            "pf_rccl_unique_id", "pf_rccl_comm_create", "pf_rccl_exchange", "pf_rccl_comm_destroy"]
@@ -174,6 +178,10 @@ def lib():
         L.pf_engine_timing.argtypes = [vp, ctypes.POINTER(PfTiming), i32]
         for f in (L.pf_engine_save_state, L.pf_engine_load_state, L.pf_multi_save_state, L.pf_multi_load_state):
             f.argtypes = [vp, ctypes.POINTER(PfState)]
+        L.pf_region_count.restype = i64
+        L.pf_region_count.argtypes = [ctypes.POINTER(PfRegion), ctypes.POINTER(i64)]
+        for f in (L.pf_engine_get_region, L.pf_multi_get_region):
+            f.argtypes = [vp, i32, ctypes.POINTER(PfRegion), vp]
         L.pf_engine_set_timing.argtypes = [vp, i32]
         dp = ctypes.POINTER(ctypes.c_double)
         L.pf_engine_energy_cfg.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, dp]
@@ -206,6 +214,20 @@ def _check(rc):
         e = PfError(f"pffdtd_hip error {rc}: {lib().pf_last_error().decode()}")
         e.code = int(rc)
         raise e
+
+
+def _get_region(call, handle, dtype, which, lo, hi, stride):
+    """pf_engine_get_region / pf_multi_get_region -> ndarray of shape counts, the cells lo + k * stride < hi in FILE coordinates x, y, z"""
+    try:
+        r = PfRegion((ctypes.c_int64 * 3)(*[int(v) for v in lo]), (ctypes.c_int64 * 3)(*[int(v) for v in hi]), (ctypes.c_int64 * 3)(*[int(v) for v in stride]))
+    except TypeError as e:
+        raise PfError(f"get_region: lo, hi and stride are three integers each ({e})")
+    counts = (ctypes.c_int64 * 3)()
+    if lib().pf_region_count(ctypes.byref(r), counts) < 0:
+        _check(1)  # (PF_ERR_ARG: pf_last_error names the field)
+    a = np.empty(tuple(int(c) for c in counts), dtype=dtype)
+    _check(call(handle, int(which), ctypes.byref(r), a.ctypes.data_as(ctypes.c_void_p)))
+    return a
 
 
 def device_count():
@@ -292,6 +314,11 @@ class HipMulti:
         arr, st = _state_arrays(self.sd, state)
         _check(lib().pf_multi_load_state(self._h, ctypes.byref(st)))
 
+    def get_region(self, which, lo, hi, stride=(1, 1, 1)):
+        """A strided box of u^{n-1} (which = 0) or u^n (1) of the whole scene (pf_multi_get_region): every slab cuts the part it owns on its own
+        device.  PfError with code 4 while a slab is inside a blocked pass: advance a step and ask again."""
+        return _get_region(lib().pf_multi_get_region, self._h, np.float32 if self.sd.real_bytes == 4 else np.float64, which, lo, hi, stride)
+
     def slab(self, g):
         """-> dict(x0, x1, device, paired, steps_per_pass, engine): engine = a non-owning HipEngine view of slab g's engine (state_grids, timing)"""
         x0, x1, dev, pr, eh = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_void_p()
@@ -324,6 +351,7 @@ class _EngineView:
     timing = lambda self, reset=False: HipEngine.timing(self, reset)  # noqa: E731
     sync = lambda self: HipEngine.sync(self)  # noqa: E731
     set_timing = lambda self, on: HipEngine.set_timing(self, on)  # noqa: E731
+    get_region = lambda self, which, lo, hi, stride=(1, 1, 1): HipEngine.get_region(self, which, lo, hi, stride)  # noqa: E731  (the slab's LOCAL coordinates)
 
 
 def slab_partition(sd, nslabs, even=False, wall_scale=1.0, along_z=False):
@@ -433,6 +461,11 @@ class HipEngine:
         a = np.empty((self.sd.Nx, self.sd.Ny, self.sd.Nz), dtype=self.dtype)
         _check(lib().pf_engine_get_grid(self._h, int(which), a.ctypes.data_as(ctypes.c_void_p)))
         return a
+
+    def get_region(self, which, lo, hi, stride=(1, 1, 1)):
+        """A strided box of u^{n-1} (which = 0) or u^n (1) without copying the grid (pf_engine_get_region): the cells lo + k * stride < hi in
+        FILE coordinates, as get_grid(which)[lo[0]:hi[0]:stride[0], lo[1]:hi[1]:stride[1], lo[2]:hi[2]:stride[2]]."""
+        return _get_region(lib().pf_engine_get_region, self._h, self.dtype, which, lo, hi, stride)
 
     def set_grid(self, which, a):
         a = np.ascontiguousarray(a, dtype=self.dtype)

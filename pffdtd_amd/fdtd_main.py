@@ -26,13 +26,20 @@ its first N steps (steps 0 .. N-1; exit status 0, no sim_outs.h5); `--resume FIL
 sim_outs.h5 of a run in one piece, bit for bit.  A chain whose slabs step in blocked pairs or triples can only be saved between
 passes: the checkpoint is then taken up to five steps later, at the first step every slab's pass has ended (the file records its step).
 One process with one device or a chain of them; the one-process-per-GPU launcher refuses these arguments.
+
+Field frames (the data behind the reference's `--plot`, without the plotting): `--field-planes x=I,y=J,z=K` (any subset, an axis may
+repeat) and `--field-box x0:x1:sx,y0:y1:sy,z0:z1:sz` name regions of the grid in FILE coordinates, `--field-every K` records them at the
+steps `--field-first N` (default 0), N + K, ... into `--field-file FILE` (default sim_fields.h5 beside sim_outs.h5; pffdtd_amd/fields.py
+describes the file).  The run is cut at the frame steps exactly as at checkpoint steps, and a chain inside a blocked pass takes the frame
+up to five steps later, recording where.  With `--resume` the file is appended to and the frames before the resumed step are kept.
+Same processes as the checkpoint arguments; without these arguments nothing about a run changes.
 """
 import argparse
 import os
 import time
 from pathlib import Path
 
-from . import checkpoint, engine, sim_data
+from . import checkpoint, engine, fields, sim_data
 
 
 def _summary(sd, tm, el):
@@ -86,7 +93,7 @@ def _run_chain(a, sd, m):
     """all Nt steps of a chain object, in one go or in chunks with progress reports; returns (seconds, timing of the busiest slab).
     With --resume / --checkpoint / --stop-after: from the resumed step, to the step the run stops after (a.stopped_at: less than Nt then)."""
     live = range(m.nslabs)
-    if a.resume or a.checkpoint:
+    if a.resume or a.checkpoint or a.field_every:
         return _run_chain_checkpointed(a, sd, m)
     t0 = time.perf_counter()
     if not a.progress:
@@ -113,7 +120,21 @@ def _run_chain(a, sd, m):
     return time.perf_counter() - t0, {"air_ms_total": air_all * 1e3, "step_ms_total": step_all * 1e3}
 
 
+def _field_writer(a, sd, resume_at):
+    """the FieldWriter of --field-planes / --field-box (None without them)"""
+    if not a.field_every:
+        return None
+    N = (sd.Nx, sd.Ny, sd.Nz)
+    try:
+        regions = [r for spec in a.field_planes for r in fields.parse_planes(spec, N)] + [fields.parse_box(spec, N) for spec in a.field_box]
+        path = a.field_file if a.field_file else Path(a.data_dir) / "sim_fields.h5"
+        return fields.FieldWriter(path, sd, regions, a.field_every, a.field_first, resume_at=resume_at)
+    except ValueError as e:
+        raise SystemExit(str(e))
+
+
 def _run_chain_checkpointed(a, sd, m):
+    """the run cut at checkpoint steps and at frame steps (--field-every)"""
     live = range(m.nslabs)
     n = 0
     if a.resume:
@@ -124,20 +145,31 @@ def _run_chain_checkpointed(a, sd, m):
         sd.u_out[...] = u_out  # (in place: the library writes into this array)
         m.load_state(state)
         print(f"--resumed at step {n} of {sd.Nt}: {a.resume}", flush=True)
+    fw = _field_writer(a, sd, n if a.resume else None)
     end = sd.Nt if a.stop_after is None else min(max(a.stop_after, n), sd.Nt)
     every = a.checkpoint_every if a.checkpoint else 0
     t0 = time.perf_counter()
     air_all = step_all = 0.0
+    if fw and fw.due(n) and n < end:  # (the frame of the first step: before any step of this run)
+        n = fw.take(m, n)
+        print(f"--field frame at step {n} of {sd.Nt}: {fw.path}", flush=True)
     while n < end:
         k = end - n
         if a.progress:
             k = min(k, a.progress)
         if every:
             k = min(k, every - n % every)
+        if fw and fw.next_step(n + 1) < n + k:
+            k = fw.next_step(n + 1) - n
         tc = time.perf_counter()
         m.run(n, k)
         n += k
-        if a.checkpoint and n < sd.Nt and ((every and n % every == 0) or n == end):
+        save = a.checkpoint and n < sd.Nt and ((every and n % every == 0) or n == end)
+        if fw and fw.due(n):
+            n = fw.take(m, n)
+            print(f"--field frame at step {n} of {sd.Nt}: {fw.path}", flush=True)
+            end = max(end, n)
+        if save:
             n = _save_checkpoint(a, sd, m, n)
             end = max(end, n)
         now = time.perf_counter()
@@ -275,7 +307,16 @@ def main():
     p.add_argument("--stop-after", type=int, default=None, metavar="N",
                    help="take the first N steps (0 .. N-1), write the checkpoint and exit with status 0, without sim_outs.h5")
     p.add_argument("--resume", default="", metavar="FILE", help="continue from this checkpoint file")
+    p.add_argument("--field-planes", action="append", default=[], metavar="x=I,y=J,z=K", help="record these planes of the field (FILE coordinates; any subset, an axis may repeat)")
+    p.add_argument("--field-box", action="append", default=[], metavar="x0:x1:sx,y0:y1:sy,z0:z1:sz", help="record this strided box of the field")
+    p.add_argument("--field-every", type=int, default=0, metavar="K", help="record the field regions every K steps")
+    p.add_argument("--field-first", type=int, default=0, metavar="N", help="... from step N on (default 0)")
+    p.add_argument("--field-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_fields.h5 in the data folder)")
     a = p.parse_args()
+    if bool(a.field_planes or a.field_box) != bool(a.field_every) or a.field_every < 0 or a.field_first < 0:
+        p.error("--field-planes / --field-box need --field-every K >= 1 (and the other way round); --field-first: not negative")
+    if (a.field_first or a.field_file) and not a.field_every:
+        p.error("--field-first / --field-file need --field-planes or --field-box")
     if (a.checkpoint_every or a.stop_after is not None) and not a.checkpoint:
         p.error("--checkpoint-every / --stop-after need --checkpoint FILE")
     if a.checkpoint_every < 0 or (a.stop_after is not None and a.stop_after < 0):
@@ -283,6 +324,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 and (a.checkpoint or a.resume) and not a.devices:
         raise SystemExit("--checkpoint / --resume: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
+    if world > 1 and a.field_every and not a.devices:
+        raise SystemExit("--field-planes / --field-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
     if a.devices:
         return run_devices(a, [int(v) for v in a.devices.split(",")])
     if world > 1:

@@ -6,7 +6,7 @@ the time loop on the MI355X through the C ABI instead of numba.
 Same method names and call order as the reference's `main()` (sim_fdtd.py:898-937): load_h5_data -> setup_mask ->
 allocate_mem -> set_coeffs -> checks -> run_all -> save_outputs -> print_last_samples.  Like the reference Python
 engine it does not rescale the input (`scale_input` belongs to the C flow: see pffdtd_amd/fdtd_main.py).
-Plotting (`--plot`) is out of scope.  `--energy` runs the reference's energy-conservation diagnostic on the device.
+Plotting (`--plot`) is out of scope; the data behind the reference's plots, `gather_slice`, is there.  `--energy` runs the reference's energy-conservation diagnostic on the device.
 """
 import argparse
 import time
@@ -87,13 +87,11 @@ class SimEngine:
         """One plane of the current field u1 (sim_fdtd.py:630-658); the reference fills the checkerboard holes of an FCC
         subgrid for plotting (nb_fcc_fill_plot_holes, :888-895), reproduced with numpy."""
         import numpy as np
-        u1 = self.eng.get_grid(1)
-        if ix is not None:
-            sl, k = u1[ix, :, :].copy(), ix
-        elif iy is not None:
-            sl, k = u1[:, iy, :].copy(), iy
-        else:
-            sl, k = u1[:, :, iz].copy(), iz
+        lo, hi = [0, 0, 0], [self.sd.Nx, self.sd.Ny, self.sd.Nz]
+        a, k = (0, ix) if ix is not None else ((1, iy) if iy is not None else (2, iz))
+        k = int(k) + (hi[a] if k < 0 else 0)  # (a negative index counts from the end, as in the slicing this replaces)
+        lo[a], hi[a] = k, k + 1
+        sl = self.eng.get_region(1, lo, hi).squeeze(axis=a)  # the plane alone (pf_engine_get_region), not a copy of the grid
         if self.fcc and self.sd.fcc_flag == 1:
             i1, i2 = np.meshgrid(np.arange(1, sl.shape[0] - 1), np.arange(1, sl.shape[1] - 1), indexing="ij")
             holes = ((i1 + i2 + k) % 2) == 1
