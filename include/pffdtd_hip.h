@@ -371,6 +371,44 @@ typedef struct pf_region { int64_t lo[3], hi[3], stride[3]; } pf_region;
 int64_t pf_region_count(const pf_region *r, int64_t counts[3]);
 int  pf_engine_get_region(pf_engine *e, int32_t which, const pf_region *r, void *host);
 int  pf_multi_get_region(pf_multi *m, int32_t which, const pf_region *r, void *host);
+/* ---- field accumulators: running sums of a region over the time steps, kept on the device ----
+ * What frames cannot give: EVERY step of every cell of a region (a 1024^2 plane over 76 460 steps is 320 GB through the host).  An accumulator
+ * belongs to one engine (or chain) and holds, for a region and nchan real channels,
+ *        acc[m][cell] += w[m] * (double)u^n[cell]          at every pf_engine_accum_add, in double, on the device
+ * -- with w = g(n) cos(2 pi f n Ts), -g(n) sin(2 pi f n Ts) a running DFT of every cell (pffdtd_amd/spectra.py).  16 bytes per cell and channel,
+ * whatever the run's length.  No counterpart in the reference.
+ *   - The sample is u^n, the field the receivers of step n sample: cell for cell -- ghost cells and the folded row included -- what
+ *     pf_engine_get_region(1, ...) gives at the same moment, and the virtual ghost shell is materialised exactly when that call would.  Nothing a
+ *     later step reads changes; the receiver ring is not flushed.
+ *   - Arithmetic: one multiplication rounded to double, one addition rounded to double per sample and channel, in the order of the calls (no fused
+ *     multiply-add): numpy's acc += w * u.astype(float64) gives the same bits.  fp32 denormals of the field are kept.
+ *   - depth (1 .. 16, 0 = the default the measurements of profiles/field_spectra.txt chose): so many samples wait in a ring on the device and are
+ *     folded into the sums together, which moves 16 * nchan / depth + 2 * sizeof(Real) bytes per sample and cell instead of 16 * nchan +
+ *     sizeof(Real).  The order of the additions is the same: the depth never changes a bit of a sum.
+ *   - get folds what is pending and copies the sums out, [nchan][cells] doubles, the cells dense in the region's order (z fastest, as
+ *     pf_engine_get_region); it resets nothing.  set drops what is pending and replaces the sums (host NULL: zeros) and the count: how a resumed
+ *     run continues.  pf_accum_count: the samples added so far, or the count given to set.
+ *   - add, get and set are valid between runs only: PF_ERR_STATE under the conditions of pf_engine_get_region.  An engine created with pf_opts.energy
+ *     answers.  PF_ERR_ARG, with a message that names the field, for a null pointer, nchan outside 1 .. 256, depth outside 0 .. 16, a region
+ *     pf_engine_get_region would refuse, a negative count, and a handle that belongs to another engine or chain.
+ *   - Several accumulators per engine are allowed; pf_engine_destroy / pf_multi_destroy free those left (their handles are dead afterwards).
+ *   - Device memory, all of it the engine's: nchan * cells doubles (rows padded to an even cell count), depth * cells Reals, depth * nchan doubles.
+ *   - A chain gives every slab that owns cells of the region an accumulator over its part (csrc/pf_region_cut.h); add runs on every slab's own
+ *     device and host thread.  add is all or nothing: where any slab is inside a pair or a triple no slab's sums or count change, the call
+ *     returns PF_ERR_STATE and the chain stays usable -- a chain meant to be sampled at given steps is created with
+ *     PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES.  PF_ERR_STATE for a one-rank cost model (pf_opts.only_slab). */
+typedef struct pf_accum pf_accum;
+int     pf_engine_accum_create (pf_engine *e, const pf_region *r, int32_t nchan, int32_t depth, pf_accum **out);
+int     pf_engine_accum_add    (pf_engine *e, pf_accum *a, const double *w);          /* w[nchan] */
+int     pf_engine_accum_get    (pf_engine *e, pf_accum *a, double *host);             /* host[nchan][cells] */
+int     pf_engine_accum_set    (pf_engine *e, pf_accum *a, const double *host, int64_t count);
+int64_t pf_accum_count         (const pf_accum *a);
+int     pf_engine_accum_destroy(pf_engine *e, pf_accum *a);
+int     pf_multi_accum_create  (pf_multi *m, const pf_region *r, int32_t nchan, int32_t depth, pf_accum **out);
+int     pf_multi_accum_add     (pf_multi *m, pf_accum *a, const double *w);
+int     pf_multi_accum_get     (pf_multi *m, pf_accum *a, double *host);
+int     pf_multi_accum_set     (pf_multi *m, pf_accum *a, const double *host, int64_t count);
+int     pf_multi_accum_destroy (pf_multi *m, pf_accum *a);
 int  pf_engine_timing(pf_engine *e, pf_timing *t, int32_t reset);
 /* switch the per-launch HIP events of pf_opts.timing on / off between runs (a host times its headline region without them
  * and collects kernel durations in a region of its own) */

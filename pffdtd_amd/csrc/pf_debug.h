@@ -4,6 +4,7 @@
 // pf_opts (include/pffdtd_hip.h); they reach the library through pf_internal_hooks below (exported, declared only here; pffdtd_amd/engine.py
 // calls it for its `debug=` / `test_*=` keyword arguments) or the environment variable PFFDTD_DEBUG (a number, OR-ed in).
 #pragma once
+#include <vector>
 #include "pffdtd_hip.h"
 // the options as the engines and the chain see them: the public ones + the switches
 struct pf_opts_x : pf_opts {
@@ -20,6 +21,22 @@ extern "C" void pf_internal_hooks(int32_t debug, int32_t test_drop_exchange, int
 pf_opts_x pf__take_hooks(const pf_opts *o); // *o (NULL: the defaults) + the calling thread's pending switches + PFFDTD_DEBUG
 int pf__engine_create_x(const pf_simdata *sd, const pf_opts_x *o, pf_engine **out);
 int pf__engine_get_region_x(pf_engine *e, int32_t which, const pf_region *r, void *host, int64_t pitch); // pf_engine_get_region with the output's rows `pitch` elements apart (0: dense)
+// A field accumulator's handle (pffdtd_hip.h: pf_accum).  An engine's: `eng` and the engine's own object `impl`.  A chain's: `chain` and one engine
+// handle per slab, null where the region misses the slab -- part[g] sums region_part(...).local of slab g.  `count` is kept here, by the C ABI.
+struct pf_accum {
+   pf_engine *eng = nullptr;
+   void *impl = nullptr;
+   pf_multi *chain = nullptr;
+   std::vector<pf_accum *> part;
+   pf_region region{};
+   int64_t rc[3] = {0, 0, 0}, cells = 0; // the region's counts
+   int32_t nchan = 0;
+   int64_t count = 0;
+};
+// pf_engine_accum_get / _set with the caller's rows `pitch` and channels `chstride` doubles apart (0: dense) -- a slab's cells of a chain's array; count: as given
+int pf__engine_accum_get_x(pf_engine *e, pf_accum *a, double *host, int64_t pitch, int64_t chstride);
+int pf__engine_accum_set_x(pf_engine *e, pf_accum *a, const double *host, int64_t pitch, int64_t chstride, int64_t count);
+int pf__engine_between_runs(pf_engine *e); // 1: not inside a split-phase step or pass (what pf_engine_accum_add needs)
 enum : int {
    PF_DBG_BRANCH_SELECTS = 0x1,       // three-step wall regions: fd_regs' select form (a branch count per lane) even where every material has the same count
    PF_DBG_STORE_UNREAD = 0x2,         // three-step wall regions: u^{n+1} of their cells goes to the scratch grid even where nothing reads it

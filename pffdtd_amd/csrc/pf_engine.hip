@@ -50,13 +50,14 @@ extern "C" int pf__axis_exchange_pays(const pf_simdata *sd, int64_t *counts) {
 
 struct pf_engine {
    pfeng::EngineBase *impl;
+   std::vector<pf_accum *> accums; // the handles of its field accumulators still alive (pf_engine_destroy frees those left)
 };
 pfeng::EngineBase *pf__new_engine_f64(const pf_simdata *sd, const pf_opts_x *o, int *rc); // pf_engine_f64.hip
 
 extern "C" {
 
 const char *pf_last_error(void) { return g_err.c_str(); }
-const char *pf_version(void) { return "pffdtd_hip 0.2 (gfx950)"; }
+const char *pf_version(void) { return "pffdtd_hip 0.3 (gfx950)"; }
 
 int pf_device_count(void) {
    int n = 0;
@@ -123,7 +124,7 @@ int pf__engine_create_x(const pf_simdata *sd, const pf_opts_x *opts, pf_engine *
       return set_err(PF_ERR_ARG, "real_bytes must be 4 or 8 (got %d)", sd->real_bytes);
    }
    if (rc) { std::string keep = g_err; delete impl; g_err = keep; return rc; }
-   *out = new pf_engine{impl};
+   *out = new pf_engine{impl, {}};
    return PF_OK;
 }
 
@@ -133,12 +134,67 @@ int pf__engine_get_region_x(pf_engine *e, int32_t which, const pf_region *r, voi
    return e->impl->get_region(which, r, host, pitch);
 }
 
+// field accumulators: the handle must be this engine's (a chain's handle, or another engine's, is refused before the engine sees it)
+static int accum_mine(pf_engine *e, const pf_accum *a, const char *what) {
+   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
+   if (!a) return set_err(PF_ERR_ARG, "%s: null pf_accum", what);
+   if (a->eng != e) return set_err(PF_ERR_ARG, "%s: the pf_accum belongs to another engine%s", what, a->chain ? " (it is a chain's: pf_multi_accum_*)" : "");
+   return PF_OK;
+}
+// internal (pf_multi.hip): a slab's cells of a chain's [nchan][cells] array -- rows `pitch`, channels `chstride` doubles apart
+int pf__engine_accum_get_x(pf_engine *e, pf_accum *a, double *host, int64_t pitch, int64_t chstride) {
+   const int rc = accum_mine(e, a, "pf_engine_accum_get");
+   return rc ? rc : e->impl->accum_get(a->impl, host, pitch, chstride);
+}
+int pf__engine_accum_set_x(pf_engine *e, pf_accum *a, const double *host, int64_t pitch, int64_t chstride, int64_t count) {
+   int rc = accum_mine(e, a, "pf_engine_accum_set");
+   if (rc) return rc;
+   if (count < 0) return set_err(PF_ERR_ARG, "pf_engine_accum_set: count = %ld < 0", (long)count);
+   if ((rc = e->impl->accum_set(a->impl, host, pitch, chstride))) return rc;
+   a->count = count;
+   return PF_OK;
+}
+int pf__engine_between_runs(pf_engine *e) { return e && e->impl && e->impl->between_runs() ? 1 : 0; }
+
 extern "C" {
 
 void pf_engine_destroy(pf_engine *e) {
    if (!e) return;
+   for (pf_accum *a : e->accums) delete a; // (their device memory is the engine's: freed with it)
    delete e->impl;
    delete e;
+}
+
+int pf_engine_accum_create(pf_engine *e, const pf_region *r, int32_t nchan, int32_t depth, pf_accum **out) {
+   const char *what = "pf_engine_accum_create";
+   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
+   if (!out) return set_err(PF_ERR_ARG, "%s: null out", what);
+   *out = nullptr;
+   void *impl = nullptr;
+   const int rc = e->impl->accum_create(r, nchan, depth, &impl);
+   if (rc) return rc;
+   pf_accum *a = new pf_accum();
+   a->eng = e; a->impl = impl; a->region = *r; a->nchan = nchan;
+   a->cells = pf_cut::region_counts(r, a->rc);
+   e->accums.push_back(a);
+   *out = a;
+   return PF_OK;
+}
+int pf_engine_accum_add(pf_engine *e, pf_accum *a, const double *w) {
+   int rc = accum_mine(e, a, "pf_engine_accum_add");
+   if (rc || (rc = e->impl->accum_add(a->impl, w))) return rc;
+   a->count++;
+   return PF_OK;
+}
+int pf_engine_accum_get(pf_engine *e, pf_accum *a, double *host) { return pf__engine_accum_get_x(e, a, host, 0, 0); }
+int pf_engine_accum_set(pf_engine *e, pf_accum *a, const double *host, int64_t count) { return pf__engine_accum_set_x(e, a, host, 0, 0, count); }
+int64_t pf_accum_count(const pf_accum *a) { return a ? a->count : -1; }
+int pf_engine_accum_destroy(pf_engine *e, pf_accum *a) {
+   int rc = accum_mine(e, a, "pf_engine_accum_destroy");
+   if (rc || (rc = e->impl->accum_destroy(a->impl))) return rc;
+   e->accums.erase(std::find(e->accums.begin(), e->accums.end(), a));
+   delete a;
+   return PF_OK;
 }
 
 #define PF_NEED(e) if (!(e) || !(e)->impl) return set_err(PF_ERR_ARG, "null engine")

@@ -8,6 +8,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <numeric>
@@ -28,6 +29,7 @@
 #include "pf_state.h"
 #include "pf_region.h"
 #include "pf_region_cut.h"
+#include "pf_accum.h"
 
 // shared between the two units (defined in pf_engine.hip)
 extern "C" void pf__set_error(const char *msg);
@@ -53,6 +55,12 @@ struct EngineBase {
    virtual int get_grid(int which, void *host) = 0;
    virtual int set_grid(int which, const void *host) = 0;
    virtual int get_region(int which, const pf_region *r, void *host, int64_t pitch) = 0;
+   virtual int accum_create(const pf_region *r, int nchan, int depth, void **out) = 0; // field accumulators (pf_engine_accum.inc); the handle is the engine's own
+   virtual int accum_add(void *a, const double *w) = 0;
+   virtual int accum_get(void *a, double *host, int64_t pitch, int64_t chstride) = 0;
+   virtual int accum_set(void *a, const double *host, int64_t pitch, int64_t chstride) = 0;
+   virtual int accum_destroy(void *a) = 0;
+   virtual bool between_runs() const = 0; // not inside a split-phase step or pass
    virtual int save_state(pf_state *st) = 0;
    virtual int load_state(const pf_state *st) = 0;
    virtual int timing(pf_timing *t, int reset) = 0;
@@ -1072,6 +1080,7 @@ template <typename Real> struct Engine : EngineBase {
    }
 #include "pf_engine_state.inc"
 #include "pf_engine_region.inc"
+#include "pf_engine_accum.inc"
    void *stream(int which) override { return which == 1 ? (void *)s_edge : (void *)s_main; }
 };
 

@@ -600,6 +600,13 @@ void region_slab(Shared &S, int g, int which, const pf_region &r, const int64_t 
    ECHK(g, pf__engine_get_region_x(S.eng[g], which, &p.local, out, p.out_pitch));
 }
 
+// a sample of a field accumulator: slab g adds u^n of its part on its own device (the caller has seen every slab between two passes: all or nothing)
+void accum_add_slab(Shared &S, int g, pf_accum *a, const double *w) {
+   if (S.err.load() || !S.eng[g] || !a->part[g]) return;
+   MCHK(g, hipSetDevice(S.dev[g]));
+   ECHK(g, pf_engine_accum_add(S.eng[g], a->part[g], w));
+}
+
 void finish_slab(Shared &S, int g) {
    if (!S.eng[g]) return;
    hipSetDevice(S.dev[g]);
@@ -683,7 +690,10 @@ struct pf_multi {
    std::mutex mu;
    std::condition_variable cv_cmd, cv_done;
    int64_t cmd_seq = 0, cmd_n0 = 0, cmd_ns = 0;
-   int cmd_kind = 0;                 // 1 run, 2 quit, 3 save the state, 4 load it, 5 cut a region of a field
+   int cmd_kind = 0;                 // 1 run, 2 quit, 3 save the state, 4 load it, 5 cut a region of a field, 6 add a sample to a field accumulator
+   pf_accum *cmd_accum = nullptr;    // 6: the chain's accumulator and the sample's weights
+   const double *cmd_w = nullptr;
+   std::vector<pf_accum *> accums;   // the chain's field accumulators still alive (pf_multi_destroy frees those left)
    pf_state *cmd_state = nullptr;    // ... from / into these global arrays
    pf_region cmd_region{};           // 5: the region (checked), its counts, the field, the caller's dense array
    int64_t cmd_rc[3] = {0, 0, 0};
@@ -718,6 +728,7 @@ void worker(pf_multi *m, int g) {
       if (kind == 2) break;
       if (kind == 3 || kind == 4) state_slab(S, g, m->sd, m->cmd_state, kind == 4);
       else if (kind == 5) region_slab(S, g, m->cmd_which, m->cmd_region, m->cmd_rc, m->cmd_host);
+      else if (kind == 6) accum_add_slab(S, g, m->cmd_accum, m->cmd_w);
       else run_slabs(S, g, g + 1, local, n0, ns);
       S.bar.wait(local, S.err, S.bar_timeout);
       { std::lock_guard<std::mutex> lk(m->mu); m->done++; }
@@ -1041,6 +1052,134 @@ int pf_multi_get_region(pf_multi *m, int32_t which, const pf_region *r, void *ho
    return PF_OK;
 }
 
+// ---- field accumulators of a chain: one engine accumulator per slab that owns cells of the region, over region_part(...).local; get and set move a
+// slab's sums to and from its cells of the caller's [nchan][cells] array (offset out_off, rows out_pitch apart, channels `cells` apart).  Create, get,
+// set and destroy walk the slabs on the caller's thread (the engine calls choose their device); add is a command of the slab threads.
+static int accum_chain(pf_multi *m, const pf_accum *a, const char *what) { // G > 1: the handle is this chain's
+   if (!a) return fail("%s: null pf_accum", what);
+   if (a->chain != m) return fail("%s: the pf_accum belongs to another engine or chain", what);
+   return PF_OK;
+}
+// an error the slabs raised: a refusal (PF_ERR_STATE, PF_ERR_ARG) leaves every engine as it was and the chain usable
+static int accum_status(Shared &S) {
+   const int code = S.err.load();
+   if (!code) return PF_OK;
+   pf__set_error(S.err_msg.c_str());
+   if (code == PF_ERR_STATE || code == PF_ERR_ARG) S.err.store(0);
+   return code;
+}
+#define PF_ACCUM_ENTER(what)                                                                                                        \
+   if (!m) return fail("%s: null object", what);                                                                                    \
+   Shared &S = m->S;                                                                                                                \
+   if (S.only >= 0) { fail("%s: a one-rank cost model (pf_opts.only_slab) has no field of the scene", what); return PF_ERR_STATE; }
+
+int pf_multi_accum_create(pf_multi *m, const pf_region *r, int32_t nchan, int32_t depth, pf_accum **out) {
+   const char *what = "pf_multi_accum_create";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_accum_create(S.eng[0], r, nchan, depth, out);
+   if (!r) return fail("%s: null pf_region", what);
+   if (!out) return fail("%s: null out", what);
+   *out = nullptr;
+   const int64_t N[3] = {m->sd->Nx, m->sd->Ny, m->sd->Nz};
+   char msg[256], full[320];
+   std::unique_ptr<pf_accum> a(new pf_accum());
+   if ((a->cells = pf_cut::region_check(r, N, a->rc, msg, sizeof msg)) < 0) { snprintf(full, sizeof full, "%s: %s", what, msg); return fail("%s", full); }
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   a->chain = m; a->region = *r; a->nchan = nchan;
+   a->part.assign((size_t)S.G, nullptr);
+   for (int g = 0; g < S.G; g++) {
+      const pf_cut::RegionPart p = pf_cut::region_part(*r, a->rc, S.slabs[g], S.along_z);
+      if (p.empty) continue;
+      const int rc = pf_engine_accum_create(S.eng[g], &p.local, nchan, depth, &a->part[g]); // (nchan, depth out of range: the first slab's message names them)
+      if (rc) {
+         const std::string keep = pf_last_error();
+         for (int h = 0; h < g; h++) if (a->part[h]) pf_engine_accum_destroy(S.eng[h], a->part[h]);
+         pf__set_error(keep.c_str());
+         return rc;
+      }
+   }
+   m->accums.push_back(a.get());
+   *out = a.release();
+   return PF_OK;
+}
+
+int pf_multi_accum_add(pf_multi *m, pf_accum *a, const double *w) {
+   const char *what = "pf_multi_accum_add";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_accum_add(S.eng[0], a, w);
+   if (accum_chain(m, a, what)) return PF_ERR_ARG;
+   if (!w) return fail("%s: null weights", what);
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   // all or nothing: the slab threads are idle, so every engine can be asked here, before any of them takes the sample
+   for (int g = 0; g < S.G; g++)
+      if (!pf__engine_between_runs(S.eng[g])) {
+         char b[256];
+         snprintf(b, sizeof b, "%s: slab %d is inside a pair or triple (u^{n+1} is not complete in memory): no slab took the sample; advance a step, or create the chain with "
+                               "PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES", what, g);
+         pf__set_error(b);
+         return PF_ERR_STATE;
+      }
+   if (m->one_thread) { for (int g = 0; g < S.G; g++) accum_add_slab(S, g, a, w); }
+   else {
+      { std::lock_guard<std::mutex> lk(m->mu); m->cmd_accum = a; m->cmd_w = w; }
+      post(m, 6, 0, 0);
+      wait_done(m);
+      if (m->broken && !S.err.load()) S.set_error(PF_ERR_HIP, "slab chain hung: a slab's host thread never came back");
+   }
+   const int rc = accum_status(S);
+   if (rc == PF_OK) a->count++;
+   return rc;
+}
+
+int pf_multi_accum_get(pf_multi *m, pf_accum *a, double *host) {
+   const char *what = "pf_multi_accum_get";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_accum_get(S.eng[0], a, host);
+   if (accum_chain(m, a, what)) return PF_ERR_ARG;
+   if (!host) return fail("%s: null host array", what);
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   for (int g = 0; g < S.G; g++) {
+      if (!a->part[g]) continue;
+      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
+      const int rc = pf__engine_accum_get_x(S.eng[g], a->part[g], host + p.out_off, p.out_pitch, a->cells);
+      if (rc) return rc;
+   }
+   return PF_OK;
+}
+
+int pf_multi_accum_set(pf_multi *m, pf_accum *a, const double *host, int64_t count) {
+   const char *what = "pf_multi_accum_set";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_accum_set(S.eng[0], a, host, count);
+   if (accum_chain(m, a, what)) return PF_ERR_ARG;
+   if (count < 0) return fail("%s: count < 0", what);
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   for (int g = 0; g < S.G; g++)
+      if (!pf__engine_between_runs(S.eng[g])) { fail("%s: a slab is inside a pair or triple: valid between passes only", what); return PF_ERR_STATE; }
+   for (int g = 0; g < S.G; g++) {
+      if (!a->part[g]) continue;
+      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
+      const int rc = pf__engine_accum_set_x(S.eng[g], a->part[g], host ? host + p.out_off : nullptr, p.out_pitch, a->cells, count);
+      if (rc) return rc;
+   }
+   a->count = count;
+   return PF_OK;
+}
+
+int pf_multi_accum_destroy(pf_multi *m, pf_accum *a) {
+   const char *what = "pf_multi_accum_destroy";
+   if (!m) return fail("%s: null object", what);
+   Shared &S = m->S;
+   if (S.G == 1) return pf_engine_accum_destroy(S.eng[0], a);
+   if (accum_chain(m, a, what)) return PF_ERR_ARG;
+   int rc = PF_OK;
+   for (int g = 0; g < S.G; g++)
+      if (a->part[g] && S.eng[g]) { const int r1 = pf_engine_accum_destroy(S.eng[g], a->part[g]); if (r1 && !rc) rc = r1; }
+   m->accums.erase(std::find(m->accums.begin(), m->accums.end(), a));
+   delete a;
+   return rc;
+}
+
 int pf_multi_get_info(pf_multi *m, pf_multi_info *info) {
    if (!m || !info) return fail("pf_multi_get_info: null argument");
    const Shared &S = m->S;
@@ -1085,6 +1224,7 @@ void pf_multi_destroy(pf_multi *m) {
    }
    if (S.G == 1) { if (S.eng[0]) { pf_engine_destroy(S.eng[0]); S.eng[0] = nullptr; } }
    else for (int g = 0; g < S.G; g++) destroy_slab(S, g);
+   for (pf_accum *a : m->accums) delete a; // (the slabs' parts went with their engines)
    for (auto &c : S.comm) if (c) { g_rccl.CommDestroy(c); c = nullptr; }
    delete m;
 }

@@ -96,6 +96,8 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_grid_bytes", "p
            "pf_engine_halo_ptrs", "pf_engine_step_end", "pf_engine_state_grids", "pf_engine_layout", "pf_engine_place_grids", "pf_engine_place_grids5", "pf_engine_set_spares", "pf_engine_stream", "pf_engine_sync",
            "pf_engine_flush_outputs", "pf_engine_get_grid", "pf_engine_set_grid", "pf_engine_save_state", "pf_engine_load_state",
            "pf_multi_save_state", "pf_multi_load_state", "pf_region_count", "pf_engine_get_region", "pf_multi_get_region", "pf_engine_timing", "pf_engine_set_timing",
+           "pf_engine_accum_create", "pf_engine_accum_add", "pf_engine_accum_get", "pf_engine_accum_set", "pf_engine_accum_destroy", "pf_accum_count",
+           "pf_multi_accum_create", "pf_multi_accum_add", "pf_multi_accum_get", "pf_multi_accum_set", "pf_multi_accum_destroy",
            "pf_engine_energy_cfg", "pf_engine_run_energy", "pf_run_sim_devices", "pf_slab_partition", "pf_slab_partition_w", "pf_slab_partition_axis", "pf_slab_wall_scale",
            "pf_multi_create", "pf_multi_run", "pf_multi_get_info", "pf_multi_get_slab", "pf_multi_destroy",
            "pf_rccl_unique_id", "pf_rccl_comm_create", "pf_rccl_exchange", "pf_rccl_comm_destroy"]
@@ -183,6 +185,14 @@ def lib():
         for f in (L.pf_engine_get_region, L.pf_multi_get_region):
             f.argtypes = [vp, i32, ctypes.POINTER(PfRegion), vp]
         L.pf_engine_set_timing.argtypes = [vp, i32]
+        for pre in ("pf_engine", "pf_multi"):
+            getattr(L, pre + "_accum_create").argtypes = [vp, ctypes.POINTER(PfRegion), i32, i32, ctypes.POINTER(vp)]
+            getattr(L, pre + "_accum_add").argtypes = [vp, vp, vp]
+            getattr(L, pre + "_accum_get").argtypes = [vp, vp, vp]
+            getattr(L, pre + "_accum_set").argtypes = [vp, vp, vp, i64]
+            getattr(L, pre + "_accum_destroy").argtypes = [vp, vp]
+        L.pf_accum_count.restype = i64
+        L.pf_accum_count.argtypes = [vp]
         dp = ctypes.POINTER(ctypes.c_double)
         L.pf_engine_energy_cfg.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, dp]
         L.pf_engine_run_energy.argtypes = [vp, i64, i64, dp, dp, dp]
@@ -228,6 +238,68 @@ def _get_region(call, handle, dtype, which, lo, hi, stride):
     a = np.empty(tuple(int(c) for c in counts), dtype=dtype)
     _check(call(handle, int(which), ctypes.byref(r), a.ctypes.data_as(ctypes.c_void_p)))
     return a
+
+
+class Accumulator:
+    """Running sums of a region of the field on the device (pf_engine_accum_* / pf_multi_accum_*): acc[m] += w[m] * double(u^n) at every add.
+    Made by HipEngine.accumulator / HipMulti.accumulator; it lives no longer than the object that made it."""
+
+    def __init__(self, owner, prefix, lo, hi, stride, nchan, depth):
+        try:
+            r = PfRegion((ctypes.c_int64 * 3)(*[int(v) for v in lo]), (ctypes.c_int64 * 3)(*[int(v) for v in hi]), (ctypes.c_int64 * 3)(*[int(v) for v in stride]))
+        except TypeError as e:
+            raise PfError(f"accumulator: lo, hi and stride are three integers each ({e})")
+        L = lib()
+        self._owner, self._f = owner, {k: getattr(L, f"{prefix}_accum_{k}") for k in ("create", "add", "get", "set", "destroy")}
+        self._a = ctypes.c_void_p()
+        _check(self._f["create"](owner._h, ctypes.byref(r), int(nchan), int(depth), ctypes.byref(self._a)))
+        counts = (ctypes.c_int64 * 3)()
+        L.pf_region_count(ctypes.byref(r), counts)
+        self.nchan = int(nchan)
+        self.shape = (self.nchan,) + tuple(int(c) for c in counts)  # of get()
+
+    def add(self, w):
+        """the sample of the step the owner stands at: acc[m] += w[m] * double(u^n), w: nchan doubles"""
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if w.size != self.nchan:
+            raise PfError(f"Accumulator.add: {w.size} weights for {self.nchan} channels")
+        _check(self._f["add"](self._owner._h, self._a, w.ctypes.data_as(ctypes.c_void_p)))
+
+    def get(self):
+        """-> float64 [nchan, c0, c1, c2]: the sums so far (pending samples folded in, nothing reset)"""
+        a = np.empty(self.shape, dtype=np.float64)
+        _check(self._f["get"](self._owner._h, self._a, a.ctypes.data_as(ctypes.c_void_p)))
+        return a
+
+    def set(self, a, count):
+        """replace sums and count (a = None: zeros); pending samples are dropped -- how a resumed run continues"""
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != int(np.prod(self.shape)):
+                raise PfError(f"Accumulator.set: {a.size} sums, the accumulator holds {int(np.prod(self.shape))}")
+        _check(self._f["set"](self._owner._h, self._a, None if a is None else a.ctypes.data_as(ctypes.c_void_p), int(count)))
+
+    @property
+    def count(self):
+        """samples added so far, or the count given to set"""
+        if not (self._a.value and self._alive()):
+            raise PfError("Accumulator.count: the accumulator or its owner is closed")
+        return int(lib().pf_accum_count(self._a))
+
+    def _alive(self):  # (an owner closed first took its accumulators with it: the handle is dead)
+        return bool(getattr(self._owner, "_h", None) and self._owner._h.value)
+
+    def close(self):
+        if getattr(self, "_a", None) and self._a.value:
+            if self._alive():
+                _check(self._f["destroy"](self._owner._h, self._a))
+            self._a = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def device_count():
@@ -318,6 +390,11 @@ class HipMulti:
         """A strided box of u^{n-1} (which = 0) or u^n (1) of the whole scene (pf_multi_get_region): every slab cuts the part it owns on its own
         device.  PfError with code 4 while a slab is inside a blocked pass: advance a step and ask again."""
         return _get_region(lib().pf_multi_get_region, self._h, np.float32 if self.sd.real_bytes == 4 else np.float64, which, lo, hi, stride)
+
+    def accumulator(self, lo, hi, stride=(1, 1, 1), nchan=1, depth=0):
+        """Running sums of a region of the whole scene (pf_multi_accum_create): every slab sums the part it owns on its own device.  add raises
+        PfError with code 4, and changes nothing, while any slab is inside a blocked pass: create the chain with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES."""
+        return Accumulator(self, "pf_multi", lo, hi, stride, nchan, depth)
 
     def slab(self, g):
         """-> dict(x0, x1, device, paired, steps_per_pass, engine): engine = a non-owning HipEngine view of slab g's engine (state_grids, timing)"""
@@ -466,6 +543,11 @@ class HipEngine:
         """A strided box of u^{n-1} (which = 0) or u^n (1) without copying the grid (pf_engine_get_region): the cells lo + k * stride < hi in
         FILE coordinates, as get_grid(which)[lo[0]:hi[0]:stride[0], lo[1]:hi[1]:stride[1], lo[2]:hi[2]:stride[2]]."""
         return _get_region(lib().pf_engine_get_region, self._h, self.dtype, which, lo, hi, stride)
+
+    def accumulator(self, lo, hi, stride=(1, 1, 1), nchan=1, depth=0):
+        """Running sums of the region's cells over the steps, on the device (pf_engine_accum_create): an Accumulator whose add(w) takes u^n --
+        get_region(1, lo, hi, stride) at the same moment -- as acc[m] += w[m] * double(u^n).  depth: samples folded in together (0: the default)."""
+        return Accumulator(self, "pf_engine", lo, hi, stride, nchan, depth)
 
     def set_grid(self, which, a):
         a = np.ascontiguousarray(a, dtype=self.dtype)

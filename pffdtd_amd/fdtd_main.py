@@ -33,13 +33,20 @@ steps `--field-first N` (default 0), N + K, ... into `--field-file FILE` (defaul
 describes the file).  The run is cut at the frame steps exactly as at checkpoint steps, and a chain inside a blocked pass takes the frame
 up to five steps later, recording where.  With `--resume` the file is appended to and the frames before the resumed step are kept.
 Same processes as the checkpoint arguments; without these arguments nothing about a run changes.
+
+Field spectra (pffdtd_amd/spectra.py): `--spectrum-planes` / `--spectrum-box` (the syntax of the field arguments) name regions whose cells' DFT at
+`--spectrum-freqs 63,125,250` (or `lo:hi:n`, linearly spaced) is summed ON THE DEVICE over the steps `--spectrum-first N` (default 0), N + K, ...
+(`--spectrum-every K`, default 1: every step), optionally under `--spectrum-window hann`, and written to `--spectrum-file FILE` (default
+sim_spectra.h5 beside sim_outs.h5) at every checkpoint and at the end.  The run is cut at the sample steps exactly as at frame and checkpoint
+steps; a sample is never taken at another step than its own, so a chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (one line says
+so).  `--resume` restores the sums from the file.  Same processes as the checkpoint arguments; without these arguments nothing about a run changes.
 """
 import argparse
 import os
 import time
 from pathlib import Path
 
-from . import checkpoint, engine, fields, sim_data
+from . import checkpoint, engine, fields, sim_data, spectra
 
 
 def _summary(sd, tm, el):
@@ -93,7 +100,7 @@ def _run_chain(a, sd, m):
     """all Nt steps of a chain object, in one go or in chunks with progress reports; returns (seconds, timing of the busiest slab).
     With --resume / --checkpoint / --stop-after: from the resumed step, to the step the run stops after (a.stopped_at: less than Nt then)."""
     live = range(m.nslabs)
-    if a.resume or a.checkpoint or a.field_every:
+    if a.resume or a.checkpoint or a.field_every or a.spectrum:
         return _run_chain_checkpointed(a, sd, m)
     t0 = time.perf_counter()
     if not a.progress:
@@ -133,8 +140,31 @@ def _field_writer(a, sd, resume_at):
         raise SystemExit(str(e))
 
 
+def _field_spectrum(a, sd, m, resume_at):
+    """the FieldSpectrum of --spectrum-planes / --spectrum-box on chain m (None without them); a resumed run's sums are restored"""
+    if not a.spectrum:
+        return None
+    N = (sd.Nx, sd.Ny, sd.Nz)
+    try:
+        regions = [r for spec in a.spectrum_planes for r in fields.parse_planes(spec, N)] + [fields.parse_box(spec, N) for spec in a.spectrum_box]
+        path = a.spectrum_file if a.spectrum_file else Path(a.data_dir) / "sim_spectra.h5"
+        fs = spectra.FieldSpectrum(path, sd, regions, spectra.parse_freqs(a.spectrum_freqs), a.spectrum_every, a.spectrum_first, a.spectrum_window, resume_at=resume_at)
+    except ValueError as e:
+        raise SystemExit(str(e).replace("--field-", "--spectrum-"))
+    fs.attach(m)
+    return fs
+
+
+def _chain_flags(a, nslabs):
+    """multi_flags of the chain: sampled for a spectrum, its slabs take single steps (a sample is never shifted, and no slab answers inside a pass)"""
+    if not a.spectrum or nslabs < 2:
+        return 0
+    print("--field spectrum: the chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (its slabs take single steps: every sample step can be sampled)")
+    return engine.PF_MULTI_NO_PAIRS | engine.PF_MULTI_NO_TRIPLES
+
+
 def _run_chain_checkpointed(a, sd, m):
-    """the run cut at checkpoint steps and at frame steps (--field-every)"""
+    """the run cut at checkpoint steps, at frame steps (--field-every) and at the sample steps of a spectrum (--spectrum-every)"""
     live = range(m.nslabs)
     n = 0
     if a.resume:
@@ -146,6 +176,7 @@ def _run_chain_checkpointed(a, sd, m):
         m.load_state(state)
         print(f"--resumed at step {n} of {sd.Nt}: {a.resume}", flush=True)
     fw = _field_writer(a, sd, n if a.resume else None)
+    fs = _field_spectrum(a, sd, m, n if a.resume else None)
     end = sd.Nt if a.stop_after is None else min(max(a.stop_after, n), sd.Nt)
     every = a.checkpoint_every if a.checkpoint else 0
     t0 = time.perf_counter()
@@ -153,6 +184,8 @@ def _run_chain_checkpointed(a, sd, m):
     if fw and fw.due(n) and n < end:  # (the frame of the first step: before any step of this run)
         n = fw.take(m, n)
         print(f"--field frame at step {n} of {sd.Nt}: {fw.path}", flush=True)
+    if fs and fs.due(n) and n < end:  # (a step's sample belongs to the run that takes the step: a stopped run leaves the sample of its last step to the resumed one)
+        fs.take(m, n)
     while n < end:
         k = end - n
         if a.progress:
@@ -161,6 +194,8 @@ def _run_chain_checkpointed(a, sd, m):
             k = min(k, every - n % every)
         if fw and fw.next_step(n + 1) < n + k:
             k = fw.next_step(n + 1) - n
+        if fs and fs.next_step(n + 1) < n + k:
+            k = fs.next_step(n + 1) - n
         tc = time.perf_counter()
         m.run(n, k)
         n += k
@@ -172,6 +207,10 @@ def _run_chain_checkpointed(a, sd, m):
         if save:
             n = _save_checkpoint(a, sd, m, n)
             end = max(end, n)
+            if fs:
+                fs.write()  # (the sums of the sample steps below n: what --resume of this checkpoint continues)
+        if fs and fs.due(n) and n < end:
+            fs.take(m, n)
         now = time.perf_counter()
         tms = [m.slab(g)["engine"].timing(reset=True) for g in live]
         air = max(t["air_ms_total"] for t in tms) * 1e-3
@@ -183,6 +222,10 @@ def _run_chain_checkpointed(a, sd, m):
         if a.progress:
             _progress(sd, n, sd.Nt, now - t0, now - tc, k, air_all, air, max(step_all - air_all, 1e-12), max(step - air, 1e-12), m.nslabs)
     a.stopped_at = n
+    if fs:
+        fs.write()
+        print(f"--field spectrum of {fs.count} samples at {fs.freqs.size} frequencies: {fs.path}", flush=True)
+        fs.close()
     return time.perf_counter() - t0, {"air_ms_total": air_all * 1e3, "step_ms_total": step_all * 1e3}
 
 
@@ -204,7 +247,7 @@ def run_single(a):
     sd.scale_input()
     from .dist import scene_prefers_exchanged_axes
     two = sd.Nz >= 64 and scene_prefers_exchanged_axes(sd)  # (`--devices 0` = one domain on device 0)
-    m = engine.HipMulti(sd, [a.gpu] * (2 if two else 1), timing=1)
+    m = engine.HipMulti(sd, [a.gpu] * (2 if two else 1), multi_flags=_chain_flags(a, 2 if two else 1), timing=1)
     if two:
         print(f"--2 slabs on device {a.gpu}, cut along file z: {[(m.slab(g)['x0'], m.slab(g)['x1']) for g in range(2)]}")
     # sub-timers: the busier slab's HIP-event sums (two slabs run side by side on the device)
@@ -224,7 +267,7 @@ def run_devices(a, devices):
     sd = sim_data.SimData.from_folder(Path(a.data_dir), a.precision, build_mask=False)
     sd.scale_input()
     try:  # (the library checks the slab count against the axis it actually cuts -- file x, or file z for rooms; gpu_engine.h:682)
-        m = engine.HipMulti(sd, devices, timing=1, verify_exchange=2)
+        m = engine.HipMulti(sd, devices, multi_flags=_chain_flags(a, len(devices)), timing=1, verify_exchange=2)
     except engine.PfError as e:
         raise SystemExit(f"cannot run on {len(devices)} slabs: {e}")
     info = m.info()
@@ -312,7 +355,19 @@ def main():
     p.add_argument("--field-every", type=int, default=0, metavar="K", help="record the field regions every K steps")
     p.add_argument("--field-first", type=int, default=0, metavar="N", help="... from step N on (default 0)")
     p.add_argument("--field-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_fields.h5 in the data folder)")
+    p.add_argument("--spectrum-planes", action="append", default=[], metavar="x=I,y=J,z=K", help="sum the DFT of these planes of the field on the device (the syntax of --field-planes)")
+    p.add_argument("--spectrum-box", action="append", default=[], metavar="x0:x1:sx,y0:y1:sy,z0:z1:sz", help="... of this strided box")
+    p.add_argument("--spectrum-freqs", default="", metavar="F1,F2,... | LO:HI:N", help="... at these frequencies in Hz (LO:HI:N: N of them, linearly spaced)")
+    p.add_argument("--spectrum-every", type=int, default=1, metavar="K", help="... sampling every K steps (default 1; content above 1 / (2 K Ts) aliases)")
+    p.add_argument("--spectrum-first", type=int, default=0, metavar="N", help="... from step N on (default 0)")
+    p.add_argument("--spectrum-window", default=None, choices=["hann"], help="... under a window over the sample steps (default: none)")
+    p.add_argument("--spectrum-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_spectra.h5 in the data folder)")
     a = p.parse_args()
+    a.spectrum = bool(a.spectrum_planes or a.spectrum_box)
+    if a.spectrum != bool(a.spectrum_freqs) or a.spectrum_every < 1 or a.spectrum_first < 0:
+        p.error("--spectrum-planes / --spectrum-box need --spectrum-freqs (and the other way round); --spectrum-every >= 1, --spectrum-first: not negative")
+    if (a.spectrum_first or a.spectrum_file or a.spectrum_window or a.spectrum_every != 1) and not a.spectrum:
+        p.error("--spectrum-every / --spectrum-first / --spectrum-window / --spectrum-file need --spectrum-planes or --spectrum-box")
     if bool(a.field_planes or a.field_box) != bool(a.field_every) or a.field_every < 0 or a.field_first < 0:
         p.error("--field-planes / --field-box need --field-every K >= 1 (and the other way round); --field-first: not negative")
     if (a.field_first or a.field_file) and not a.field_every:
@@ -326,6 +381,8 @@ def main():
         raise SystemExit("--checkpoint / --resume: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
     if world > 1 and a.field_every and not a.devices:
         raise SystemExit("--field-planes / --field-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
+    if world > 1 and a.spectrum and not a.devices:
+        raise SystemExit("--spectrum-planes / --spectrum-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
     if a.devices:
         return run_devices(a, [int(v) for v in a.devices.split(",")])
     if world > 1:
