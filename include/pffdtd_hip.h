@@ -409,6 +409,42 @@ int     pf_multi_accum_add     (pf_multi *m, pf_accum *a, const double *w);
 int     pf_multi_accum_get     (pf_multi *m, pf_accum *a, double *host);
 int     pf_multi_accum_set     (pf_multi *m, pf_accum *a, const double *host, int64_t count);
 int     pf_multi_accum_destroy (pf_multi *m, pf_accum *a);
+/* ---- band accumulators: per cell, the sample filtered by second-order sections, squared, summed into time bins -- on the device ----
+ * What an energy decay per octave band needs of every cell of an audience plane (EDT, T20 / T30, C50 / C80, D50, strength: pffdtd_amd/decay.py),
+ * and what the linear sums above cannot give.  A band accumulator belongs to one engine (or chain) and holds a region, npre shared sections,
+ * nband bands of nsec sections each, nbin time bins and a ring of `depth` samples.  No counterpart in the reference.
+ *   - A section is five doubles b0 b1 b2 a1 a2 (a0 = 1; scipy's sos rows without their fourth column) with state s1, s2 per cell, transposed
+ *     direct form II, every operation rounded to double once, no fused multiply-add, in exactly this association:
+ *            y  = b0*x + s1;     s1 = (b1*x - a1*y) + s2;     s2 = b2*x - a2*y
+ *     pre_sos[npre][5], band_sos[nband][nsec][5].  npre = nsec = 0: plain squares.
+ *   - pf_engine_bandacc_add(a, bin) takes u^n of the region exactly as pf_engine_accum_add does (the same cells, the same ghost-shell rule) and per
+ *     cell: x = (double)u through the shared sections in order; per band b, y = x through that band's sections; bin >= 0: E[b][bin] = E[b][bin] + y*y
+ *     (one multiplication, one addition); bin == -1: the filters run, nothing is summed.  Samples are applied in the order of the calls: the depth
+ *     (1 .. 16, 0 = the default) never changes a bit, and a numpy loop over time written with the three lines above gives the same bits.
+ *   - get folds what is pending and copies sums[nband][nbin][cells] and state[npre + nband*nsec][2][cells] out (s1, s2; the shared sections first,
+ *     then band 0's, ...), the cells dense in the region's order, z fastest; state may be NULL; nothing is reset.  set drops what is pending and
+ *     replaces sums, state (NULL: zeros) and the count: how a resumed run continues.  pf_bandacc_count: the samples added, or the count given to set.
+ *   - PF_ERR_STATE as pf_engine_accum_*.  PF_ERR_ARG, with a message that names the field, for a null pointer, nband outside 1 .. 16, npre or nsec
+ *     outside 0 .. 8, nbin < 1, depth outside 0 .. 16, a coefficient that is not finite, a region pf_engine_get_region would refuse, bin outside
+ *     -1 .. nbin-1, a negative count, and a handle that belongs to another engine or chain.  An engine created with pf_opts.energy answers.
+ *   - Several per engine are allowed; pf_engine_destroy / pf_multi_destroy free those left.
+ *   - Device memory, all of it the engine's: E nband*nbin rows and state (npre + nband*nsec)*2 rows of doubles (rows padded to an even cell
+ *     count), depth * cells Reals, and -- npre > 0 -- depth rows of doubles for the samples after the shared sections.
+ *   - A chain: as the field accumulators, one per slab over its part; add is all or nothing. */
+typedef struct pf_bandacc pf_bandacc;
+int     pf_engine_bandacc_create (pf_engine *e, const pf_region *r, int32_t npre, const double *pre_sos, int32_t nband, int32_t nsec, const double *band_sos,
+                                  int64_t nbin, int32_t depth, pf_bandacc **out);
+int     pf_engine_bandacc_add    (pf_engine *e, pf_bandacc *a, int64_t bin);
+int     pf_engine_bandacc_get    (pf_engine *e, pf_bandacc *a, double *sums, double *state);
+int     pf_engine_bandacc_set    (pf_engine *e, pf_bandacc *a, const double *sums, const double *state, int64_t count);
+int64_t pf_bandacc_count         (const pf_bandacc *a);
+int     pf_engine_bandacc_destroy(pf_engine *e, pf_bandacc *a);
+int     pf_multi_bandacc_create  (pf_multi *m, const pf_region *r, int32_t npre, const double *pre_sos, int32_t nband, int32_t nsec, const double *band_sos,
+                                  int64_t nbin, int32_t depth, pf_bandacc **out);
+int     pf_multi_bandacc_add     (pf_multi *m, pf_bandacc *a, int64_t bin);
+int     pf_multi_bandacc_get     (pf_multi *m, pf_bandacc *a, double *sums, double *state);
+int     pf_multi_bandacc_set     (pf_multi *m, pf_bandacc *a, const double *sums, const double *state, int64_t count);
+int     pf_multi_bandacc_destroy (pf_multi *m, pf_bandacc *a);
 int  pf_engine_timing(pf_engine *e, pf_timing *t, int32_t reset);
 /* switch the per-launch HIP events of pf_opts.timing on / off between runs (a host times its headline region without them
  * and collects kernel durations in a region of its own) */

@@ -78,25 +78,19 @@
       return PF_OK;
    }
 
-   int accum_add(void *h, const double *w) override {
-      const char *what = "pf_engine_accum_add";
-      if (!w) return set_err(PF_ERR_ARG, "%s: null weights", what);
-      Accum *a;
-      int rc = accum_enter(what, h, &a);
-      if (rc) return rc;
-      if ((lean || vg) && a->shell) { // the virtual ghost shell, exactly as get_region(1) writes it out
+   // u^n of a region -> a ring slot of `cells` Reals, dense (the accumulators' and the band accumulators' sample)
+   int region_to_slot(const pf_region &r, const int64_t *c, bool shell, Real *slot) {
+      if ((lean || vg) && shell) { // the virtual ghost shell, exactly as get_region(1) writes it out
          launch_flips(s_main, grids());
          HIPCHK(hipGetLastError());
       }
       // u^n of the region -> the next ring slot.  Pieces only where a launch's grid demands them (at most 65535 blocks along y and z): blocks of
       // planes, or -- more than 65535 rows in a plane -- runs of rows of one plane; both contiguous in the slot
-      Real *slot = a->ring + (int64_t)a->fill * a->cells;
-      const int64_t *c = a->c;
       const bool planes = c[1] <= 65535;
       const int64_t n0 = planes ? std::min<int64_t>(c[0], 65535) : 1, n1 = planes ? c[1] : 65535;
       for (int64_t i0 = 0; i0 < c[0]; i0 += n0)
          for (int64_t j0 = 0; j0 < c[1]; j0 += n1) {
-            const pf::RegionPiece q{a->r.lo[0] + i0 * a->r.stride[0], a->r.lo[1] + j0 * a->r.stride[1], a->r.lo[2], a->r.stride[0], a->r.stride[1], a->r.stride[2],
+            const pf::RegionPiece q{r.lo[0] + i0 * r.stride[0], r.lo[1] + j0 * r.stride[1], r.lo[2], r.stride[0], r.stride[1], r.stride[2],
                                     std::min(n0, c[0] - i0), std::min(n1, c[1] - j0), c[2]};
             const bool tiled = swz && q.n0 >= 2 && q.n2 >= 2;
             int bzl = 0;
@@ -108,6 +102,16 @@
             else hipLaunchKernelGGL((pf::k_region_cut<Real, false>), g, dim3(256), 0, s_main, (const Real *)u1, out, q, Ny, P, 0, bzl);
             HIPCHK(hipGetLastError());
          }
+      return PF_OK;
+   }
+
+   int accum_add(void *h, const double *w) override {
+      const char *what = "pf_engine_accum_add";
+      if (!w) return set_err(PF_ERR_ARG, "%s: null weights", what);
+      Accum *a;
+      int rc = accum_enter(what, h, &a);
+      if (rc) return rc;
+      if ((rc = region_to_slot(a->r, a->c, a->shell, a->ring + (int64_t)a->fill * a->cells))) return rc;
       memcpy(a->hwt.data() + (size_t)a->fill * a->nchan, w, (size_t)a->nchan * sizeof(double));
       a->fill++;
       if (a->fill == a->depth) return accum_fold(a);

@@ -30,6 +30,7 @@
 #include "pf_region.h"
 #include "pf_region_cut.h"
 #include "pf_accum.h"
+#include "pf_band.h"
 
 // shared between the two units (defined in pf_engine.hip)
 extern "C" void pf__set_error(const char *msg);
@@ -60,6 +61,11 @@ struct EngineBase {
    virtual int accum_get(void *a, double *host, int64_t pitch, int64_t chstride) = 0;
    virtual int accum_set(void *a, const double *host, int64_t pitch, int64_t chstride) = 0;
    virtual int accum_destroy(void *a) = 0;
+   virtual int band_create(const pf_region *r, int npre, const double *pre_sos, int nband, int nsec, const double *band_sos, int64_t nbin, int depth, void **out) = 0; // band accumulators (pf_engine_band.inc)
+   virtual int band_add(void *a, int64_t bin) = 0;
+   virtual int band_get(void *a, double *sums, double *state, int64_t pitch, int64_t rowstride) = 0;
+   virtual int band_set(void *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride) = 0;
+   virtual int band_destroy(void *a) = 0;
    virtual bool between_runs() const = 0; // not inside a split-phase step or pass
    virtual int save_state(pf_state *st) = 0;
    virtual int load_state(const pf_state *st) = 0;
@@ -1081,6 +1087,7 @@ template <typename Real> struct Engine : EngineBase {
 #include "pf_engine_state.inc"
 #include "pf_engine_region.inc"
 #include "pf_engine_accum.inc"
+#include "pf_engine_band.inc"
    void *stream(int which) override { return which == 1 ? (void *)s_edge : (void *)s_main; }
 };
 

@@ -98,6 +98,8 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_grid_bytes", "p
            "pf_multi_save_state", "pf_multi_load_state", "pf_region_count", "pf_engine_get_region", "pf_multi_get_region", "pf_engine_timing", "pf_engine_set_timing",
            "pf_engine_accum_create", "pf_engine_accum_add", "pf_engine_accum_get", "pf_engine_accum_set", "pf_engine_accum_destroy", "pf_accum_count",
            "pf_multi_accum_create", "pf_multi_accum_add", "pf_multi_accum_get", "pf_multi_accum_set", "pf_multi_accum_destroy",
+           "pf_engine_bandacc_create", "pf_engine_bandacc_add", "pf_engine_bandacc_get", "pf_engine_bandacc_set", "pf_engine_bandacc_destroy", "pf_bandacc_count",
+           "pf_multi_bandacc_create", "pf_multi_bandacc_add", "pf_multi_bandacc_get", "pf_multi_bandacc_set", "pf_multi_bandacc_destroy",
            "pf_engine_energy_cfg", "pf_engine_run_energy", "pf_run_sim_devices", "pf_slab_partition", "pf_slab_partition_w", "pf_slab_partition_axis", "pf_slab_wall_scale",
            "pf_multi_create", "pf_multi_run", "pf_multi_get_info", "pf_multi_get_slab", "pf_multi_destroy",
            "pf_rccl_unique_id", "pf_rccl_comm_create", "pf_rccl_exchange", "pf_rccl_comm_destroy"]
@@ -191,8 +193,15 @@ def lib():
             getattr(L, pre + "_accum_get").argtypes = [vp, vp, vp]
             getattr(L, pre + "_accum_set").argtypes = [vp, vp, vp, i64]
             getattr(L, pre + "_accum_destroy").argtypes = [vp, vp]
+            getattr(L, pre + "_bandacc_create").argtypes = [vp, ctypes.POINTER(PfRegion), i32, vp, i32, i32, vp, i64, i32, ctypes.POINTER(vp)]
+            getattr(L, pre + "_bandacc_add").argtypes = [vp, vp, i64]
+            getattr(L, pre + "_bandacc_get").argtypes = [vp, vp, vp, vp]
+            getattr(L, pre + "_bandacc_set").argtypes = [vp, vp, vp, vp, i64]
+            getattr(L, pre + "_bandacc_destroy").argtypes = [vp, vp]
         L.pf_accum_count.restype = i64
         L.pf_accum_count.argtypes = [vp]
+        L.pf_bandacc_count.restype = i64
+        L.pf_bandacc_count.argtypes = [vp]
         dp = ctypes.POINTER(ctypes.c_double)
         L.pf_engine_energy_cfg.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, dp]
         L.pf_engine_run_energy.argtypes = [vp, i64, i64, dp, dp, dp]
@@ -302,6 +311,93 @@ class Accumulator:
             pass
 
 
+def _sos5(name, sos, lead):
+    """scipy-style rows [.., 6] (b0 b1 b2 a0 a1 a2, a0 = 1) -> float64 [.., 5] as the C ABI takes them; `lead` leading dimensions"""
+    a = np.asarray([] if sos is None else sos, dtype=np.float64)
+    if a.size == 0:
+        return np.zeros((0,) * lead + (5,))
+    if a.ndim != lead + 1 or a.shape[-1] != 6:
+        raise PfError(f"band_accumulator: {name} has shape {a.shape}: {'[npre, 6]' if lead == 1 else '[nband, nsec, 6]'} rows b0 b1 b2 a0 a1 a2 are expected")
+    if not np.all(a[..., 3] == 1.0):
+        raise PfError(f"band_accumulator: {name}: a0 != 1 in a section (normalise the rows: scipy's sos output has a0 = 1)")
+    return np.ascontiguousarray(a[..., [0, 1, 2, 4, 5]])
+
+
+class BandAccumulator:
+    """Per cell of a region, on the device (pf_engine_bandacc_* / pf_multi_bandacc_*): u^n through the shared sections pre_sos [npre, 6], then per
+    band through band_sos [nband, nsec, 6] (scipy's sos rows, a0 = 1), squared and summed into time bin `bin` at every add(bin).
+    Made by HipEngine.band_accumulator / HipMulti.band_accumulator; it lives no longer than the object that made it."""
+
+    def __init__(self, owner, prefix, lo, hi, stride, pre_sos, band_sos, nbin, depth):
+        try:
+            r = PfRegion((ctypes.c_int64 * 3)(*[int(v) for v in lo]), (ctypes.c_int64 * 3)(*[int(v) for v in hi]), (ctypes.c_int64 * 3)(*[int(v) for v in stride]))
+        except TypeError as e:
+            raise PfError(f"band_accumulator: lo, hi and stride are three integers each ({e})")
+        pre = _sos5("pre_sos", pre_sos, 1)
+        b = np.asarray(band_sos, dtype=np.float64)
+        if b.ndim == 3 and b.shape[1] == 0:  # nband bands without sections: plain squares of what the shared sections give
+            band, nband = np.zeros((b.shape[0], 0, 5)), b.shape[0]
+        else:
+            band = _sos5("band_sos", band_sos, 2)
+            nband = band.shape[0] if band.ndim == 3 else 0
+        L = lib()
+        self._owner, self._f = owner, {k: getattr(L, f"{prefix}_bandacc_{k}") for k in ("create", "add", "get", "set", "destroy")}
+        self._a = ctypes.c_void_p()
+        self.npre, self.nband, self.nsec, self.nbin = int(pre.shape[0]), int(nband), int(band.shape[1]) if band.ndim == 3 else 0, int(nbin)
+        vp = ctypes.c_void_p
+        _check(self._f["create"](owner._h, ctypes.byref(r), self.npre, pre.ctypes.data_as(vp) if pre.size else None, self.nband, self.nsec,
+                                 band.ctypes.data_as(vp) if band.size else None, self.nbin, int(depth), ctypes.byref(self._a)))
+        counts = (ctypes.c_int64 * 3)()
+        L.pf_region_count(ctypes.byref(r), counts)
+        cells = tuple(int(c) for c in counts)
+        self.shape = (self.nband, self.nbin) + cells  # of get()'s sums
+        self.state_shape = (self.npre + self.nband * self.nsec, 2) + cells  # ... and state
+
+    def add(self, bin):
+        """the sample of the step the owner stands at, summed into time bin `bin` (-1: the filters run, nothing is summed)"""
+        _check(self._f["add"](self._owner._h, self._a, int(bin)))
+
+    def get(self, state=True):
+        """-> (sums float64 [nband, nbin, c0, c1, c2], state float64 [npre + nband * nsec, 2, c0, c1, c2] or None): pending samples folded in, nothing reset"""
+        e = np.empty(self.shape, dtype=np.float64)
+        s = np.empty(self.state_shape, dtype=np.float64) if state else None
+        _check(self._f["get"](self._owner._h, self._a, e.ctypes.data_as(ctypes.c_void_p), s.ctypes.data_as(ctypes.c_void_p) if state and s.size else None))
+        return e, s
+
+    def set(self, sums, state, count):
+        """replace sums, filter state and count (None: zeros); pending samples are dropped -- how a resumed run continues"""
+        arrs = []
+        for name, a, shape in (("sums", sums, self.shape), ("state", state, self.state_shape)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.size != int(np.prod(shape)):
+                    raise PfError(f"BandAccumulator.set: {name} has {a.size} elements, the accumulator holds {int(np.prod(shape))}")
+            arrs.append(a)
+        _check(self._f["set"](self._owner._h, self._a, *[None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p) for a in arrs], int(count)))
+
+    @property
+    def count(self):
+        """samples added so far, or the count given to set"""
+        if not (self._a.value and self._alive()):
+            raise PfError("BandAccumulator.count: the accumulator or its owner is closed")
+        return int(lib().pf_bandacc_count(self._a))
+
+    def _alive(self):
+        return bool(getattr(self._owner, "_h", None) and self._owner._h.value)
+
+    def close(self):
+        if getattr(self, "_a", None) and self._a.value:
+            if self._alive():
+                _check(self._f["destroy"](self._owner._h, self._a))
+            self._a = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def device_count():
     return int(lib().pf_device_count())
 
@@ -395,6 +491,11 @@ class HipMulti:
         """Running sums of a region of the whole scene (pf_multi_accum_create): every slab sums the part it owns on its own device.  add raises
         PfError with code 4, and changes nothing, while any slab is inside a blocked pass: create the chain with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES."""
         return Accumulator(self, "pf_multi", lo, hi, stride, nchan, depth)
+
+    def band_accumulator(self, lo, hi, stride=(1, 1, 1), pre_sos=None, band_sos=None, nbin=1, depth=0):
+        """Band-filtered squares of a region of the whole scene in time bins (pf_multi_bandacc_create): every slab keeps the part it owns.  add raises
+        PfError with code 4, and changes nothing, while any slab is inside a blocked pass."""
+        return BandAccumulator(self, "pf_multi", lo, hi, stride, pre_sos, band_sos, nbin, depth)
 
     def slab(self, g):
         """-> dict(x0, x1, device, paired, steps_per_pass, engine): engine = a non-owning HipEngine view of slab g's engine (state_grids, timing)"""
@@ -548,6 +649,11 @@ class HipEngine:
         """Running sums of the region's cells over the steps, on the device (pf_engine_accum_create): an Accumulator whose add(w) takes u^n --
         get_region(1, lo, hi, stride) at the same moment -- as acc[m] += w[m] * double(u^n).  depth: samples folded in together (0: the default)."""
         return Accumulator(self, "pf_engine", lo, hi, stride, nchan, depth)
+
+    def band_accumulator(self, lo, hi, stride=(1, 1, 1), pre_sos=None, band_sos=None, nbin=1, depth=0):
+        """Per cell of the region, on the device (pf_engine_bandacc_create): u^n through the second-order sections pre_sos [npre, 6] and, per band,
+        band_sos [nband, nsec, 6] (scipy's rows, a0 = 1), squared, summed into the time bin given to add(bin) -- a BandAccumulator."""
+        return BandAccumulator(self, "pf_engine", lo, hi, stride, pre_sos, band_sos, nbin, depth)
 
     def set_grid(self, which, a):
         a = np.ascontiguousarray(a, dtype=self.dtype)

@@ -40,6 +40,13 @@ Field spectra (pffdtd_amd/spectra.py): `--spectrum-planes` / `--spectrum-box` (t
 sim_spectra.h5 beside sim_outs.h5) at every checkpoint and at the end.  The run is cut at the sample steps exactly as at frame and checkpoint
 steps; a sample is never taken at another step than its own, so a chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (one line says
 so).  `--resume` restores the sums from the file.  Same processes as the checkpoint arguments; without these arguments nothing about a run changes.
+
+Energy decay maps (pffdtd_amd/decay.py): `--decay-planes` / `--decay-box` (the syntax of the field arguments) name regions whose cells' pressure is
+filtered into the octave bands `--decay-bands 125,250,500` (centre frequencies in Hz), squared and summed ON THE DEVICE into time bins of
+`--decay-bin-ms 5` milliseconds, at EVERY step from `--decay-first N` (default 0) on, and written to `--decay-file FILE` (default sim_decay.h5
+beside sim_outs.h5) at every checkpoint and at the end.  The run is cut at every step from N on; a chain is created with
+PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (one line says so).  `--resume` restores sums and filter state from the file.  Same processes as the
+checkpoint arguments; without these arguments nothing about a run changes.  (`--energy` is not a name of these: it stays the diagnostic's.)
 """
 import argparse
 import os
@@ -47,6 +54,7 @@ import time
 from pathlib import Path
 
 from . import checkpoint, engine, fields, sim_data, spectra
+from . import decay as decay_mod
 
 
 def _summary(sd, tm, el):
@@ -100,7 +108,7 @@ def _run_chain(a, sd, m):
     """all Nt steps of a chain object, in one go or in chunks with progress reports; returns (seconds, timing of the busiest slab).
     With --resume / --checkpoint / --stop-after: from the resumed step, to the step the run stops after (a.stopped_at: less than Nt then)."""
     live = range(m.nslabs)
-    if a.resume or a.checkpoint or a.field_every or a.spectrum:
+    if a.resume or a.checkpoint or a.field_every or a.spectrum or a.decay:
         return _run_chain_checkpointed(a, sd, m)
     t0 = time.perf_counter()
     if not a.progress:
@@ -155,10 +163,30 @@ def _field_spectrum(a, sd, m, resume_at):
     return fs
 
 
+def _field_decay(a, sd, m, resume_at):
+    """the FieldDecay of --decay-planes / --decay-box on chain m (None without them); a resumed run's sums and filter state are restored"""
+    if not a.decay:
+        return None
+    N = (sd.Nx, sd.Ny, sd.Nz)
+    try:
+        regions = [r for spec in a.decay_planes for r in fields.parse_planes(spec, N)] + [fields.parse_box(spec, N) for spec in a.decay_box]
+        path = a.decay_file if a.decay_file else Path(a.data_dir) / "sim_decay.h5"
+        fd = decay_mod.FieldDecay(path, sd, regions, decay_mod.parse_bands(a.decay_bands), a.decay_bin_ms, a.decay_first, resume_at=resume_at)
+    except ValueError as e:
+        raise SystemExit(str(e).replace("--field-", "--decay-"))
+    fd.attach(m)
+    return fd
+
+
 def _chain_flags(a, nslabs):
-    """multi_flags of the chain: sampled for a spectrum, its slabs take single steps (a sample is never shifted, and no slab answers inside a pass)"""
-    if not a.spectrum or nslabs < 2:
+    """multi_flags of the chain: sampled for a spectrum or a decay map, its slabs take single steps (a sample is never shifted, and no slab answers
+    inside a pass)"""
+    if not (a.spectrum or a.decay) or nslabs < 2:
         return 0
+    if a.decay:
+        print("--field decay: the chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (its slabs take single steps: every step is sampled)")
+    if not a.spectrum:
+        return engine.PF_MULTI_NO_PAIRS | engine.PF_MULTI_NO_TRIPLES
     print("--field spectrum: the chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (its slabs take single steps: every sample step can be sampled)")
     return engine.PF_MULTI_NO_PAIRS | engine.PF_MULTI_NO_TRIPLES
 
@@ -177,6 +205,7 @@ def _run_chain_checkpointed(a, sd, m):
         print(f"--resumed at step {n} of {sd.Nt}: {a.resume}", flush=True)
     fw = _field_writer(a, sd, n if a.resume else None)
     fs = _field_spectrum(a, sd, m, n if a.resume else None)
+    fd = _field_decay(a, sd, m, n if a.resume else None)
     end = sd.Nt if a.stop_after is None else min(max(a.stop_after, n), sd.Nt)
     every = a.checkpoint_every if a.checkpoint else 0
     t0 = time.perf_counter()
@@ -186,6 +215,8 @@ def _run_chain_checkpointed(a, sd, m):
         print(f"--field frame at step {n} of {sd.Nt}: {fw.path}", flush=True)
     if fs and fs.due(n) and n < end:  # (a step's sample belongs to the run that takes the step: a stopped run leaves the sample of its last step to the resumed one)
         fs.take(m, n)
+    if fd and fd.due(n) and n < end:
+        fd.take(m, n)
     while n < end:
         k = end - n
         if a.progress:
@@ -196,6 +227,8 @@ def _run_chain_checkpointed(a, sd, m):
             k = fw.next_step(n + 1) - n
         if fs and fs.next_step(n + 1) < n + k:
             k = fs.next_step(n + 1) - n
+        if fd and fd.next_step(n + 1) < n + k:
+            k = fd.next_step(n + 1) - n
         tc = time.perf_counter()
         m.run(n, k)
         n += k
@@ -209,8 +242,12 @@ def _run_chain_checkpointed(a, sd, m):
             end = max(end, n)
             if fs:
                 fs.write()  # (the sums of the sample steps below n: what --resume of this checkpoint continues)
+            if fd:
+                fd.write()
         if fs and fs.due(n) and n < end:
             fs.take(m, n)
+        if fd and fd.due(n) and n < end:
+            fd.take(m, n)
         now = time.perf_counter()
         tms = [m.slab(g)["engine"].timing(reset=True) for g in live]
         air = max(t["air_ms_total"] for t in tms) * 1e-3
@@ -226,6 +263,10 @@ def _run_chain_checkpointed(a, sd, m):
         fs.write()
         print(f"--field spectrum of {fs.count} samples at {fs.freqs.size} frequencies: {fs.path}", flush=True)
         fs.close()
+    if fd:
+        fd.write()
+        print(f"--field decay of {fd.count} samples in {fd.bands.size} bands, bins of {fd.bin_steps} steps: {fd.path}", flush=True)
+        fd.close()
     return time.perf_counter() - t0, {"air_ms_total": air_all * 1e3, "step_ms_total": step_all * 1e3}
 
 
@@ -362,7 +403,18 @@ def main():
     p.add_argument("--spectrum-first", type=int, default=0, metavar="N", help="... from step N on (default 0)")
     p.add_argument("--spectrum-window", default=None, choices=["hann"], help="... under a window over the sample steps (default: none)")
     p.add_argument("--spectrum-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_spectra.h5 in the data folder)")
+    p.add_argument("--decay-planes", action="append", default=[], metavar="x=I,y=J,z=K", help="sum the band-filtered, squared field of these planes into time bins on the device (the syntax of --field-planes)")
+    p.add_argument("--decay-box", action="append", default=[], metavar="x0:x1:sx,y0:y1:sy,z0:z1:sz", help="... of this strided box")
+    p.add_argument("--decay-bands", default="", metavar="F1,F2,...", help="... in the octave bands around these centre frequencies in Hz")
+    p.add_argument("--decay-bin-ms", type=float, default=5.0, metavar="MS", help="... in time bins of MS milliseconds (default 5)")
+    p.add_argument("--decay-first", type=int, default=0, metavar="N", help="... at every step from N on (default 0)")
+    p.add_argument("--decay-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_decay.h5 in the data folder)")
     a = p.parse_args()
+    a.decay = bool(a.decay_planes or a.decay_box)
+    if a.decay != bool(a.decay_bands) or a.decay_bin_ms <= 0 or a.decay_first < 0:
+        p.error("--decay-planes / --decay-box need --decay-bands (and the other way round); --decay-bin-ms: positive, --decay-first: not negative")
+    if (a.decay_first or a.decay_file or a.decay_bin_ms != 5.0) and not a.decay:
+        p.error("--decay-bin-ms / --decay-first / --decay-file need --decay-planes or --decay-box")
     a.spectrum = bool(a.spectrum_planes or a.spectrum_box)
     if a.spectrum != bool(a.spectrum_freqs) or a.spectrum_every < 1 or a.spectrum_first < 0:
         p.error("--spectrum-planes / --spectrum-box need --spectrum-freqs (and the other way round); --spectrum-every >= 1, --spectrum-first: not negative")
@@ -383,6 +435,8 @@ def main():
         raise SystemExit("--field-planes / --field-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
     if world > 1 and a.spectrum and not a.devices:
         raise SystemExit("--spectrum-planes / --spectrum-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
+    if world > 1 and a.decay and not a.devices:
+        raise SystemExit("--decay-planes / --decay-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
     if a.devices:
         return run_devices(a, [int(v) for v in a.devices.split(",")])
     if world > 1:

@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""What a band accumulator costs per sample, and which depth of its ring is fastest: pf_engine_bandacc_add against the engine's own steps.
+
+  tools/field_decay_cost.py [--size 512] [--reps 7] [--out profiles/field_decay.txt]
+
+On a shoebox size^3, fp32 (synth.shoebox), once stored in file order and once with the x and z axes exchanged, in one process:
+  * a size^2 z plane and a 64^3 box, 6 octave bands of 3 sections each and 2 shared sections (what pffdtd_amd/decay.py builds for order 3 and the
+    integrator + low-cut of order 4), 40 time bins, the bin changing every 16 samples;
+  * ms per sample at depths 1, 4, 8 and 16: wall time around 16 adds that end in a device synchronise (16 is a multiple of every depth measured, so
+    every timing holds whole folds), over 16, after a warm-up of the same 16; the median of --reps repetitions in which the depths ALTERNATE;
+  * beside them the same engine's wall time per single step (run(n, 1)) without any accumulator call in between.
+No threshold is fixed in advance.  Recorded at the end: the depth with the smallest sum of medians over the plane cases, which
+PF_BAND_DEFAULT_DEPTH (csrc/pf_band.h) is to equal.  Needs a GPU; there is no fallback.
+"""
+import argparse
+import statistics
+import sys
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tools"))
+from checkpoint_cost import timed  # noqa: E402
+from pffdtd_amd import decay, engine, sim_data, synth  # noqa: E402
+
+BATCH = 16
+DEPTHS = (1, 4, 8, 16)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "field_decay.txt"))
+    a = ap.parse_args()
+    if engine.device_count() < 1:
+        raise SystemExit("no HIP device visible: nothing can be measured here")
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    n = a.size
+    sd = sim_data.SimData.from_sim(synth.shoebox(n, n, n, Nt=16 + a.reps + 8, Nm=1, Mb=3), "single", build_mask=False)
+    sd.scale_input()
+    Ts = 1.0 / 25500.0
+    pre = decay.pre_sections(Ts, True, 10.0, 4)
+    bands = decay.band_sections(Ts, [125.0, 250.0, 500.0, 1000.0, 2000.0, 4000.0], 3)
+    assert pre.shape == (2, 6) and bands.shape == (6, 3, 6)
+    h, b0 = n // 2, n // 2 - 32
+    shapes = [(f"{n}^2 z plane", ([0, 0, h], [n, n, h + 1])), ("64^3 box", ([b0] * 3, [b0 + 64] * 3))]
+    nbin = 40
+    say(f"band accumulators: shoebox {n}^3 fp32, 6 bands x 3 sections + 2 shared, ms per sample (wall time of {BATCH} adds and a synchronise, over {BATCH}), "
+        f"median of {a.reps} alternating repetitions")
+    plane_sum = {d: 0.0 for d in DEPTHS}
+    for name, layout in (("file order", engine.PF_LAYOUT_FILE), ("exchanged axes", engine.PF_LAYOUT_EXCHANGED)):
+        eng = engine.HipEngine(sd, layout=layout)
+        assert eng.layout()[2] == (layout == engine.PF_LAYOUT_EXCHANGED)
+        eng.run(0, 16)
+        eng.sync()
+        step = 16
+        t1 = []
+        for _ in range(a.reps):  # the engine alone: no accumulator exists yet
+            t1.append(timed(lambda: (eng.run(step, 1), eng.sync()))[0] * 1e3)
+            step += 1
+        say(f"{name}: the engine alone: a single step {statistics.median(t1):.3f} ms (min {min(t1):.3f})")
+        for label, (lo, hi) in shapes:
+            accs = {d: eng.band_accumulator(lo, hi, pre_sos=pre, band_sos=bands, nbin=nbin, depth=d) for d in DEPTHS}
+            batches = {d: 0 for d in DEPTHS}
+
+            def batch(d):
+                for _ in range(BATCH):
+                    accs[d].add(batches[d] % nbin)
+                eng.sync()
+                batches[d] += 1
+
+            ms = {d: [] for d in DEPTHS}
+            for d in DEPTHS:
+                batch(d)  # warm-up: the code objects of this depth's fold
+            for _ in range(a.reps):
+                for d in DEPTHS:
+                    ms[d].append(timed(lambda: batch(d))[0] * 1e3 / BATCH)
+            med = {d: statistics.median(ms[d]) for d in DEPTHS}
+            for d in DEPTHS:
+                say(f"  {label:13s} depth {d:2d}: {med[d]:8.4f} ms per sample (min {min(ms[d]):.4f}, max {max(ms[d]):.4f})   {100 * med[d] / statistics.median(t1):5.1f} % of a single step")
+                if "plane" in label:
+                    plane_sum[d] += med[d]
+            for acc in accs.values():
+                assert acc.count == BATCH * (a.reps + 1)
+                acc.close()
+        eng.close()
+    best = min(DEPTHS, key=lambda d: plane_sum[d])
+    say("sum of the plane cases' medians per depth: " + ", ".join(f"{d}: {plane_sum[d]:.4f} ms" for d in DEPTHS) + f"  ->  the default depth these measurements justify: {best}")
+    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(a.out).write_text("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
