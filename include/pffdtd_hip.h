@@ -445,6 +445,53 @@ int     pf_multi_bandacc_add     (pf_multi *m, pf_bandacc *a, int64_t bin);
 int     pf_multi_bandacc_get     (pf_multi *m, pf_bandacc *a, double *sums, double *state);
 int     pf_multi_bandacc_set     (pf_multi *m, pf_bandacc *a, const double *sums, const double *state, int64_t count);
 int     pf_multi_bandacc_destroy (pf_multi *m, pf_bandacc *a);
+/* ---- vector band accumulators: per cell, up to four COMPONENTS of the field filtered, PRODUCTS of two of them summed into time bins -- on the device ----
+ * What a quantity that needs the field's direction asks of every cell of an audience plane: the lateral energy fraction LF / LFC of ISO 3382-1 and
+ * the sound intensity per band and time bin (pffdtd_amd/directional.py).  A pf_bandacc squares one input; two of them cannot be multiplied after the
+ * fact, because the product is formed per sample.  A vector band accumulator belongs to one engine (or chain) and holds a region, ncomp components,
+ * npre sections PER COMPONENT, nband bands of nsec sections each (coefficients shared by the components, state per component), nprod products, nbin
+ * time bins and a ring of `depth` samples.  No counterpart in the reference.
+ *   - comp[ncomp], ncomp 1 .. 4, no value twice.  Component 0 is the cell itself: exactly what pf_engine_bandacc_add samples.  Component a = 1, 2, 3 is
+ *     the central difference along FILE x, y, z:   d_a(c) = u^n[c + e_a] - u^n[c - e_a],   ONE subtraction in the field's own precision, rounded once
+ *     (numpy: u[hi] - u[lo] in the field's dtype), each operand bit for bit the cell pf_engine_get_region(1, ...) gives for it.  The difference is
+ *     kept in the field's precision until the filters widen it.
+ *   - A region with a difference component along axis a keeps one cell clear of both faces along a: lo[a] >= 1 and its last cell <= N[a] - 2;
+ *     otherwise PF_ERR_ARG names the axis.  The virtual ghost shell is materialised when the region, WIDENED by one cell along its difference axes,
+ *     holds a face cell: the pf_engine_get_region rule applied to the cells actually read.
+ *   - Difference components are refused by name on fcc_flag != 0: an axis neighbour at +-1 is no node of the checkerboard, and a stencil over the
+ *     FCC neighbours is out of scope here.  comp = {0} alone works on every grid.
+ *   - pre_sos[ncomp][npre][5] (npre 0 .. 8; a shorter cascade is padded with 1 0 0 0 0), band_sos[nband][nsec][5]; a section and its three lines
+ *     exactly as pf_bandacc above: the same association, every operation rounded to double once, no fused multiply-add.  Per component k,
+ *     x_k = (double)component runs through pre_sos[k] in order; for every band b, y_k = x_k runs through band_sos[b] with component k's own state.
+ *   - prod[nprod][3], nprod 1 .. 10, rows (i, j, mode) with i, j < ncomp.  bin >= 0, mode 0: S[p][b][bin] = S[p][b][bin] + y_i * y_j (one
+ *     multiplication, one addition); mode 1: S[p][b][bin] + fabs(y_i * y_j).  bin == -1: the filters run, nothing is summed.  Samples are applied in
+ *     the order of the calls: the depth (1 .. 8, 0 = the default) never changes a bit, and a numpy loop over time written with those lines
+ *     gives the same bits.
+ *   - get folds what is pending and copies sums[nprod][nband][nbin][cells] and state[ncomp][npre + nband*nsec][2][cells] out (per component: its pre
+ *     sections first, then band 0's, ...), the cells dense in the region's order, z fastest; state may be NULL; nothing is reset.  set drops what is
+ *     pending and replaces sums, state (NULL: zeros) and the count.  pf_vbandacc_count: the samples added, or the count given to set.
+ *   - Between runs only, PF_ERR_STATE, an engine created with pf_opts.energy, handles of another engine or chain, several per engine, freeing by
+ *     pf_engine_destroy / pf_multi_destroy: all as pf_bandacc.  PF_ERR_ARG, with a message that names the field, also for ncomp outside 1 .. 4, a
+ *     comp value outside 0 .. 3, a repeated component, nprod outside 1 .. 10, a product index >= ncomp, a mode outside 0 / 1, a coefficient that is
+ *     not finite, depth outside 0 .. 8.
+ *   - Device memory, all of it the engine's: nprod*nband*nbin rows of sums and ncomp*(npre + nband*nsec)*2 rows of state (doubles, rows padded to an
+ *     even cell count), ncomp * depth * cells Reals, and -- npre > 0 -- ncomp * depth rows of doubles.
+ *   - A chain: as the band accumulators, one per slab over its part; add is all or nothing.  A difference across the cut reads the slab's ghost
+ *     plane, which between runs holds the neighbour's u^n (the exchange of the step that wrote u^n filled it; pf_multi_load_state fills it). */
+typedef struct pf_vbandacc pf_vbandacc;
+int     pf_engine_vband_create (pf_engine *e, const pf_region *r, int32_t ncomp, const int32_t *comp, int32_t npre, const double *pre_sos, int32_t nband, int32_t nsec,
+                                const double *band_sos, int32_t nprod, const int32_t *prod, int64_t nbin, int32_t depth, pf_vbandacc **out);
+int     pf_engine_vband_add    (pf_engine *e, pf_vbandacc *a, int64_t bin);
+int     pf_engine_vband_get    (pf_engine *e, pf_vbandacc *a, double *sums, double *state);
+int     pf_engine_vband_set    (pf_engine *e, pf_vbandacc *a, const double *sums, const double *state, int64_t count);
+int64_t pf_vbandacc_count      (const pf_vbandacc *a);
+int     pf_engine_vband_destroy(pf_engine *e, pf_vbandacc *a);
+int     pf_multi_vband_create  (pf_multi *m, const pf_region *r, int32_t ncomp, const int32_t *comp, int32_t npre, const double *pre_sos, int32_t nband, int32_t nsec,
+                                const double *band_sos, int32_t nprod, const int32_t *prod, int64_t nbin, int32_t depth, pf_vbandacc **out);
+int     pf_multi_vband_add     (pf_multi *m, pf_vbandacc *a, int64_t bin);
+int     pf_multi_vband_get     (pf_multi *m, pf_vbandacc *a, double *sums, double *state);
+int     pf_multi_vband_set     (pf_multi *m, pf_vbandacc *a, const double *sums, const double *state, int64_t count);
+int     pf_multi_vband_destroy (pf_multi *m, pf_vbandacc *a);
 int  pf_engine_timing(pf_engine *e, pf_timing *t, int32_t reset);
 /* switch the per-launch HIP events of pf_opts.timing on / off between runs (a host times its headline region without them
  * and collects kernel durations in a region of its own) */

@@ -49,6 +49,19 @@ struct pf_bandacc {
 // pf_engine_bandacc_get / _set with the caller's region rows `pitch` and sum / state rows `rowstride` doubles apart (0: dense) -- a slab's cells of a chain's arrays
 int pf__engine_bandacc_get_x(pf_engine *e, pf_bandacc *a, double *sums, double *state, int64_t pitch, int64_t rowstride);
 int pf__engine_bandacc_set_x(pf_engine *e, pf_bandacc *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride, int64_t count);
+// A vector band accumulator's handle (pffdtd_hip.h: pf_vbandacc): as pf_bandacc.
+struct pf_vbandacc {
+   pf_engine *eng = nullptr;
+   void *impl = nullptr;
+   pf_multi *chain = nullptr;
+   std::vector<pf_vbandacc *> part;
+   pf_region region{};
+   int64_t rc[3] = {0, 0, 0}, cells = 0;
+   int64_t nbin = 0, count = 0;
+};
+// pf_engine_vband_get / _set with the caller's region rows `pitch` and sum / state rows `rowstride` doubles apart (0: dense) -- a slab's cells of a chain's arrays
+int pf__engine_vband_get_x(pf_engine *e, pf_vbandacc *a, double *sums, double *state, int64_t pitch, int64_t rowstride);
+int pf__engine_vband_set_x(pf_engine *e, pf_vbandacc *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride, int64_t count);
 int pf__engine_between_runs(pf_engine *e); // 1: not inside a split-phase step or pass (what pf_engine_accum_add needs)
 enum : int {
    PF_DBG_BRANCH_SELECTS = 0x1,       // three-step wall regions: fd_regs' select form (a branch count per lane) even where every material has the same count

@@ -52,6 +52,7 @@ struct pf_engine {
    pfeng::EngineBase *impl;
    std::vector<pf_accum *> accums; // the handles of its field accumulators still alive (pf_engine_destroy frees those left)
    std::vector<pf_bandacc *> bands; // ... and of its band accumulators
+   std::vector<pf_vbandacc *> vbands; // ... and of its vector band accumulators
 };
 pfeng::EngineBase *pf__new_engine_f64(const pf_simdata *sd, const pf_opts_x *o, int *rc); // pf_engine_f64.hip
 
@@ -125,7 +126,7 @@ int pf__engine_create_x(const pf_simdata *sd, const pf_opts_x *opts, pf_engine *
       return set_err(PF_ERR_ARG, "real_bytes must be 4 or 8 (got %d)", sd->real_bytes);
    }
    if (rc) { std::string keep = g_err; delete impl; g_err = keep; return rc; }
-   *out = new pf_engine{impl, {}, {}};
+   *out = new pf_engine{impl, {}, {}, {}};
    return PF_OK;
 }
 
@@ -174,6 +175,25 @@ int pf__engine_bandacc_set_x(pf_engine *e, pf_bandacc *a, const double *sums, co
    a->count = count;
    return PF_OK;
 }
+// vector band accumulators: the same rule
+static int vband_mine(pf_engine *e, const pf_vbandacc *a, const char *what) {
+   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
+   if (!a) return set_err(PF_ERR_ARG, "%s: null pf_vbandacc", what);
+   if (a->eng != e) return set_err(PF_ERR_ARG, "%s: the pf_vbandacc belongs to another engine%s", what, a->chain ? " (it is a chain's: pf_multi_vband_*)" : "");
+   return PF_OK;
+}
+int pf__engine_vband_get_x(pf_engine *e, pf_vbandacc *a, double *sums, double *state, int64_t pitch, int64_t rowstride) {
+   const int rc = vband_mine(e, a, "pf_engine_vband_get");
+   return rc ? rc : e->impl->vband_get(a->impl, sums, state, pitch, rowstride);
+}
+int pf__engine_vband_set_x(pf_engine *e, pf_vbandacc *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride, int64_t count) {
+   int rc = vband_mine(e, a, "pf_engine_vband_set");
+   if (rc) return rc;
+   if (count < 0) return set_err(PF_ERR_ARG, "pf_engine_vband_set: count = %ld < 0", (long)count);
+   if ((rc = e->impl->vband_set(a->impl, sums, state, pitch, rowstride))) return rc;
+   a->count = count;
+   return PF_OK;
+}
 int pf__engine_between_runs(pf_engine *e) { return e && e->impl && e->impl->between_runs() ? 1 : 0; }
 
 extern "C" {
@@ -182,6 +202,7 @@ void pf_engine_destroy(pf_engine *e) {
    if (!e) return;
    for (pf_accum *a : e->accums) delete a; // (their device memory is the engine's: freed with it)
    for (pf_bandacc *a : e->bands) delete a;
+   for (pf_vbandacc *a : e->vbands) delete a;
    delete e->impl;
    delete e;
 }
@@ -247,6 +268,39 @@ int pf_engine_bandacc_destroy(pf_engine *e, pf_bandacc *a) {
    int rc = band_mine(e, a, "pf_engine_bandacc_destroy");
    if (rc || (rc = e->impl->band_destroy(a->impl))) return rc;
    e->bands.erase(std::find(e->bands.begin(), e->bands.end(), a));
+   delete a;
+   return PF_OK;
+}
+
+int pf_engine_vband_create(pf_engine *e, const pf_region *r, int32_t ncomp, const int32_t *comp, int32_t npre, const double *pre_sos, int32_t nband, int32_t nsec,
+                           const double *band_sos, int32_t nprod, const int32_t *prod, int64_t nbin, int32_t depth, pf_vbandacc **out) {
+   const char *what = "pf_engine_vband_create";
+   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
+   if (!out) return set_err(PF_ERR_ARG, "%s: null out", what);
+   *out = nullptr;
+   void *impl = nullptr;
+   const int rc = e->impl->vband_create(r, ncomp, comp, npre, pre_sos, nband, nsec, band_sos, nprod, prod, nbin, depth, &impl);
+   if (rc) return rc;
+   pf_vbandacc *a = new pf_vbandacc();
+   a->eng = e; a->impl = impl; a->region = *r; a->nbin = nbin;
+   a->cells = pf_cut::region_counts(r, a->rc);
+   e->vbands.push_back(a);
+   *out = a;
+   return PF_OK;
+}
+int pf_engine_vband_add(pf_engine *e, pf_vbandacc *a, int64_t bin) {
+   int rc = vband_mine(e, a, "pf_engine_vband_add");
+   if (rc || (rc = e->impl->vband_add(a->impl, bin))) return rc;
+   a->count++;
+   return PF_OK;
+}
+int pf_engine_vband_get(pf_engine *e, pf_vbandacc *a, double *sums, double *state) { return pf__engine_vband_get_x(e, a, sums, state, 0, 0); }
+int pf_engine_vband_set(pf_engine *e, pf_vbandacc *a, const double *sums, const double *state, int64_t count) { return pf__engine_vband_set_x(e, a, sums, state, 0, 0, count); }
+int64_t pf_vbandacc_count(const pf_vbandacc *a) { return a ? a->count : -1; }
+int pf_engine_vband_destroy(pf_engine *e, pf_vbandacc *a) {
+   int rc = vband_mine(e, a, "pf_engine_vband_destroy");
+   if (rc || (rc = e->impl->vband_destroy(a->impl))) return rc;
+   e->vbands.erase(std::find(e->vbands.begin(), e->vbands.end(), a));
    delete a;
    return PF_OK;
 }

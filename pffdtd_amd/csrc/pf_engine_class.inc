@@ -31,6 +31,7 @@
 #include "pf_region_cut.h"
 #include "pf_accum.h"
 #include "pf_band.h"
+#include "pf_vband.h"
 
 // shared between the two units (defined in pf_engine.hip)
 extern "C" void pf__set_error(const char *msg);
@@ -66,6 +67,12 @@ struct EngineBase {
    virtual int band_get(void *a, double *sums, double *state, int64_t pitch, int64_t rowstride) = 0;
    virtual int band_set(void *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride) = 0;
    virtual int band_destroy(void *a) = 0;
+   virtual int vband_create(const pf_region *r, int ncomp, const int32_t *comp, int npre, const double *pre_sos, int nband, int nsec, const double *band_sos, int nprod,
+                            const int32_t *prod, int64_t nbin, int depth, void **out) = 0; // vector band accumulators (pf_engine_vband.inc)
+   virtual int vband_add(void *a, int64_t bin) = 0;
+   virtual int vband_get(void *a, double *sums, double *state, int64_t pitch, int64_t rowstride) = 0;
+   virtual int vband_set(void *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride) = 0;
+   virtual int vband_destroy(void *a) = 0;
    virtual bool between_runs() const = 0; // not inside a split-phase step or pass
    virtual int save_state(pf_state *st) = 0;
    virtual int load_state(const pf_state *st) = 0;
@@ -1088,6 +1095,7 @@ template <typename Real> struct Engine : EngineBase {
 #include "pf_engine_region.inc"
 #include "pf_engine_accum.inc"
 #include "pf_engine_band.inc"
+#include "pf_engine_vband.inc"
    void *stream(int which) override { return which == 1 ? (void *)s_edge : (void *)s_main; }
 };
 

@@ -614,6 +614,13 @@ void band_add_slab(Shared &S, int g, pf_bandacc *a, int64_t bin) {
    ECHK(g, pf_engine_bandacc_add(S.eng[g], a->part[g], bin));
 }
 
+// ... and of a vector band accumulator
+void vband_add_slab(Shared &S, int g, pf_vbandacc *a, int64_t bin) {
+   if (S.err.load() || !S.eng[g] || !a->part[g]) return;
+   MCHK(g, hipSetDevice(S.dev[g]));
+   ECHK(g, pf_engine_vband_add(S.eng[g], a->part[g], bin));
+}
+
 void finish_slab(Shared &S, int g) {
    if (!S.eng[g]) return;
    hipSetDevice(S.dev[g]);
@@ -697,12 +704,14 @@ struct pf_multi {
    std::mutex mu;
    std::condition_variable cv_cmd, cv_done;
    int64_t cmd_seq = 0, cmd_n0 = 0, cmd_ns = 0;
-   int cmd_kind = 0;                 // 1 run, 2 quit, 3 save the state, 4 load it, 5 cut a region of a field, 6 add a sample to a field accumulator, 7 to a band accumulator
+   int cmd_kind = 0;                 // 1 run, 2 quit, 3 save the state, 4 load it, 5 cut a region of a field, 6 add a sample to a field accumulator, 7 to a band accumulator, 8 to a vector band accumulator
    pf_accum *cmd_accum = nullptr;    // 6: the chain's accumulator and the sample's weights
    const double *cmd_w = nullptr;
    pf_bandacc *cmd_band = nullptr;   // 7: the chain's band accumulator and the sample's bin
    int64_t cmd_bin = 0;
    std::vector<pf_bandacc *> bands;  // the chain's band accumulators still alive
+   pf_vbandacc *cmd_vband = nullptr; // 8: the chain's vector band accumulator (its bin: cmd_bin)
+   std::vector<pf_vbandacc *> vbands; // the chain's vector band accumulators still alive
    std::vector<pf_accum *> accums;   // the chain's field accumulators still alive (pf_multi_destroy frees those left)
    pf_state *cmd_state = nullptr;    // ... from / into these global arrays
    pf_region cmd_region{};           // 5: the region (checked), its counts, the field, the caller's dense array
@@ -740,6 +749,7 @@ void worker(pf_multi *m, int g) {
       else if (kind == 5) region_slab(S, g, m->cmd_which, m->cmd_region, m->cmd_rc, m->cmd_host);
       else if (kind == 6) accum_add_slab(S, g, m->cmd_accum, m->cmd_w);
       else if (kind == 7) band_add_slab(S, g, m->cmd_band, m->cmd_bin);
+      else if (kind == 8) vband_add_slab(S, g, m->cmd_vband, m->cmd_bin);
       else run_slabs(S, g, g + 1, local, n0, ns);
       S.bar.wait(local, S.err, S.bar_timeout);
       { std::lock_guard<std::mutex> lk(m->mu); m->done++; }
@@ -1311,6 +1321,139 @@ int pf_multi_bandacc_destroy(pf_multi *m, pf_bandacc *a) {
    return rc;
 }
 
+// ---- vector band accumulators of a chain: the band accumulators' scheme, no new cut code.  A slab's part is an engine object over
+// region_part(...).local; a difference across the cut reads the slab's ghost plane, which between runs holds the neighbour's u^n (the exchange of the
+// step that wrote u^n received it into that plane: pf_engine_halo_ptrs; a load scatters the planes [xlo, xhi), ghost planes included).
+static int vband_chain(pf_multi *m, const pf_vbandacc *a, const char *what) {
+   if (!a) return fail("%s: null pf_vbandacc", what);
+   if (a->chain != m) return fail("%s: the pf_vbandacc belongs to another engine or chain", what);
+   return PF_OK;
+}
+
+int pf_multi_vband_create(pf_multi *m, const pf_region *r, int32_t ncomp, const int32_t *comp, int32_t npre, const double *pre_sos, int32_t nband, int32_t nsec,
+                          const double *band_sos, int32_t nprod, const int32_t *prod, int64_t nbin, int32_t depth, pf_vbandacc **out) {
+   const char *what = "pf_multi_vband_create";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_vband_create(S.eng[0], r, ncomp, comp, npre, pre_sos, nband, nsec, band_sos, nprod, prod, nbin, depth, out);
+   if (!r) return fail("%s: null pf_region", what);
+   if (!out) return fail("%s: null out", what);
+   *out = nullptr;
+   const int64_t N[3] = {m->sd->Nx, m->sd->Ny, m->sd->Nz};
+   char msg[256], full[400];
+   std::unique_ptr<pf_vbandacc> a(new pf_vbandacc());
+   if ((a->cells = pf_cut::region_check(r, N, a->rc, msg, sizeof msg)) < 0) { snprintf(full, sizeof full, "%s: %s", what, msg); return fail("%s", full); }
+   // the one-cell rule against the SCENE's faces (a slab checks its part against its own planes, where a cut is no face)
+   if (comp && ncomp >= 1 && ncomp <= 4)
+      for (int k = 0; k < ncomp; k++) {
+         const int ax = comp[k] - 1;
+         if (ax < 0 || ax > 2) continue;
+         const int64_t last = r->lo[ax] + (a->rc[ax] - 1) * r->stride[ax];
+         if (r->lo[ax] < 1 || last > N[ax] - 2) {
+            snprintf(full, sizeof full, "%s: a difference along file %c needs the region one cell clear of both faces along %c: pf_region.lo[%d] = %ld >= 1 and its last cell %ld <= %ld",
+                     what, "xyz"[ax], "xyz"[ax], ax, (long)r->lo[ax], (long)last, (long)N[ax] - 2);
+            return fail("%s", full);
+         }
+      }
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   a->chain = m; a->region = *r; a->nbin = nbin;
+   a->part.assign((size_t)S.G, nullptr);
+   for (int g = 0; g < S.G; g++) {
+      const pf_cut::RegionPart p = pf_cut::region_part(*r, a->rc, S.slabs[g], S.along_z);
+      if (p.empty) continue;
+      const int rc = pf_engine_vband_create(S.eng[g], &p.local, ncomp, comp, npre, pre_sos, nband, nsec, band_sos, nprod, prod, nbin, depth, &a->part[g]); // (a bad count, index or coefficient: the first slab's message names it)
+      if (rc) {
+         const std::string keep = pf_last_error();
+         for (int h = 0; h < g; h++) if (a->part[h]) pf_engine_vband_destroy(S.eng[h], a->part[h]);
+         pf__set_error(keep.c_str());
+         return rc;
+      }
+   }
+   m->vbands.push_back(a.get());
+   *out = a.release();
+   return PF_OK;
+}
+
+int pf_multi_vband_add(pf_multi *m, pf_vbandacc *a, int64_t bin) {
+   const char *what = "pf_multi_vband_add";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_vband_add(S.eng[0], a, bin);
+   if (vband_chain(m, a, what)) return PF_ERR_ARG;
+   if (bin < -1 || bin >= a->nbin) {
+      char b[160];
+      snprintf(b, sizeof b, "%s: bin = %ld outside -1 .. %ld", what, (long)bin, (long)a->nbin - 1);
+      return fail("%s", b);
+   }
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   // all or nothing: the slab threads are idle, so every engine can be asked here, before any of them takes the sample
+   for (int g = 0; g < S.G; g++)
+      if (!pf__engine_between_runs(S.eng[g])) {
+         char b[256];
+         snprintf(b, sizeof b, "%s: slab %d is inside a pair or triple (u^{n+1} is not complete in memory): no slab took the sample; advance a step, or create the chain with "
+                               "PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES", what, g);
+         pf__set_error(b);
+         return PF_ERR_STATE;
+      }
+   if (m->one_thread) { for (int g = 0; g < S.G; g++) vband_add_slab(S, g, a, bin); }
+   else {
+      { std::lock_guard<std::mutex> lk(m->mu); m->cmd_vband = a; m->cmd_bin = bin; }
+      post(m, 8, 0, 0);
+      wait_done(m);
+      if (m->broken && !S.err.load()) S.set_error(PF_ERR_HIP, "slab chain hung: a slab's host thread never came back");
+   }
+   const int rc = accum_status(S);
+   if (rc == PF_OK) a->count++;
+   return rc;
+}
+
+int pf_multi_vband_get(pf_multi *m, pf_vbandacc *a, double *sums, double *state) {
+   const char *what = "pf_multi_vband_get";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_vband_get(S.eng[0], a, sums, state);
+   if (vband_chain(m, a, what)) return PF_ERR_ARG;
+   if (!sums) return fail("%s: null sums array", what);
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   for (int g = 0; g < S.G; g++) {
+      if (!a->part[g]) continue;
+      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
+      const int rc = pf__engine_vband_get_x(S.eng[g], a->part[g], sums + p.out_off, state ? state + p.out_off : nullptr, p.out_pitch, a->cells);
+      if (rc) return rc;
+   }
+   return PF_OK;
+}
+
+int pf_multi_vband_set(pf_multi *m, pf_vbandacc *a, const double *sums, const double *state, int64_t count) {
+   const char *what = "pf_multi_vband_set";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_vband_set(S.eng[0], a, sums, state, count);
+   if (vband_chain(m, a, what)) return PF_ERR_ARG;
+   if (count < 0) return fail("%s: count < 0", what);
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   for (int g = 0; g < S.G; g++)
+      if (!pf__engine_between_runs(S.eng[g])) { fail("%s: a slab is inside a pair or triple: valid between passes only", what); return PF_ERR_STATE; }
+   for (int g = 0; g < S.G; g++) {
+      if (!a->part[g]) continue;
+      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
+      const int rc = pf__engine_vband_set_x(S.eng[g], a->part[g], sums ? sums + p.out_off : nullptr, state ? state + p.out_off : nullptr, p.out_pitch, a->cells, count);
+      if (rc) return rc;
+   }
+   a->count = count;
+   return PF_OK;
+}
+
+int pf_multi_vband_destroy(pf_multi *m, pf_vbandacc *a) {
+   const char *what = "pf_multi_vband_destroy";
+   if (!m) return fail("%s: null object", what);
+   Shared &S = m->S;
+   if (S.G == 1) return pf_engine_vband_destroy(S.eng[0], a);
+   if (vband_chain(m, a, what)) return PF_ERR_ARG;
+   int rc = PF_OK;
+   for (int g = 0; g < S.G; g++)
+      if (a->part[g] && S.eng[g]) { const int r1 = pf_engine_vband_destroy(S.eng[g], a->part[g]); if (r1 && !rc) rc = r1; }
+   m->vbands.erase(std::find(m->vbands.begin(), m->vbands.end(), a));
+   delete a;
+   return rc;
+}
+
 int pf_multi_get_info(pf_multi *m, pf_multi_info *info) {
    if (!m || !info) return fail("pf_multi_get_info: null argument");
    const Shared &S = m->S;
@@ -1357,6 +1500,7 @@ void pf_multi_destroy(pf_multi *m) {
    else for (int g = 0; g < S.G; g++) destroy_slab(S, g);
    for (pf_accum *a : m->accums) delete a; // (the slabs' parts went with their engines)
    for (pf_bandacc *a : m->bands) delete a;
+   for (pf_vbandacc *a : m->vbands) delete a;
    for (auto &c : S.comm) if (c) { g_rccl.CommDestroy(c); c = nullptr; }
    delete m;
 }

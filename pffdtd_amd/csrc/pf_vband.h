@@ -1,0 +1,167 @@
+// pf_vband.h -- device side of the vector band accumulators (include/pffdtd_hip.h: pf_vbandacc): per cell of a region, up to four COMPONENTS of
+// the field -- the cell itself (0) or the central difference along file x / y / z (1 / 2 / 3), d_a = u^n[c + e_a] - u^n[c - e_a] in the field's own
+// precision -- run through a cascade of second-order sections each, and PRODUCTS of two filtered components are summed into time bins,
+//    x_k = double(component k);  x_k -> pre sections of k;  per band b: y_k = x_k -> the band's sections (state per component);
+//    S[p][b][bin] = S[p][b][bin] + y_i * y_j          (mode 1: + fabs(y_i * y_j))         for every product p = (i, j, mode)
+// which is what a lateral energy fraction or an intensity map needs of every cell (pffdtd_amd/directional.py).  The section is pf_band.h's
+// band_section, unchanged: the same three lines, every operation rounded to double once, NO fma (the build has -ffp-contract=off, the pragmas
+// below say so again).
+//   S     double [nprod * nband * nbin][cstride]            cstride = the cell count rounded up to a multiple of 2
+//   st    double [ncomp][(npre + nband*nsec) * 2][cstride]   component k's s1, s2 of section q in rows 2q, 2q + 1 of its block
+//   coef  double [(ncomp*npre + nband*nsec) * 5]            the components' pre sections, then the bands' (shared by the components)
+//   ring  Real   [ncomp][depth][cells]                      the components at the samples not folded in yet: component 0 by k_region_cut
+//                                                           (pf_region.h), a difference by k_region_diff below -- a fold reads Real whatever
+//                                                           the component
+//   xpre  double [ncomp][depth][cstride]                    npre > 0 only: the pending samples after the components' pre sections
+//   bins  int32  [depth];  prod  int32 [nprod][3]
+// k_region_diff<Real, EXCH> is k_region_cut with the two neighbour loads and ONE subtraction, rounded once in Real.  The subtraction is done in
+// registers before anything goes to LDS, so the tiled form keeps ONE 32 x 33 tile of Real and the bank picture of pf_region.h as it is (two
+// operand tiles would double the LDS for nothing: the operands are never needed apart).  On exchanged storage a difference along file x has its
+// operands one element apart (same lines), along file z one storage plane apart.
+// A fold of NT pending samples is k_vband_pre<Real, NT> (npre > 0; grid.y = the component) and ONE k_vband_fold<In, NC, NT> on a grid of
+// (cdiv(cdiv(cells, 2), 256), nband): a thread owns two adjacent cells (16-byte loads and stores, lanes along cells), runs all NC components'
+// sections of its band over the NT samples in registers -- y[NC][NT] of two cells, 2 * NC * NT doubles, never go to memory -- and then walks the
+// products and, per product, the bins exactly as k_band_fold walks its one square: consecutive samples of one bin are summed in a register from
+// the loaded S in call order, a bin change stores and loads.  The components of a product are picked with selects on (i == k), uniform over the
+// wave: no indexed register file, hence no scratch.  prod, coef and bins do not depend on the lane: scalar loads.  No atomics, no LDS in the
+// folds, no scratch (tools/kernel_resources.py k_vband).  64-bit indices, every access guarded by the cell count.
+// Instantiated for NC = 1 .. 4 and NT in {1, 2, 4, 8}: a partly filled ring is folded greedily (7 = 4 + 2 + 1), the samples still in call order,
+// so the pieces never change a bit.
+//
+// PF_VBAND_DEFAULT_DEPTH: the fastest of the depths 1, 2, 4, 8 on the plane case of tools/field_directional_cost.py (profiles/field_directional.txt).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "pf_band.h"
+#include "pf_region.h"
+
+namespace pf {
+
+constexpr int PF_VBAND_MAX_COMP = 4;
+constexpr int PF_VBAND_MAX_PROD = 10;
+constexpr int PF_VBAND_MAX_DEPTH = 8;
+constexpr int PF_VBAND_DEFAULT_DEPTH = 8;
+
+// grid and arguments as k_region_cut; dx, dy, dz: the difference's unit vector in FILE coordinates (one of them 1).  The caller keeps the region one
+// cell clear of both faces along that axis, so both neighbours are cells of the grid.
+template <typename Real, bool EXCH>
+static __global__ void __launch_bounds__(256) k_region_diff(const Real *__restrict__ st, Real *__restrict__ stage, RegionPiece q, int64_t Ny, int64_t P, int tiled, int bz_log2,
+                                                            int dx, int dy, int dz) {
+#pragma clang fp contract(off)
+   // storage offset of one cell along the difference axis
+   const int64_t step = EXCH ? ((int64_t)dz * Ny + dy) * P + dx : ((int64_t)dx * Ny + dy) * P + dz;
+   if (EXCH && tiled) {
+      __shared__ Real tile[32][33];
+      const int a = threadIdx.x & 31, b = threadIdx.x >> 5; // 32 x 8
+      const int64_t j = blockIdx.y, kt = (int64_t)blockIdx.x * 32, it = (int64_t)blockIdx.z * 32;
+      const int64_t fy = q.lo1 + j * q.s1;
+#pragma unroll
+      for (int r = 0; r < 4; r++) { // lanes along file x: the storage's unit-stride axis
+         const int64_t i = it + a, k = kt + b + 8 * r;
+         if (i < q.n0 && k < q.n2) {
+            const int64_t at = ((q.lo2 + k * q.s2) * Ny + fy) * P + q.lo0 + i * q.s0;
+            tile[b + 8 * r][a] = st[at + step] - st[at - step];
+         }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int r = 0; r < 4; r++) { // lanes along file z: the slot's
+         const int64_t i = it + b + 8 * r, k = kt + a;
+         if (i < q.n0 && k < q.n2) stage[(i * q.n1 + j) * q.n2 + k] = tile[a][b + 8 * r];
+      }
+      return;
+   }
+   const int bz = 1 << bz_log2;
+   const int64_t k = (int64_t)blockIdx.x * bz + (threadIdx.x & (bz - 1));
+   const int64_t j = (int64_t)blockIdx.y * (256 >> bz_log2) + (threadIdx.x >> bz_log2);
+   const int64_t i = blockIdx.z;
+   if (k >= q.n2 || j >= q.n1) return;
+   const int64_t fx = q.lo0 + i * q.s0, fy = q.lo1 + j * q.s1, fz = q.lo2 + k * q.s2;
+   const int64_t at = EXCH ? (fz * Ny + fy) * P + fx : (fx * Ny + fy) * P + fz;
+   stage[(i * q.n1 + j) * q.n2 + k] = st[at + step] - st[at - step];
+}
+
+// grid: (cdiv(cdiv(cells, 2), 256), ncomp) blocks of 256 threads; npre >= 1.  ring, xpre: at the first of the NT samples; rcomp, xcomp, scomp: elements
+// between two components' blocks of the ring, of xpre, of the state
+template <typename Real, int NT>
+static __global__ void __launch_bounds__(256) k_vband_pre(double *__restrict__ st, double *__restrict__ xpre, const Real *__restrict__ ring, const double *__restrict__ coef,
+                                                          int64_t cells, int64_t cstride, int64_t rcomp, int64_t xcomp, int64_t scomp, int npre) {
+#pragma clang fp contract(off)
+   const int64_t c = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
+   if (c >= cells) return;
+   const bool two = c + 1 < cells;
+   const int k = blockIdx.y;
+   const Real *x = ring + (int64_t)k * rcomp;
+   double xa[NT], xb[NT];
+#pragma unroll
+   for (int t = 0; t < NT; t++) {
+      xa[t] = (double)x[(int64_t)t * cells + c];
+      xb[t] = two ? (double)x[(int64_t)t * cells + c + 1] : 0.0;
+   }
+   double *sk = st + (int64_t)k * scomp;
+   const double *ck = coef + (int64_t)k * npre * 5;
+   for (int q = 0; q < npre; q++) band_section<NT>(sk, ck + 5 * q, q, c, cstride, xa, xb);
+   double *o = xpre + (int64_t)k * xcomp;
+#pragma unroll
+   for (int t = 0; t < NT; t++) *reinterpret_cast<double2 *>(o + (int64_t)t * cstride + c) = make_double2(xa[t], xb[t]);
+}
+
+// grid: (cdiv(cdiv(cells, 2), 256), nband) blocks of 256 threads.  x: the ring (xstride = cells) or xpre (xstride = cstride) at the first of the NT samples,
+// xcomp elements between two components; bcoef: the bands' coefficients
+template <typename In, int NC, int NT>
+static __global__ void __launch_bounds__(256) k_vband_fold(double *__restrict__ S, double *__restrict__ st, const In *__restrict__ x, const double *__restrict__ bcoef,
+                                                           const int32_t *__restrict__ bins, const int32_t *__restrict__ prod, int64_t cells, int64_t cstride, int64_t xstride,
+                                                           int64_t xcomp, int64_t scomp, int npre, int nsec, int nband, int nbin, int nprod) {
+#pragma clang fp contract(off)
+   const int64_t c = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
+   if (c >= cells) return;
+   const bool two = c + 1 < cells;
+   const int b = blockIdx.y;
+   double ya[NC][NT], yb[NC][NT];
+#pragma unroll
+   for (int k = 0; k < NC; k++) {
+      const In *xk = x + (int64_t)k * xcomp;
+#pragma unroll
+      for (int t = 0; t < NT; t++) {
+         ya[k][t] = (double)xk[(int64_t)t * xstride + c];
+         yb[k][t] = two ? (double)xk[(int64_t)t * xstride + c + 1] : 0.0;
+      }
+   }
+   const int64_t q0 = npre + (int64_t)b * nsec;
+#pragma unroll
+   for (int k = 0; k < NC; k++)
+      for (int s = 0; s < nsec; s++) band_section<NT>(st + (int64_t)k * scomp, bcoef + 5 * ((int64_t)b * nsec + s), q0 + s, c, cstride, ya[k], yb[k]);
+   for (int p = 0; p < nprod; p++) {
+      const int pi = prod[3 * p], pj = prod[3 * p + 1], mode = prod[3 * p + 2];
+      int cur = -1;
+      double2 e = make_double2(0.0, 0.0);
+      double2 *row = nullptr;
+#pragma unroll
+      for (int t = 0; t < NT; t++) {
+         const int bin = bins[t];
+         if (bin < 0 || bin >= nbin) continue; // (-1: the filters ran, nothing is summed)
+         if (bin != cur) {
+            if (cur >= 0) *row = e;
+            row = reinterpret_cast<double2 *>(S + (((int64_t)p * nband + b) * nbin + bin) * cstride + c);
+            e = *row;
+            cur = bin;
+         }
+         double ia = ya[0][t], ib = yb[0][t], ja = ya[0][t], jb = yb[0][t];
+#pragma unroll
+         for (int k = 1; k < NC; k++) { // (pi, pj are uniform: selects, never an indexed register file)
+            ia = pi == k ? ya[k][t] : ia;
+            ib = pi == k ? yb[k][t] : ib;
+            ja = pj == k ? ya[k][t] : ja;
+            jb = pj == k ? yb[k][t] : jb;
+         }
+         double va = ia * ja, vb = ib * jb;
+         if (mode) { va = fabs(va); vb = fabs(vb); }
+         e.x = e.x + va;
+         e.y = e.y + vb;
+      }
+      if (cur >= 0) *row = e;
+   }
+}
+
+} // namespace pf

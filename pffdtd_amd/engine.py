@@ -100,6 +100,8 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_grid_bytes", "p
            "pf_multi_accum_create", "pf_multi_accum_add", "pf_multi_accum_get", "pf_multi_accum_set", "pf_multi_accum_destroy",
            "pf_engine_bandacc_create", "pf_engine_bandacc_add", "pf_engine_bandacc_get", "pf_engine_bandacc_set", "pf_engine_bandacc_destroy", "pf_bandacc_count",
            "pf_multi_bandacc_create", "pf_multi_bandacc_add", "pf_multi_bandacc_get", "pf_multi_bandacc_set", "pf_multi_bandacc_destroy",
+           "pf_engine_vband_create", "pf_engine_vband_add", "pf_engine_vband_get", "pf_engine_vband_set", "pf_engine_vband_destroy", "pf_vbandacc_count",
+           "pf_multi_vband_create", "pf_multi_vband_add", "pf_multi_vband_get", "pf_multi_vband_set", "pf_multi_vband_destroy",
            "pf_engine_energy_cfg", "pf_engine_run_energy", "pf_run_sim_devices", "pf_slab_partition", "pf_slab_partition_w", "pf_slab_partition_axis", "pf_slab_wall_scale",
            "pf_multi_create", "pf_multi_run", "pf_multi_get_info", "pf_multi_get_slab", "pf_multi_destroy",
            "pf_rccl_unique_id", "pf_rccl_comm_create", "pf_rccl_exchange", "pf_rccl_comm_destroy"]
@@ -198,10 +200,17 @@ def lib():
             getattr(L, pre + "_bandacc_get").argtypes = [vp, vp, vp, vp]
             getattr(L, pre + "_bandacc_set").argtypes = [vp, vp, vp, vp, i64]
             getattr(L, pre + "_bandacc_destroy").argtypes = [vp, vp]
+            getattr(L, pre + "_vband_create").argtypes = [vp, ctypes.POINTER(PfRegion), i32, vp, i32, vp, i32, i32, vp, i32, vp, i64, i32, ctypes.POINTER(vp)]
+            getattr(L, pre + "_vband_add").argtypes = [vp, vp, i64]
+            getattr(L, pre + "_vband_get").argtypes = [vp, vp, vp, vp]
+            getattr(L, pre + "_vband_set").argtypes = [vp, vp, vp, vp, i64]
+            getattr(L, pre + "_vband_destroy").argtypes = [vp, vp]
         L.pf_accum_count.restype = i64
         L.pf_accum_count.argtypes = [vp]
         L.pf_bandacc_count.restype = i64
         L.pf_bandacc_count.argtypes = [vp]
+        L.pf_vbandacc_count.restype = i64
+        L.pf_vbandacc_count.argtypes = [vp]
         dp = ctypes.POINTER(ctypes.c_double)
         L.pf_engine_energy_cfg.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, dp]
         L.pf_engine_run_energy.argtypes = [vp, i64, i64, dp, dp, dp]
@@ -398,6 +407,96 @@ class BandAccumulator:
             pass
 
 
+class VectorBandAccumulator:
+    """Per cell of a region, on the device (pf_engine_vband_* / pf_multi_vband_*): the components `comp` (0: the cell of u^n, 1 / 2 / 3: its central
+    difference along file x / y / z) through their own sections pre_sos [ncomp, npre, 6], then per band through band_sos [nband, nsec, 6] (scipy's
+    sos rows, a0 = 1; state per component); the products prod [nprod, 3] -- rows (i, j, mode), mode 1: the absolute value -- of two filtered
+    components are summed into time bin `bin` at every add(bin).
+    Made by HipEngine.vector_band_accumulator / HipMulti.vector_band_accumulator; it lives no longer than the object that made it."""
+
+    def __init__(self, owner, prefix, lo, hi, stride, comp, pre_sos, band_sos, prod, nbin, depth):
+        try:
+            r = PfRegion((ctypes.c_int64 * 3)(*[int(v) for v in lo]), (ctypes.c_int64 * 3)(*[int(v) for v in hi]), (ctypes.c_int64 * 3)(*[int(v) for v in stride]))
+        except TypeError as e:
+            raise PfError(f"vector_band_accumulator: lo, hi and stride are three integers each ({e})")
+        comp = np.ascontiguousarray(np.asarray(comp).reshape(-1), dtype=np.int32)
+        prod = np.asarray([] if prod is None else prod)
+        if prod.size and (prod.ndim != 2 or prod.shape[1] != 3):
+            raise PfError(f"vector_band_accumulator: prod has shape {prod.shape}: [nprod, 3] rows (i, j, mode) are expected")
+        prod = np.ascontiguousarray(prod.reshape(-1, 3), dtype=np.int32)
+        p = np.asarray([] if pre_sos is None else pre_sos, dtype=np.float64)
+        if p.size == 0:
+            pre = np.zeros((comp.size, 0, 5))
+        else:
+            if p.ndim != 3 or p.shape[0] != comp.size:
+                raise PfError(f"vector_band_accumulator: pre_sos has shape {p.shape}: [ncomp = {comp.size}, npre, 6] is expected (pad a shorter cascade with 1 0 0 1 0 0)")
+            pre = _sos5("pre_sos", p, 2)
+        b = np.asarray([] if band_sos is None else band_sos, dtype=np.float64)
+        if b.ndim == 3 and b.shape[1] == 0:  # nband bands without sections
+            band, nband = np.zeros((b.shape[0], 0, 5)), b.shape[0]
+        else:
+            band = _sos5("band_sos", band_sos, 2)
+            nband = band.shape[0] if band.ndim == 3 else 0
+        L = lib()
+        self._owner, self._f = owner, {k: getattr(L, f"{prefix}_vband_{k}") for k in ("create", "add", "get", "set", "destroy")}
+        self._a = ctypes.c_void_p()
+        self.ncomp, self.nprod, self.npre, self.nband, self.nbin = int(comp.size), int(prod.shape[0]), int(pre.shape[1]), int(nband), int(nbin)
+        self.nsec = int(band.shape[1]) if band.ndim == 3 else 0
+        vp = ctypes.c_void_p
+        _check(self._f["create"](owner._h, ctypes.byref(r), self.ncomp, comp.ctypes.data_as(vp) if comp.size else None, self.npre, pre.ctypes.data_as(vp) if pre.size else None,
+                                 self.nband, self.nsec, band.ctypes.data_as(vp) if band.size else None, self.nprod, prod.ctypes.data_as(vp) if prod.size else None,
+                                 self.nbin, int(depth), ctypes.byref(self._a)))
+        counts = (ctypes.c_int64 * 3)()
+        L.pf_region_count(ctypes.byref(r), counts)
+        cells = tuple(int(c) for c in counts)
+        self.shape = (self.nprod, self.nband, self.nbin) + cells  # of get()'s sums
+        self.state_shape = (self.ncomp, self.npre + self.nband * self.nsec, 2) + cells  # ... and state
+
+    def add(self, bin):
+        """the sample of the step the owner stands at, its products summed into time bin `bin` (-1: the filters run, nothing is summed)"""
+        _check(self._f["add"](self._owner._h, self._a, int(bin)))
+
+    def get(self, state=True):
+        """-> (sums float64 [nprod, nband, nbin, c0, c1, c2], state float64 [ncomp, npre + nband * nsec, 2, c0, c1, c2] or None): pending samples folded in"""
+        e = np.empty(self.shape, dtype=np.float64)
+        s = np.empty(self.state_shape, dtype=np.float64) if state else None
+        _check(self._f["get"](self._owner._h, self._a, e.ctypes.data_as(ctypes.c_void_p), s.ctypes.data_as(ctypes.c_void_p) if state and s.size else None))
+        return e, s
+
+    def set(self, sums, state, count):
+        """replace sums, filter state and count (None: zeros); pending samples are dropped -- how a resumed run continues"""
+        arrs = []
+        for name, a, shape in (("sums", sums, self.shape), ("state", state, self.state_shape)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.size != int(np.prod(shape)):
+                    raise PfError(f"VectorBandAccumulator.set: {name} has {a.size} elements, the accumulator holds {int(np.prod(shape))}")
+            arrs.append(a)
+        _check(self._f["set"](self._owner._h, self._a, *[None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p) for a in arrs], int(count)))
+
+    @property
+    def count(self):
+        """samples added so far, or the count given to set"""
+        if not (self._a.value and self._alive()):
+            raise PfError("VectorBandAccumulator.count: the accumulator or its owner is closed")
+        return int(lib().pf_vbandacc_count(self._a))
+
+    def _alive(self):
+        return bool(getattr(self._owner, "_h", None) and self._owner._h.value)
+
+    def close(self):
+        if getattr(self, "_a", None) and self._a.value:
+            if self._alive():
+                _check(self._f["destroy"](self._owner._h, self._a))
+            self._a = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def device_count():
     return int(lib().pf_device_count())
 
@@ -496,6 +595,11 @@ class HipMulti:
         """Band-filtered squares of a region of the whole scene in time bins (pf_multi_bandacc_create): every slab keeps the part it owns.  add raises
         PfError with code 4, and changes nothing, while any slab is inside a blocked pass."""
         return BandAccumulator(self, "pf_multi", lo, hi, stride, pre_sos, band_sos, nbin, depth)
+
+    def vector_band_accumulator(self, lo, hi, stride=(1, 1, 1), comp=(0,), pre_sos=None, band_sos=None, prod=((0, 0, 0),), nbin=1, depth=0):
+        """Band-filtered products of components of the whole scene's field in time bins (pf_multi_vband_create): every slab keeps the part it owns; a
+        difference across a cut reads the slab's ghost plane.  add raises PfError (code PF_ERR_STATE) inside a pair or triple, as accumulator."""
+        return VectorBandAccumulator(self, "pf_multi", lo, hi, stride, comp, pre_sos, band_sos, prod, nbin, depth)
 
     def slab(self, g):
         """-> dict(x0, x1, device, paired, steps_per_pass, engine): engine = a non-owning HipEngine view of slab g's engine (state_grids, timing)"""
@@ -654,6 +758,12 @@ class HipEngine:
         """Per cell of the region, on the device (pf_engine_bandacc_create): u^n through the second-order sections pre_sos [npre, 6] and, per band,
         band_sos [nband, nsec, 6] (scipy's rows, a0 = 1), squared, summed into the time bin given to add(bin) -- a BandAccumulator."""
         return BandAccumulator(self, "pf_engine", lo, hi, stride, pre_sos, band_sos, nbin, depth)
+
+    def vector_band_accumulator(self, lo, hi, stride=(1, 1, 1), comp=(0,), pre_sos=None, band_sos=None, prod=((0, 0, 0),), nbin=1, depth=0):
+        """Per cell of the region, on the device (pf_engine_vband_create): the components comp (0: the cell of u^n, 1 / 2 / 3: its central difference
+        along file x / y / z) through pre_sos [ncomp, npre, 6] and, per band, band_sos [nband, nsec, 6]; the products prod [nprod, 3] = (i, j, mode) of
+        two filtered components summed into the time bin given to add(bin) -- a VectorBandAccumulator."""
+        return VectorBandAccumulator(self, "pf_engine", lo, hi, stride, comp, pre_sos, band_sos, prod, nbin, depth)
 
     def set_grid(self, which, a):
         a = np.ascontiguousarray(a, dtype=self.dtype)

@@ -47,6 +47,14 @@ filtered into the octave bands `--decay-bands 125,250,500` (centre frequencies i
 beside sim_outs.h5) at every checkpoint and at the end.  The run is cut at every step from N on; a chain is created with
 PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (one line says so).  `--resume` restores sums and filter state from the file.  Same processes as the
 checkpoint arguments; without these arguments nothing about a run changes.  (`--energy` is not a name of these: it stays the diagnostic's.)
+
+Directional band maps (pffdtd_amd/directional.py): `--dir-planes` / `--dir-box` (the syntax of the field arguments; one cell clear of the faces along
+every chosen axis) name regions whose cells' pressure and pressure gradient along `--dir-axes y[,x,z]` (file axes; default y) are filtered into the
+octave bands `--dir-bands 125,250,500`, multiplied and summed ON THE DEVICE into time bins of `--dir-bin-ms 5` milliseconds, at EVERY step from
+`--dir-first N` (default 0) on, and written to `--dir-file FILE` (default sim_directional.h5 beside sim_outs.h5) at every checkpoint and at the end:
+what the lateral energy fractions LF, LFC and the intensity maps are functions of (directional.parameters).  Cartesian grids only.  Everything else
+as the decay arguments: the run is cut at every step from N on, a chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (one line says
+so), `--resume` restores sums and filter state from the file, and without these arguments nothing about a run changes.
 """
 import argparse
 import os
@@ -55,6 +63,7 @@ from pathlib import Path
 
 from . import checkpoint, engine, fields, sim_data, spectra
 from . import decay as decay_mod
+from . import directional as dir_mod
 
 
 def _summary(sd, tm, el):
@@ -108,7 +117,7 @@ def _run_chain(a, sd, m):
     """all Nt steps of a chain object, in one go or in chunks with progress reports; returns (seconds, timing of the busiest slab).
     With --resume / --checkpoint / --stop-after: from the resumed step, to the step the run stops after (a.stopped_at: less than Nt then)."""
     live = range(m.nslabs)
-    if a.resume or a.checkpoint or a.field_every or a.spectrum or a.decay:
+    if a.resume or a.checkpoint or a.field_every or a.spectrum or a.decay or a.directional:
         return _run_chain_checkpointed(a, sd, m)
     t0 = time.perf_counter()
     if not a.progress:
@@ -178,11 +187,31 @@ def _field_decay(a, sd, m, resume_at):
     return fd
 
 
+def _field_directional(a, sd, m, resume_at):
+    """the FieldDirectional of --dir-planes / --dir-box on chain m (None without them); a resumed run's sums and filter state are restored"""
+    if not a.directional:
+        return None
+    N = (sd.Nx, sd.Ny, sd.Nz)
+    try:
+        regions = [r for spec in a.dir_planes for r in fields.parse_planes(spec, N)] + [fields.parse_box(spec, N) for spec in a.dir_box]
+        path = a.dir_file if a.dir_file else Path(a.data_dir) / "sim_directional.h5"
+        fv = dir_mod.FieldDirectional(path, sd, regions, decay_mod.parse_bands(a.dir_bands), dir_mod.parse_axes(a.dir_axes), a.dir_bin_ms, a.dir_first, resume_at=resume_at)
+    except ValueError as e:
+        raise SystemExit(str(e).replace("--field-", "--dir-").replace("--decay-", "--dir-"))
+    try:
+        fv.attach(m)
+    except engine.PfError as e:  # (a region on a face along a chosen axis, an FCC grid: the engine names it)
+        raise SystemExit(f"--dir-planes / --dir-box: {e}")
+    return fv
+
+
 def _chain_flags(a, nslabs):
     """multi_flags of the chain: sampled for a spectrum or a decay map, its slabs take single steps (a sample is never shifted, and no slab answers
     inside a pass)"""
-    if not (a.spectrum or a.decay) or nslabs < 2:
+    if not (a.spectrum or a.decay or a.directional) or nslabs < 2:
         return 0
+    if a.directional:
+        print("--field directional: the chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (its slabs take single steps: every step is sampled)")
     if a.decay:
         print("--field decay: the chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (its slabs take single steps: every step is sampled)")
     if not a.spectrum:
@@ -206,6 +235,7 @@ def _run_chain_checkpointed(a, sd, m):
     fw = _field_writer(a, sd, n if a.resume else None)
     fs = _field_spectrum(a, sd, m, n if a.resume else None)
     fd = _field_decay(a, sd, m, n if a.resume else None)
+    fv = _field_directional(a, sd, m, n if a.resume else None)
     end = sd.Nt if a.stop_after is None else min(max(a.stop_after, n), sd.Nt)
     every = a.checkpoint_every if a.checkpoint else 0
     t0 = time.perf_counter()
@@ -217,6 +247,8 @@ def _run_chain_checkpointed(a, sd, m):
         fs.take(m, n)
     if fd and fd.due(n) and n < end:
         fd.take(m, n)
+    if fv and fv.due(n) and n < end:
+        fv.take(m, n)
     while n < end:
         k = end - n
         if a.progress:
@@ -229,6 +261,8 @@ def _run_chain_checkpointed(a, sd, m):
             k = fs.next_step(n + 1) - n
         if fd and fd.next_step(n + 1) < n + k:
             k = fd.next_step(n + 1) - n
+        if fv and fv.next_step(n + 1) < n + k:
+            k = fv.next_step(n + 1) - n
         tc = time.perf_counter()
         m.run(n, k)
         n += k
@@ -244,10 +278,14 @@ def _run_chain_checkpointed(a, sd, m):
                 fs.write()  # (the sums of the sample steps below n: what --resume of this checkpoint continues)
             if fd:
                 fd.write()
+            if fv:
+                fv.write()
         if fs and fs.due(n) and n < end:
             fs.take(m, n)
         if fd and fd.due(n) and n < end:
             fd.take(m, n)
+        if fv and fv.due(n) and n < end:
+            fv.take(m, n)
         now = time.perf_counter()
         tms = [m.slab(g)["engine"].timing(reset=True) for g in live]
         air = max(t["air_ms_total"] for t in tms) * 1e-3
@@ -267,6 +305,10 @@ def _run_chain_checkpointed(a, sd, m):
         fd.write()
         print(f"--field decay of {fd.count} samples in {fd.bands.size} bands, bins of {fd.bin_steps} steps: {fd.path}", flush=True)
         fd.close()
+    if fv:
+        fv.write()
+        print(f"--field directional maps of {fv.count} samples in {fv.bands.size} bands along {','.join('xyz'[k - 1] for k in fv.axes)}, bins of {fv.bin_steps} steps: {fv.path}", flush=True)
+        fv.close()
     return time.perf_counter() - t0, {"air_ms_total": air_all * 1e3, "step_ms_total": step_all * 1e3}
 
 
@@ -409,7 +451,21 @@ def main():
     p.add_argument("--decay-bin-ms", type=float, default=5.0, metavar="MS", help="... in time bins of MS milliseconds (default 5)")
     p.add_argument("--decay-first", type=int, default=0, metavar="N", help="... at every step from N on (default 0)")
     p.add_argument("--decay-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_decay.h5 in the data folder)")
+    p.add_argument("--dir-planes", action="append", default=[], metavar="x=I,y=J,z=K", help="sum band-filtered products of the pressure and its gradient on these planes into time bins on the device (the syntax of --field-planes)")
+    p.add_argument("--dir-box", action="append", default=[], metavar="x0:x1:sx,y0:y1:sy,z0:z1:sz", help="... of this strided box")
+    p.add_argument("--dir-bands", default="", metavar="F1,F2,...", help="... in the octave bands around these centre frequencies in Hz")
+    p.add_argument("--dir-axes", default="", metavar="y[,x,z]", help="... with the gradient along these file axes (default y)")
+    p.add_argument("--dir-bin-ms", type=float, default=5.0, metavar="MS", help="... in time bins of MS milliseconds (default 5)")
+    p.add_argument("--dir-first", type=int, default=0, metavar="N", help="... at every step from N on (default 0)")
+    p.add_argument("--dir-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_directional.h5 in the data folder)")
     a = p.parse_args()
+    a.directional = bool(a.dir_planes or a.dir_box)
+    if a.directional != bool(a.dir_bands) or a.dir_bin_ms <= 0 or a.dir_first < 0:
+        p.error("--dir-planes / --dir-box need --dir-bands (and the other way round); --dir-bin-ms: positive, --dir-first: not negative")
+    if (a.dir_first or a.dir_file or a.dir_axes or a.dir_bin_ms != 5.0) and not a.directional:
+        p.error("--dir-axes / --dir-bin-ms / --dir-first / --dir-file need --dir-planes or --dir-box")
+    if a.directional and not a.dir_axes:
+        a.dir_axes = "y"
     a.decay = bool(a.decay_planes or a.decay_box)
     if a.decay != bool(a.decay_bands) or a.decay_bin_ms <= 0 or a.decay_first < 0:
         p.error("--decay-planes / --decay-box need --decay-bands (and the other way round); --decay-bin-ms: positive, --decay-first: not negative")
@@ -437,6 +493,8 @@ def main():
         raise SystemExit("--spectrum-planes / --spectrum-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
     if world > 1 and a.decay and not a.devices:
         raise SystemExit("--decay-planes / --decay-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
+    if world > 1 and a.directional and not a.devices:
+        raise SystemExit("--dir-planes / --dir-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
     if a.devices:
         return run_devices(a, [int(v) for v in a.devices.split(",")])
     if world > 1:
