@@ -492,6 +492,49 @@ int     pf_multi_vband_add     (pf_multi *m, pf_vbandacc *a, int64_t bin);
 int     pf_multi_vband_get     (pf_multi *m, pf_vbandacc *a, double *sums, double *state);
 int     pf_multi_vband_set     (pf_multi *m, pf_vbandacc *a, const double *sums, const double *state, int64_t count);
 int     pf_multi_vband_destroy (pf_multi *m, pf_vbandacc *a);
+/* ---- decimating recorders: per cell, EVERY sample low-pass filtered by a linear-phase FIR and every D-th output kept -- on the device ----
+ * The impulse response of every cell of an audience plane (pffdtd_amd/recordings.py), D times smaller than a receiver per cell and not aliased as
+ * raw frames every D steps are.  A decimating recorder belongs to one engine (or chain) and holds a region, npre (0 .. 8) second-order sections,
+ * ntap (1 .. 4096) FIR taps h, a factor D (1 .. 64), a frame capacity cap (>= 1) and a ring of `depth` samples (1 .. 16, 0 = the default).
+ * P = ceil(ntap / D) outputs are in flight at a time; P > 128 is refused.  No counterpart in the reference.
+ *   - pf_engine_decim_add takes u^n of the region exactly as pf_engine_bandacc_add does (the same cut, the same ghost-shell rule); x = (double)u runs
+ *     through the npre sections pre_sos[npre][5] by pf_bandacc's three lines, unchanged (state [npre][2][cells]).
+ *   - The FIR is evaluated in ARRIVAL order, so the depth never changes a bit and a numpy loop gives the same bits.  For the sample with index n
+ *     (the count of adds before it, from 0), with q = ceil(n / D), for every slot p = 0 .. P-1:
+ *            m = q + ((p - q) mod P);  k = m*D - n          the output slot p carries, and the tap this sample meets in it
+ *            k < ntap:  acc[p] = acc[p] + h[k] * x          the product rounded to double, then the sum: no fused multiply-add
+ *            k == 0:    frame m = acc[p];  acc[p] = +0.0
+ *     Frame m = sum_k h[k] x[m D - k] over the samples that exist (nothing is added for the time before sample 0); it completes with sample m D.
+ *     P D >= ntap, so a slot never carries two outputs.  After `count` samples ceil(count / D) frames have completed.
+ *   - Frames live on the device, frame m in row m mod cap.  read folds what is pending and copies the oldest min(max_frames, pending) frames in order
+ *     as frames[nread][cells] (the cells dense in the region's order, z fastest), gives the index of the first, and marks them read.  add is refused
+ *     with PF_ERR_STATE, nothing changed, when its sample would complete a frame (count % D == 0) while pending == cap.
+ *   - get_state folds and copies acc[P][cells] in slot order and state[npre][2][cells] (may be NULL); nothing is reset.  set_state drops pending
+ *     samples and unread frames and replaces acc (NULL: zeros), state (NULL: zeros) and the count; the next frame to complete is ceil(count / D).
+ *     pf_decim_count: the samples added, or the count given to set_state.  pf_decim_pending: the frames complete and not yet read.
+ *   - Between runs only, PF_ERR_STATE, an engine created with pf_opts.energy, handles of another engine or chain, several per engine, freeing by
+ *     pf_engine_destroy / pf_multi_destroy: all as pf_bandacc.  PF_ERR_ARG, with a message that names the field, for npre, ntap, factor, P, cap or
+ *     depth out of range, a tap or coefficient that is not finite, a null array, max_frames < 0, a negative count.
+ *   - Device memory, all of it the engine's: P + cap + 2 npre rows of doubles (rows padded to an even cell count), depth * cells Reals, and
+ *     -- npre > 0 -- depth rows of doubles.
+ *   - A chain: as the band accumulators, one per slab over its part; add is all or nothing, and a full cap is refused before any slab samples. */
+typedef struct pf_decim pf_decim;
+int     pf_engine_decim_create   (pf_engine *e, const pf_region *r, int32_t npre, const double *pre_sos, int32_t ntap, const double *taps, int32_t factor,
+                                  int64_t cap, int32_t depth, pf_decim **out);
+int     pf_engine_decim_add      (pf_engine *e, pf_decim *a);
+int     pf_engine_decim_read     (pf_engine *e, pf_decim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread);
+int     pf_engine_decim_get_state(pf_engine *e, pf_decim *a, double *acc, double *state);
+int     pf_engine_decim_set_state(pf_engine *e, pf_decim *a, const double *acc, const double *state, int64_t count);
+int64_t pf_decim_count           (const pf_decim *a);
+int64_t pf_decim_pending         (const pf_decim *a);
+int     pf_engine_decim_destroy  (pf_engine *e, pf_decim *a);
+int     pf_multi_decim_create    (pf_multi *m, const pf_region *r, int32_t npre, const double *pre_sos, int32_t ntap, const double *taps, int32_t factor,
+                                  int64_t cap, int32_t depth, pf_decim **out);
+int     pf_multi_decim_add       (pf_multi *m, pf_decim *a);
+int     pf_multi_decim_read      (pf_multi *m, pf_decim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread);
+int     pf_multi_decim_get_state (pf_multi *m, pf_decim *a, double *acc, double *state);
+int     pf_multi_decim_set_state (pf_multi *m, pf_decim *a, const double *acc, const double *state, int64_t count);
+int     pf_multi_decim_destroy   (pf_multi *m, pf_decim *a);
 int  pf_engine_timing(pf_engine *e, pf_timing *t, int32_t reset);
 /* switch the per-launch HIP events of pf_opts.timing on / off between runs (a host times its headline region without them
  * and collects kernel durations in a region of its own) */

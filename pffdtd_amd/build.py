@@ -52,16 +52,17 @@ def _deps(src):
     return [src] + sorted(seen)
 
 
-def build_hip(force=False, verbose=False):
-    """libpffdtd_hip.so: HIP kernels + C ABI, gfx950 only.  One object per .hip file (csrc/_obj/), relinked when any changed."""
-    out = PKG / "libpffdtd_hip.so"
+def build_hip(force=False, verbose=False, extra_flags=(), out=None):
+    """libpffdtd_hip.so: HIP kernels + C ABI, gfx950 only.  One object per .hip file (csrc/_obj/), relinked when any changed.
+    extra_flags, out: a variant of the library beside it (measurement tools: another value of a compile-time constant); never the product."""
+    out = Path(out) if out else PKG / "libpffdtd_hip.so"
     objdir = CSRC / "_obj"
     objdir.mkdir(exist_ok=True)
     objs, relink = [], force or not out.exists()
     procs = []
     import hashlib
     for src in sorted(CSRC.glob("*.hip")):
-        flags = [*HIP_FLAGS, *FILE_FLAGS.get(src.name, [])]
+        flags = [*HIP_FLAGS, *FILE_FLAGS.get(src.name, []), *extra_flags]
         if os.environ.get("PFFDTD_DEV_F32") == "1" and src.name == "pf_engine.hip":  # development only: fp32 engine alone, half the compile time
             flags.append("-DPF_DEV_F32_ONLY")
         # the flags are part of the object's name: a changed flag set (e.g. the -fno-slp-vectorize pf_tb2_fcc.hip needs for
@@ -71,7 +72,7 @@ def build_hip(force=False, verbose=False):
         objs.append(obj)
         if force or _newer(obj, _deps(src)):
             for old in objdir.glob(src.stem + ".*o"):
-                if old != obj:
+                if old != obj and not extra_flags:  # (a variant's objects stand beside the product's)
                     old.unlink()
             cmd = [hipcc(), *flags, "-c", "-I", str(ROOT / "include"), "-I", str(CSRC), str(src), "-o", str(obj)]
             procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

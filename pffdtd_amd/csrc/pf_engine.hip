@@ -53,6 +53,7 @@ struct pf_engine {
    std::vector<pf_accum *> accums; // the handles of its field accumulators still alive (pf_engine_destroy frees those left)
    std::vector<pf_bandacc *> bands; // ... and of its band accumulators
    std::vector<pf_vbandacc *> vbands; // ... and of its vector band accumulators
+   std::vector<pf_decim *> decims; // ... and of its decimating recorders
 };
 pfeng::EngineBase *pf__new_engine_f64(const pf_simdata *sd, const pf_opts_x *o, int *rc); // pf_engine_f64.hip
 
@@ -126,7 +127,7 @@ int pf__engine_create_x(const pf_simdata *sd, const pf_opts_x *opts, pf_engine *
       return set_err(PF_ERR_ARG, "real_bytes must be 4 or 8 (got %d)", sd->real_bytes);
    }
    if (rc) { std::string keep = g_err; delete impl; g_err = keep; return rc; }
-   *out = new pf_engine{impl, {}, {}, {}};
+   *out = new pf_engine{impl, {}, {}, {}, {}};
    return PF_OK;
 }
 
@@ -194,6 +195,25 @@ int pf__engine_vband_set_x(pf_engine *e, pf_vbandacc *a, const double *sums, con
    a->count = count;
    return PF_OK;
 }
+// decimating recorders: the same rule
+static int decim_mine(pf_engine *e, const pf_decim *a, const char *what) {
+   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
+   if (!a) return set_err(PF_ERR_ARG, "%s: null pf_decim", what);
+   if (a->eng != e) return set_err(PF_ERR_ARG, "%s: the pf_decim belongs to another engine%s", what, a->chain ? " (it is a chain's: pf_multi_decim_*)" : "");
+   return PF_OK;
+}
+int pf__engine_decim_read_x(pf_engine *e, pf_decim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride) {
+   const int rc = decim_mine(e, a, "pf_engine_decim_read");
+   return rc ? rc : e->impl->decim_read(a->impl, frames, max_frames, first, nread, pitch, rowstride);
+}
+int pf__engine_decim_get_state_x(pf_engine *e, pf_decim *a, double *acc, double *state, int64_t pitch, int64_t rowstride) {
+   const int rc = decim_mine(e, a, "pf_engine_decim_get_state");
+   return rc ? rc : e->impl->decim_get_state(a->impl, acc, state, pitch, rowstride);
+}
+int pf__engine_decim_set_state_x(pf_engine *e, pf_decim *a, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count) {
+   const int rc = decim_mine(e, a, "pf_engine_decim_set_state");
+   return rc ? rc : e->impl->decim_set_state(a->impl, acc, state, pitch, rowstride, count);
+}
 int pf__engine_between_runs(pf_engine *e) { return e && e->impl && e->impl->between_runs() ? 1 : 0; }
 
 extern "C" {
@@ -203,6 +223,7 @@ void pf_engine_destroy(pf_engine *e) {
    for (pf_accum *a : e->accums) delete a; // (their device memory is the engine's: freed with it)
    for (pf_bandacc *a : e->bands) delete a;
    for (pf_vbandacc *a : e->vbands) delete a;
+   for (pf_decim *a : e->decims) delete a;
    delete e->impl;
    delete e;
 }
@@ -301,6 +322,50 @@ int pf_engine_vband_destroy(pf_engine *e, pf_vbandacc *a) {
    int rc = vband_mine(e, a, "pf_engine_vband_destroy");
    if (rc || (rc = e->impl->vband_destroy(a->impl))) return rc;
    e->vbands.erase(std::find(e->vbands.begin(), e->vbands.end(), a));
+   delete a;
+   return PF_OK;
+}
+
+int pf_engine_decim_create(pf_engine *e, const pf_region *r, int32_t npre, const double *pre_sos, int32_t ntap, const double *taps, int32_t factor, int64_t cap,
+                           int32_t depth, pf_decim **out) {
+   const char *what = "pf_engine_decim_create";
+   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
+   if (!out) return set_err(PF_ERR_ARG, "%s: null out", what);
+   *out = nullptr;
+   void *impl = nullptr;
+   const int rc = e->impl->decim_create(r, npre, pre_sos, ntap, taps, factor, cap, depth, &impl);
+   if (rc) return rc;
+   pf_decim *a = new pf_decim();
+   a->eng = e; a->impl = impl; a->region = *r; a->factor = factor; a->cap = cap;
+   a->cells = pf_cut::region_counts(r, a->rc);
+   e->decims.push_back(a);
+   *out = a;
+   return PF_OK;
+}
+int pf_engine_decim_add(pf_engine *e, pf_decim *a) {
+   const int rc = decim_mine(e, a, "pf_engine_decim_add");
+   return rc ? rc : e->impl->decim_add(a->impl);
+}
+int pf_engine_decim_read(pf_engine *e, pf_decim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread) {
+   return pf__engine_decim_read_x(e, a, frames, max_frames, first, nread, 0, 0);
+}
+int pf_engine_decim_get_state(pf_engine *e, pf_decim *a, double *acc, double *state) { return pf__engine_decim_get_state_x(e, a, acc, state, 0, 0); }
+int pf_engine_decim_set_state(pf_engine *e, pf_decim *a, const double *acc, const double *state, int64_t count) {
+   return pf__engine_decim_set_state_x(e, a, acc, state, 0, 0, count);
+}
+// (an engine's handle asks the engine's object; a chain's keeps the two numbers itself)
+static void decim_numbers(const pf_decim *a, int64_t *count, int64_t *pending) {
+   *count = *pending = -1;
+   if (!a) return;
+   if (a->chain) { *count = a->count; *pending = (a->count + a->factor - 1) / a->factor - a->rd; }
+   else if (a->eng && a->eng->impl) a->eng->impl->decim_info(a->impl, count, pending);
+}
+int64_t pf_decim_count(const pf_decim *a) { int64_t c, p; decim_numbers(a, &c, &p); return c; }
+int64_t pf_decim_pending(const pf_decim *a) { int64_t c, p; decim_numbers(a, &c, &p); return p; }
+int pf_engine_decim_destroy(pf_engine *e, pf_decim *a) {
+   int rc = decim_mine(e, a, "pf_engine_decim_destroy");
+   if (rc || (rc = e->impl->decim_destroy(a->impl))) return rc;
+   e->decims.erase(std::find(e->decims.begin(), e->decims.end(), a));
    delete a;
    return PF_OK;
 }

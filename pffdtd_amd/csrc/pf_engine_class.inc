@@ -32,6 +32,7 @@
 #include "pf_accum.h"
 #include "pf_band.h"
 #include "pf_vband.h"
+#include "pf_decim.h"
 
 // shared between the two units (defined in pf_engine.hip)
 extern "C" void pf__set_error(const char *msg);
@@ -73,6 +74,13 @@ struct EngineBase {
    virtual int vband_get(void *a, double *sums, double *state, int64_t pitch, int64_t rowstride) = 0;
    virtual int vband_set(void *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride) = 0;
    virtual int vband_destroy(void *a) = 0;
+   virtual int decim_create(const pf_region *r, int npre, const double *pre_sos, int ntap, const double *taps, int factor, int64_t cap, int depth, void **out) = 0; // decimating recorders (pf_engine_decim.inc)
+   virtual int decim_add(void *a) = 0;
+   virtual int decim_read(void *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride) = 0;
+   virtual int decim_get_state(void *a, double *acc, double *state, int64_t pitch, int64_t rowstride) = 0;
+   virtual int decim_set_state(void *a, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count) = 0;
+   virtual int decim_info(void *a, int64_t *count, int64_t *pending) const = 0;
+   virtual int decim_destroy(void *a) = 0;
    virtual bool between_runs() const = 0; // not inside a split-phase step or pass
    virtual int save_state(pf_state *st) = 0;
    virtual int load_state(const pf_state *st) = 0;
@@ -1096,6 +1104,7 @@ template <typename Real> struct Engine : EngineBase {
 #include "pf_engine_accum.inc"
 #include "pf_engine_band.inc"
 #include "pf_engine_vband.inc"
+#include "pf_engine_decim.inc"
    void *stream(int which) override { return which == 1 ? (void *)s_edge : (void *)s_main; }
 };
 

@@ -621,6 +621,13 @@ void vband_add_slab(Shared &S, int g, pf_vbandacc *a, int64_t bin) {
    ECHK(g, pf_engine_vband_add(S.eng[g], a->part[g], bin));
 }
 
+// ... and of a decimating recorder
+void decim_add_slab(Shared &S, int g, pf_decim *a) {
+   if (S.err.load() || !S.eng[g] || !a->part[g]) return;
+   MCHK(g, hipSetDevice(S.dev[g]));
+   ECHK(g, pf_engine_decim_add(S.eng[g], a->part[g]));
+}
+
 void finish_slab(Shared &S, int g) {
    if (!S.eng[g]) return;
    hipSetDevice(S.dev[g]);
@@ -704,7 +711,7 @@ struct pf_multi {
    std::mutex mu;
    std::condition_variable cv_cmd, cv_done;
    int64_t cmd_seq = 0, cmd_n0 = 0, cmd_ns = 0;
-   int cmd_kind = 0;                 // 1 run, 2 quit, 3 save the state, 4 load it, 5 cut a region of a field, 6 add a sample to a field accumulator, 7 to a band accumulator, 8 to a vector band accumulator
+   int cmd_kind = 0;                 // 1 run, 2 quit, 3 save the state, 4 load it, 5 cut a region of a field, 6 add a sample to a field accumulator, 7 to a band accumulator, 8 to a vector band accumulator, 9 to a decimating recorder
    pf_accum *cmd_accum = nullptr;    // 6: the chain's accumulator and the sample's weights
    const double *cmd_w = nullptr;
    pf_bandacc *cmd_band = nullptr;   // 7: the chain's band accumulator and the sample's bin
@@ -712,6 +719,8 @@ struct pf_multi {
    std::vector<pf_bandacc *> bands;  // the chain's band accumulators still alive
    pf_vbandacc *cmd_vband = nullptr; // 8: the chain's vector band accumulator (its bin: cmd_bin)
    std::vector<pf_vbandacc *> vbands; // the chain's vector band accumulators still alive
+   pf_decim *cmd_decim = nullptr;    // 9: the chain's decimating recorder
+   std::vector<pf_decim *> decims;   // the chain's decimating recorders still alive
    std::vector<pf_accum *> accums;   // the chain's field accumulators still alive (pf_multi_destroy frees those left)
    pf_state *cmd_state = nullptr;    // ... from / into these global arrays
    pf_region cmd_region{};           // 5: the region (checked), its counts, the field, the caller's dense array
@@ -750,6 +759,7 @@ void worker(pf_multi *m, int g) {
       else if (kind == 6) accum_add_slab(S, g, m->cmd_accum, m->cmd_w);
       else if (kind == 7) band_add_slab(S, g, m->cmd_band, m->cmd_bin);
       else if (kind == 8) vband_add_slab(S, g, m->cmd_vband, m->cmd_bin);
+      else if (kind == 9) decim_add_slab(S, g, m->cmd_decim);
       else run_slabs(S, g, g + 1, local, n0, ns);
       S.bar.wait(local, S.err, S.bar_timeout);
       { std::lock_guard<std::mutex> lk(m->mu); m->done++; }
@@ -1454,6 +1464,156 @@ int pf_multi_vband_destroy(pf_multi *m, pf_vbandacc *a) {
    return rc;
 }
 
+// ---- decimating recorders of a chain: the band accumulators' scheme, no new cut code.  A slab's part is an engine object over region_part(...).local;
+// the parts take every sample together, so their counts and frames agree and the chain keeps `count` and `rd` itself: what a full `cap` refuses and
+// how many frames a read gives are decided here, before any slab is asked.
+static int decim_chain(pf_multi *m, const pf_decim *a, const char *what) {
+   if (!a) return fail("%s: null pf_decim", what);
+   if (a->chain != m) return fail("%s: the pf_decim belongs to another engine or chain", what);
+   return PF_OK;
+}
+
+int pf_multi_decim_create(pf_multi *m, const pf_region *r, int32_t npre, const double *pre_sos, int32_t ntap, const double *taps, int32_t factor, int64_t cap,
+                          int32_t depth, pf_decim **out) {
+   const char *what = "pf_multi_decim_create";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_decim_create(S.eng[0], r, npre, pre_sos, ntap, taps, factor, cap, depth, out);
+   if (!r) return fail("%s: null pf_region", what);
+   if (!out) return fail("%s: null out", what);
+   *out = nullptr;
+   const int64_t N[3] = {m->sd->Nx, m->sd->Ny, m->sd->Nz};
+   char msg[256], full[320];
+   std::unique_ptr<pf_decim> a(new pf_decim());
+   if ((a->cells = pf_cut::region_check(r, N, a->rc, msg, sizeof msg)) < 0) { snprintf(full, sizeof full, "%s: %s", what, msg); return fail("%s", full); }
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   a->chain = m; a->region = *r; a->factor = factor; a->cap = cap;
+   a->part.assign((size_t)S.G, nullptr);
+   for (int g = 0; g < S.G; g++) {
+      const pf_cut::RegionPart p = pf_cut::region_part(*r, a->rc, S.slabs[g], S.along_z);
+      if (p.empty) continue;
+      const int rc = pf_engine_decim_create(S.eng[g], &p.local, npre, pre_sos, ntap, taps, factor, cap, depth, &a->part[g]); // (a bad count, tap or coefficient: the first slab's message names it)
+      if (rc) {
+         const std::string keep = pf_last_error();
+         for (int h = 0; h < g; h++) if (a->part[h]) pf_engine_decim_destroy(S.eng[h], a->part[h]);
+         pf__set_error(keep.c_str());
+         return rc;
+      }
+   }
+   m->decims.push_back(a.get());
+   *out = a.release();
+   return PF_OK;
+}
+
+int pf_multi_decim_add(pf_multi *m, pf_decim *a) {
+   const char *what = "pf_multi_decim_add";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_decim_add(S.eng[0], a);
+   if (decim_chain(m, a, what)) return PF_ERR_ARG;
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   // all or nothing: the slab threads are idle, so every engine can be asked here, before any of them takes the sample
+   for (int g = 0; g < S.G; g++)
+      if (!pf__engine_between_runs(S.eng[g])) {
+         char b[256];
+         snprintf(b, sizeof b, "%s: slab %d is inside a pair or triple (u^{n+1} is not complete in memory): no slab took the sample; advance a step, or create the chain with "
+                               "PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES", what, g);
+         pf__set_error(b);
+         return PF_ERR_STATE;
+      }
+   if (a->count % a->factor == 0 && (a->count + a->factor - 1) / a->factor - a->rd == a->cap) {
+      char b[256];
+      snprintf(b, sizeof b, "%s: sample %ld would complete frame %ld while cap = %ld frames are complete and unread: read some first", what, (long)a->count,
+               (long)(a->count / a->factor), (long)a->cap);
+      pf__set_error(b);
+      return PF_ERR_STATE;
+   }
+   if (m->one_thread) { for (int g = 0; g < S.G; g++) decim_add_slab(S, g, a); }
+   else {
+      { std::lock_guard<std::mutex> lk(m->mu); m->cmd_decim = a; }
+      post(m, 9, 0, 0);
+      wait_done(m);
+      if (m->broken && !S.err.load()) S.set_error(PF_ERR_HIP, "slab chain hung: a slab's host thread never came back");
+   }
+   const int rc = accum_status(S);
+   if (rc == PF_OK) a->count++;
+   return rc;
+}
+
+int pf_multi_decim_read(pf_multi *m, pf_decim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread) {
+   const char *what = "pf_multi_decim_read";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_decim_read(S.eng[0], a, frames, max_frames, first, nread);
+   if (decim_chain(m, a, what)) return PF_ERR_ARG;
+   if (!first || !nread) return fail(!first ? "%s: null first" : "%s: null nread", what);
+   if (max_frames < 0) return fail("%s: max_frames < 0", what);
+   if (max_frames > 0 && !frames) return fail("%s: null frames array", what);
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   for (int g = 0; g < S.G; g++)
+      if (!pf__engine_between_runs(S.eng[g])) { fail("%s: a slab is inside a pair or triple: valid between passes only", what); return PF_ERR_STATE; }
+   const int64_t n = std::min(max_frames, (a->count + a->factor - 1) / a->factor - a->rd);
+   for (int g = 0; g < S.G; g++) {
+      if (!a->part[g]) continue;
+      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
+      int64_t f1 = 0, n1 = 0;
+      const int rc = pf__engine_decim_read_x(S.eng[g], a->part[g], frames ? frames + p.out_off : nullptr, n, &f1, &n1, p.out_pitch, a->cells);
+      if (rc) return rc;
+      if (n1 != n || (n && f1 != a->rd)) { fail("%s: internal: a slab's frames are not the chain's", what); return PF_ERR_STATE; }
+   }
+   *first = a->rd;
+   *nread = n;
+   a->rd += n;
+   return PF_OK;
+}
+
+int pf_multi_decim_get_state(pf_multi *m, pf_decim *a, double *acc, double *state) {
+   const char *what = "pf_multi_decim_get_state";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_decim_get_state(S.eng[0], a, acc, state);
+   if (decim_chain(m, a, what)) return PF_ERR_ARG;
+   if (!acc) return fail("%s: null acc array", what);
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   for (int g = 0; g < S.G; g++) {
+      if (!a->part[g]) continue;
+      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
+      const int rc = pf__engine_decim_get_state_x(S.eng[g], a->part[g], acc + p.out_off, state ? state + p.out_off : nullptr, p.out_pitch, a->cells);
+      if (rc) return rc;
+   }
+   return PF_OK;
+}
+
+int pf_multi_decim_set_state(pf_multi *m, pf_decim *a, const double *acc, const double *state, int64_t count) {
+   const char *what = "pf_multi_decim_set_state";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_decim_set_state(S.eng[0], a, acc, state, count);
+   if (decim_chain(m, a, what)) return PF_ERR_ARG;
+   if (count < 0) return fail("%s: count < 0", what);
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   for (int g = 0; g < S.G; g++)
+      if (!pf__engine_between_runs(S.eng[g])) { fail("%s: a slab is inside a pair or triple: valid between passes only", what); return PF_ERR_STATE; }
+   for (int g = 0; g < S.G; g++) {
+      if (!a->part[g]) continue;
+      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
+      const int rc = pf__engine_decim_set_state_x(S.eng[g], a->part[g], acc ? acc + p.out_off : nullptr, state ? state + p.out_off : nullptr, p.out_pitch, a->cells, count);
+      if (rc) return rc;
+   }
+   a->count = count;
+   a->rd = (count + a->factor - 1) / a->factor;
+   return PF_OK;
+}
+
+int pf_multi_decim_destroy(pf_multi *m, pf_decim *a) {
+   const char *what = "pf_multi_decim_destroy";
+   if (!m) return fail("%s: null object", what);
+   Shared &S = m->S;
+   if (S.G == 1) return pf_engine_decim_destroy(S.eng[0], a);
+   if (decim_chain(m, a, what)) return PF_ERR_ARG;
+   int rc = PF_OK;
+   for (int g = 0; g < S.G; g++)
+      if (a->part[g] && S.eng[g]) { const int r1 = pf_engine_decim_destroy(S.eng[g], a->part[g]); if (r1 && !rc) rc = r1; }
+   m->decims.erase(std::find(m->decims.begin(), m->decims.end(), a));
+   delete a;
+   return rc;
+}
+
 int pf_multi_get_info(pf_multi *m, pf_multi_info *info) {
    if (!m || !info) return fail("pf_multi_get_info: null argument");
    const Shared &S = m->S;
@@ -1501,6 +1661,7 @@ void pf_multi_destroy(pf_multi *m) {
    for (pf_accum *a : m->accums) delete a; // (the slabs' parts went with their engines)
    for (pf_bandacc *a : m->bands) delete a;
    for (pf_vbandacc *a : m->vbands) delete a;
+   for (pf_decim *a : m->decims) delete a;
    for (auto &c : S.comm) if (c) { g_rccl.CommDestroy(c); c = nullptr; }
    delete m;
 }

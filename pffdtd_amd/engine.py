@@ -102,6 +102,9 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_grid_bytes", "p
            "pf_multi_bandacc_create", "pf_multi_bandacc_add", "pf_multi_bandacc_get", "pf_multi_bandacc_set", "pf_multi_bandacc_destroy",
            "pf_engine_vband_create", "pf_engine_vband_add", "pf_engine_vband_get", "pf_engine_vband_set", "pf_engine_vband_destroy", "pf_vbandacc_count",
            "pf_multi_vband_create", "pf_multi_vband_add", "pf_multi_vband_get", "pf_multi_vband_set", "pf_multi_vband_destroy",
+           "pf_engine_decim_create", "pf_engine_decim_add", "pf_engine_decim_read", "pf_engine_decim_get_state", "pf_engine_decim_set_state", "pf_engine_decim_destroy",
+           "pf_decim_count", "pf_decim_pending",
+           "pf_multi_decim_create", "pf_multi_decim_add", "pf_multi_decim_read", "pf_multi_decim_get_state", "pf_multi_decim_set_state", "pf_multi_decim_destroy",
            "pf_engine_energy_cfg", "pf_engine_run_energy", "pf_run_sim_devices", "pf_slab_partition", "pf_slab_partition_w", "pf_slab_partition_axis", "pf_slab_wall_scale",
            "pf_multi_create", "pf_multi_run", "pf_multi_get_info", "pf_multi_get_slab", "pf_multi_destroy",
            "pf_rccl_unique_id", "pf_rccl_comm_create", "pf_rccl_exchange", "pf_rccl_comm_destroy"]
@@ -205,12 +208,21 @@ def lib():
             getattr(L, pre + "_vband_get").argtypes = [vp, vp, vp, vp]
             getattr(L, pre + "_vband_set").argtypes = [vp, vp, vp, vp, i64]
             getattr(L, pre + "_vband_destroy").argtypes = [vp, vp]
+            getattr(L, pre + "_decim_create").argtypes = [vp, ctypes.POINTER(PfRegion), i32, vp, i32, vp, i32, i64, i32, ctypes.POINTER(vp)]
+            getattr(L, pre + "_decim_add").argtypes = [vp, vp]
+            getattr(L, pre + "_decim_read").argtypes = [vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+            getattr(L, pre + "_decim_get_state").argtypes = [vp, vp, vp, vp]
+            getattr(L, pre + "_decim_set_state").argtypes = [vp, vp, vp, vp, i64]
+            getattr(L, pre + "_decim_destroy").argtypes = [vp, vp]
         L.pf_accum_count.restype = i64
         L.pf_accum_count.argtypes = [vp]
         L.pf_bandacc_count.restype = i64
         L.pf_bandacc_count.argtypes = [vp]
         L.pf_vbandacc_count.restype = i64
         L.pf_vbandacc_count.argtypes = [vp]
+        for f in (L.pf_decim_count, L.pf_decim_pending):
+            f.restype = i64
+            f.argtypes = [vp]
         dp = ctypes.POINTER(ctypes.c_double)
         L.pf_engine_energy_cfg.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, dp]
         L.pf_engine_run_energy.argtypes = [vp, i64, i64, dp, dp, dp]
@@ -497,6 +509,95 @@ class VectorBandAccumulator:
             pass
 
 
+class DecimatingRecorder:
+    """Per cell of a region, on the device (pf_engine_decim_* / pf_multi_decim_*): every sample u^n through the shared sections pre_sos [npre, 6] and a
+    FIR of taps `taps`, every `factor`-th output kept as a frame; up to `cap` frames wait on the device for read().
+    Made by HipEngine.decimating_recorder / HipMulti.decimating_recorder; it lives no longer than the object that made it."""
+
+    def __init__(self, owner, prefix, lo, hi, stride, pre_sos, taps, factor, cap, depth):
+        try:
+            r = PfRegion((ctypes.c_int64 * 3)(*[int(v) for v in lo]), (ctypes.c_int64 * 3)(*[int(v) for v in hi]), (ctypes.c_int64 * 3)(*[int(v) for v in stride]))
+        except TypeError as e:
+            raise PfError(f"decimating_recorder: lo, hi and stride are three integers each ({e})")
+        pre = _sos5("pre_sos", pre_sos, 1)
+        h = np.ascontiguousarray([] if taps is None else taps, dtype=np.float64)
+        if h.ndim != 1:
+            raise PfError(f"decimating_recorder: taps has shape {h.shape}: a vector of ntap values is expected")
+        L = lib()
+        self._owner, self._f = owner, {k: getattr(L, f"{prefix}_decim_{k}") for k in ("create", "add", "read", "get_state", "set_state", "destroy")}
+        self._a = ctypes.c_void_p()
+        self.npre, self.ntap, self.factor = int(pre.shape[0]), int(h.size), int(factor)
+        self.cap = int(cap) if cap else 64  # frames kept on the device between two reads
+        vp = ctypes.c_void_p
+        _check(self._f["create"](owner._h, ctypes.byref(r), self.npre, pre.ctypes.data_as(vp) if pre.size else None, self.ntap, h.ctypes.data_as(vp) if h.size else None,
+                                 self.factor, self.cap, int(depth), ctypes.byref(self._a)))
+        counts = (ctypes.c_int64 * 3)()
+        L.pf_region_count(ctypes.byref(r), counts)
+        self.cells = tuple(int(c) for c in counts)
+        self.slots = -(-self.ntap // self.factor)  # P
+        self.acc_shape = (self.slots,) + self.cells  # of get_state()'s acc
+        self.state_shape = (self.npre, 2) + self.cells  # ... and state
+
+    def add(self):
+        """the sample of the step the owner stands at; PfError (code 4) and nothing changed where it would complete a frame while `cap` frames wait"""
+        _check(self._f["add"](self._owner._h, self._a))
+
+    def read(self, max_frames=None):
+        """-> (first, frames float64 [nread, c0, c1, c2]): the oldest complete frames in order (all of them, or max_frames), marked read"""
+        n = self.pending if max_frames is None else int(max_frames)
+        out = np.empty((max(n, 0),) + self.cells, dtype=np.float64)
+        first, nread = ctypes.c_int64(), ctypes.c_int64()
+        _check(self._f["read"](self._owner._h, self._a, out.ctypes.data_as(ctypes.c_void_p) if out.size else None, n, ctypes.byref(first), ctypes.byref(nread)))
+        return int(first.value), out[:nread.value]
+
+    def get_state(self):
+        """-> (acc float64 [P, c0, c1, c2] in slot order, state float64 [npre, 2, c0, c1, c2]): pending samples folded in, nothing reset"""
+        a, s = np.empty(self.acc_shape, dtype=np.float64), np.empty(self.state_shape, dtype=np.float64)
+        _check(self._f["get_state"](self._owner._h, self._a, a.ctypes.data_as(ctypes.c_void_p), s.ctypes.data_as(ctypes.c_void_p) if s.size else None))
+        return a, s
+
+    def set_state(self, acc, state, count):
+        """replace the outputs in flight, the filter state and the count (None: zeros); pending samples and unread frames are dropped"""
+        arrs = []
+        for name, a, shape in (("acc", acc, self.acc_shape), ("state", state, self.state_shape)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.size != int(np.prod(shape)):
+                    raise PfError(f"DecimatingRecorder.set_state: {name} has {a.size} elements, the recorder holds {int(np.prod(shape))}")
+            arrs.append(a)
+        _check(self._f["set_state"](self._owner._h, self._a, *[None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p) for a in arrs], int(count)))
+
+    def _number(self, name):
+        if not (self._a.value and self._alive()):
+            raise PfError(f"DecimatingRecorder.{name}: the recorder or its owner is closed")
+        return int(getattr(lib(), f"pf_decim_{name}")(self._a))
+
+    @property
+    def count(self):
+        """samples added so far, or the count given to set_state"""
+        return self._number("count")
+
+    @property
+    def pending(self):
+        """frames complete and not yet read"""
+        return self._number("pending")
+
+    def _alive(self):
+        return bool(getattr(self._owner, "_h", None) and self._owner._h.value)
+
+    def close(self):
+        if getattr(self, "_a", None) and self._a.value:
+            if self._alive():
+                _check(self._f["destroy"](self._owner._h, self._a))
+            self._a = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def device_count():
     return int(lib().pf_device_count())
 
@@ -600,6 +701,11 @@ class HipMulti:
         """Band-filtered products of components of the whole scene's field in time bins (pf_multi_vband_create): every slab keeps the part it owns; a
         difference across a cut reads the slab's ghost plane.  add raises PfError (code PF_ERR_STATE) inside a pair or triple, as accumulator."""
         return VectorBandAccumulator(self, "pf_multi", lo, hi, stride, comp, pre_sos, band_sos, prod, nbin, depth)
+
+    def decimating_recorder(self, lo, hi, stride=(1, 1, 1), pre_sos=None, taps=None, factor=1, cap=0, depth=0):
+        """Low-pass filtered, decimated frames of a region of the whole scene (pf_multi_decim_create): every slab keeps the part it owns.  add raises
+        PfError (code 4) and takes no sample while a slab is inside a pair or triple, or when `cap` frames wait unread."""
+        return DecimatingRecorder(self, "pf_multi", lo, hi, stride, pre_sos, taps, factor, cap, depth)
 
     def slab(self, g):
         """-> dict(x0, x1, device, paired, steps_per_pass, engine): engine = a non-owning HipEngine view of slab g's engine (state_grids, timing)"""
@@ -764,6 +870,11 @@ class HipEngine:
         along file x / y / z) through pre_sos [ncomp, npre, 6] and, per band, band_sos [nband, nsec, 6]; the products prod [nprod, 3] = (i, j, mode) of
         two filtered components summed into the time bin given to add(bin) -- a VectorBandAccumulator."""
         return VectorBandAccumulator(self, "pf_engine", lo, hi, stride, comp, pre_sos, band_sos, prod, nbin, depth)
+
+    def decimating_recorder(self, lo, hi, stride=(1, 1, 1), pre_sos=None, taps=None, factor=1, cap=0, depth=0):
+        """Per cell of the region, on the device (pf_engine_decim_create): every sample u^n through the sections pre_sos [npre, 6] and the FIR `taps`,
+        every factor-th output kept as a frame, up to `cap` (0: 64) of them between two reads -- a DecimatingRecorder."""
+        return DecimatingRecorder(self, "pf_engine", lo, hi, stride, pre_sos, taps, factor, cap, depth)
 
     def set_grid(self, which, a):
         a = np.ascontiguousarray(a, dtype=self.dtype)

@@ -55,6 +55,14 @@ octave bands `--dir-bands 125,250,500`, multiplied and summed ON THE DEVICE into
 what the lateral energy fractions LF, LFC and the intensity maps are functions of (directional.parameters).  Cartesian grids only.  Everything else
 as the decay arguments: the run is cut at every step from N on, a chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (one line says
 so), `--resume` restores sums and filter state from the file, and without these arguments nothing about a run changes.
+
+Decimated field recordings (pffdtd_amd/recordings.py): `--rec-planes` / `--rec-box` (the syntax of the field arguments) name regions whose cells'
+pressure is low-pass filtered ON THE DEVICE at EVERY step from `--rec-first N` (default 0) on by a verified linear-phase FIR -- flat up to
+`--rec-fpass HZ`, `--rec-atten 80` dB down from the new Nyquist frequency on -- and kept at every `--rec-factor D`-th step: the impulse response of
+every cell at the rate 1 / (D Ts), not aliased, in `--rec-dtype f4|f8`, appended to `--rec-file FILE` (default sim_recordings.h5 beside sim_outs.h5)
+as the run goes and completed at every checkpoint and at the end.  Everything else as the decay arguments: the run is cut at every step from N on,
+a chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (one line says so), `--resume` restores the outputs in flight and the filter state
+from the file, and without these arguments nothing about a run changes.
 """
 import argparse
 import os
@@ -64,6 +72,7 @@ from pathlib import Path
 from . import checkpoint, engine, fields, sim_data, spectra
 from . import decay as decay_mod
 from . import directional as dir_mod
+from . import recordings as rec_mod
 
 
 def _summary(sd, tm, el):
@@ -117,7 +126,7 @@ def _run_chain(a, sd, m):
     """all Nt steps of a chain object, in one go or in chunks with progress reports; returns (seconds, timing of the busiest slab).
     With --resume / --checkpoint / --stop-after: from the resumed step, to the step the run stops after (a.stopped_at: less than Nt then)."""
     live = range(m.nslabs)
-    if a.resume or a.checkpoint or a.field_every or a.spectrum or a.decay or a.directional:
+    if a.resume or a.checkpoint or a.field_every or a.spectrum or a.decay or a.directional or a.rec:
         return _run_chain_checkpointed(a, sd, m)
     t0 = time.perf_counter()
     if not a.progress:
@@ -205,11 +214,31 @@ def _field_directional(a, sd, m, resume_at):
     return fv
 
 
+def _field_recording(a, sd, m, resume_at):
+    """the FieldRecording of --rec-planes / --rec-box on chain m (None without them); a resumed run's outputs in flight and filter state are restored"""
+    if not a.rec:
+        return None
+    N = (sd.Nx, sd.Ny, sd.Nz)
+    try:
+        regions = [r for spec in a.rec_planes for r in fields.parse_planes(spec, N)] + [fields.parse_box(spec, N) for spec in a.rec_box]
+        path = a.rec_file if a.rec_file else Path(a.data_dir) / "sim_recordings.h5"
+        fr = rec_mod.FieldRecording(path, sd, regions, a.rec_factor, a.rec_fpass, a.rec_atten, a.rec_first, dtype=a.rec_dtype, resume_at=resume_at)
+    except ValueError as e:
+        raise SystemExit(str(e).replace("--field-", "--rec-"))
+    try:
+        fr.attach(m)
+    except engine.PfError as e:  # (a factor or a tap count the engine refuses: it names the field)
+        raise SystemExit(f"--rec-planes / --rec-box: {e}")
+    return fr
+
+
 def _chain_flags(a, nslabs):
     """multi_flags of the chain: sampled for a spectrum or a decay map, its slabs take single steps (a sample is never shifted, and no slab answers
     inside a pass)"""
-    if not (a.spectrum or a.decay or a.directional) or nslabs < 2:
+    if not (a.spectrum or a.decay or a.directional or a.rec) or nslabs < 2:
         return 0
+    if a.rec:
+        print("--field recording: the chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (its slabs take single steps: every step is sampled)")
     if a.directional:
         print("--field directional: the chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (its slabs take single steps: every step is sampled)")
     if a.decay:
@@ -236,6 +265,7 @@ def _run_chain_checkpointed(a, sd, m):
     fs = _field_spectrum(a, sd, m, n if a.resume else None)
     fd = _field_decay(a, sd, m, n if a.resume else None)
     fv = _field_directional(a, sd, m, n if a.resume else None)
+    fr = _field_recording(a, sd, m, n if a.resume else None)
     end = sd.Nt if a.stop_after is None else min(max(a.stop_after, n), sd.Nt)
     every = a.checkpoint_every if a.checkpoint else 0
     t0 = time.perf_counter()
@@ -249,6 +279,8 @@ def _run_chain_checkpointed(a, sd, m):
         fd.take(m, n)
     if fv and fv.due(n) and n < end:
         fv.take(m, n)
+    if fr and fr.due(n) and n < end:
+        fr.take(m, n)
     while n < end:
         k = end - n
         if a.progress:
@@ -263,6 +295,8 @@ def _run_chain_checkpointed(a, sd, m):
             k = fd.next_step(n + 1) - n
         if fv and fv.next_step(n + 1) < n + k:
             k = fv.next_step(n + 1) - n
+        if fr and fr.next_step(n + 1) < n + k:
+            k = fr.next_step(n + 1) - n
         tc = time.perf_counter()
         m.run(n, k)
         n += k
@@ -280,12 +314,16 @@ def _run_chain_checkpointed(a, sd, m):
                 fd.write()
             if fv:
                 fv.write()
+            if fr:
+                fr.write()
         if fs and fs.due(n) and n < end:
             fs.take(m, n)
         if fd and fd.due(n) and n < end:
             fd.take(m, n)
         if fv and fv.due(n) and n < end:
             fv.take(m, n)
+        if fr and fr.due(n) and n < end:
+            fr.take(m, n)
         now = time.perf_counter()
         tms = [m.slab(g)["engine"].timing(reset=True) for g in live]
         air = max(t["air_ms_total"] for t in tms) * 1e-3
@@ -309,6 +347,10 @@ def _run_chain_checkpointed(a, sd, m):
         fv.write()
         print(f"--field directional maps of {fv.count} samples in {fv.bands.size} bands along {','.join('xyz'[k - 1] for k in fv.axes)}, bins of {fv.bin_steps} steps: {fv.path}", flush=True)
         fv.close()
+    if fr:
+        fr.write()
+        print(f"--field recording of {fr.count} samples, {fr.frames} frames at every {fr.factor}th step through {fr.taps.size} taps: {fr.path}", flush=True)
+        fr.close()
     return time.perf_counter() - t0, {"air_ms_total": air_all * 1e3, "step_ms_total": step_all * 1e3}
 
 
@@ -458,7 +500,9 @@ def main():
     p.add_argument("--dir-bin-ms", type=float, default=5.0, metavar="MS", help="... in time bins of MS milliseconds (default 5)")
     p.add_argument("--dir-first", type=int, default=0, metavar="N", help="... at every step from N on (default 0)")
     p.add_argument("--dir-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_directional.h5 in the data folder)")
+    rec_mod.add_arguments(p)
     a = p.parse_args()
+    rec_mod.check_arguments(p, a)
     a.directional = bool(a.dir_planes or a.dir_box)
     if a.directional != bool(a.dir_bands) or a.dir_bin_ms <= 0 or a.dir_first < 0:
         p.error("--dir-planes / --dir-box need --dir-bands (and the other way round); --dir-bin-ms: positive, --dir-first: not negative")
@@ -495,6 +539,8 @@ def main():
         raise SystemExit("--decay-planes / --decay-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
     if world > 1 and a.directional and not a.devices:
         raise SystemExit("--dir-planes / --dir-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
+    if world > 1 and a.rec and not a.devices:
+        raise SystemExit("--rec-planes / --rec-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
     if a.devices:
         return run_devices(a, [int(v) for v in a.devices.split(",")])
     if world > 1:
