@@ -458,8 +458,21 @@ int     pf_multi_bandacc_destroy (pf_multi *m, pf_bandacc *a);
  *   - A region with a difference component along axis a keeps one cell clear of both faces along a: lo[a] >= 1 and its last cell <= N[a] - 2;
  *     otherwise PF_ERR_ARG names the axis.  The virtual ghost shell is materialised when the region, WIDENED by one cell along its difference axes,
  *     holds a face cell: the pf_engine_get_region rule applied to the cells actually read.
- *   - Difference components are refused by name on fcc_flag != 0: an axis neighbour at +-1 is no node of the checkerboard, and a stencil over the
- *     FCC neighbours is out of scope here.  comp = {0} alone works on every grid.
+ *   - Components 1 / 2 / 3 are refused by name on fcc_flag != 0: an axis neighbour at +-1 is no node of the checkerboard.  comp = {0} alone works on
+ *     every grid.
+ *   - Components 4, 5, 6 are the LATTICE DIFFERENCE along FILE x, y, z, on fcc_flag 1 and 2 only (refused by name, comp[k], on fcc_flag == 0).  Eight
+ *     of a node's twelve neighbours sit at +-1 along any axis, in four opposite pairs; with the + offsets o0 .. o3, in the order of the 12-point
+ *     stencil (synth.FCC_OFFS),
+ *         4 (x): (+1,+1,0) (+1,0,+1) (+1,-1,0) (+1,0,-1)     5 (y): (+1,+1,0) (0,+1,+1) (-1,+1,0) (0,+1,-1)     6 (z): (0,+1,+1) (+1,0,+1) (0,-1,+1) (-1,0,+1)
+ *         L_a(c) = ((u[c+o0] - u[c-o0]) + (u[c+o1] - u[c-o1])) + ((u[c+o2] - u[c-o2]) + (u[c+o3] - u[c-o3]))          = 8 h du/da + O(h^3)
+ *     seven operations in the field's own precision, each rounded once, in exactly this association, no contraction.  Every operand is bit for bit
+ *     the cell pf_engine_get_region(1, ...) gives right after the add, in STORED coordinates: on a folded grid (fcc_flag 2) folded ones, the fold row
+ *     Ny - 1 holding the copy of row Ny - 2 -- an add whose cells read that row writes it first, from the row of u^n the next step copies again (an
+ *     engine whose shell lives in memory otherwise still carries the row of two steps ago there; nothing a later step reads changes).  No parity
+ *     logic runs on the device: a hole of a flag-1 grid is computed like any cell, from holes.  On a folded grid the stored +y of a cell with odd
+ *     ix + iy + iz is the room's -y (pffdtd_amd/directional.py: fold_coordinates).  The value stays Real until the filters widen it.
+ *   - A region with any lattice component keeps one cell clear of ALL SIX faces (every L_a reads neighbours along all three axes); otherwise
+ *     PF_ERR_ARG names the first offending axis.  The ghost shell is materialised when the region widened by one cell on every axis holds a face cell.
  *   - pre_sos[ncomp][npre][5] (npre 0 .. 8; a shorter cascade is padded with 1 0 0 0 0), band_sos[nband][nsec][5]; a section and its three lines
  *     exactly as pf_bandacc above: the same association, every operation rounded to double once, no fused multiply-add.  Per component k,
  *     x_k = (double)component runs through pre_sos[k] in order; for every band b, y_k = x_k runs through band_sos[b] with component k's own state.
@@ -472,12 +485,14 @@ int     pf_multi_bandacc_destroy (pf_multi *m, pf_bandacc *a);
  *     pending and replaces sums, state (NULL: zeros) and the count.  pf_vbandacc_count: the samples added, or the count given to set.
  *   - Between runs only, PF_ERR_STATE, an engine created with pf_opts.energy, handles of another engine or chain, several per engine, freeing by
  *     pf_engine_destroy / pf_multi_destroy: all as pf_bandacc.  PF_ERR_ARG, with a message that names the field, also for ncomp outside 1 .. 4, a
- *     comp value outside 0 .. 3, a repeated component, nprod outside 1 .. 10, a product index >= ncomp, a mode outside 0 / 1, a coefficient that is
+ *     comp value outside 0 .. 6, a repeated component, nprod outside 1 .. 10, a product index >= ncomp, a mode outside 0 / 1, a coefficient that is
  *     not finite, depth outside 0 .. 8.
  *   - Device memory, all of it the engine's: nprod*nband*nbin rows of sums and ncomp*(npre + nband*nsec)*2 rows of state (doubles, rows padded to an
  *     even cell count), ncomp * depth * cells Reals, and -- npre > 0 -- ncomp * depth rows of doubles.
  *   - A chain: as the band accumulators, one per slab over its part; add is all or nothing.  A difference across the cut reads the slab's ghost
- *     plane, which between runs holds the neighbour's u^n (the exchange of the step that wrote u^n filled it; pf_multi_load_state fills it). */
+ *     plane, which between runs holds the neighbour's u^n (the exchange of the step that wrote u^n filled it; pf_multi_load_state fills it).  A
+ *     lattice difference beside a cut reads that plane at (y +- 1) and (z +- 1) too: it holds the neighbour's WHOLE plane.  The chain checks the
+ *     one-cell rule against the scene's faces, a slab its part against its own planes. */
 typedef struct pf_vbandacc pf_vbandacc;
 int     pf_engine_vband_create (pf_engine *e, const pf_region *r, int32_t ncomp, const int32_t *comp, int32_t npre, const double *pre_sos, int32_t nband, int32_t nsec,
                                 const double *band_sos, int32_t nprod, const int32_t *prod, int64_t nbin, int32_t depth, pf_vbandacc **out);

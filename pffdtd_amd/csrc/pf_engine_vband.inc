@@ -4,14 +4,20 @@
 // sections (state per component); products of two filtered components are summed into the time bin the caller names.  Component 0 is taken
 // exactly as a band accumulator's sample (region_to_slot: k_region_cut), a difference by k_region_diff into the component's ring slot; the ghost
 // shell is materialised when the region WIDENED by one cell along its difference axes holds a face cell -- the get_region rule applied to the
-// cells actually read.  A full ring is folded (k_vband_pre, k_vband_fold, in greedy pieces of 8, 4, 2, 1 samples); get, set and destroy fold or
-// drop what is pending.  Nothing a later step reads changes.  All device memory is `mem`'s.
+// cells actually read.  On an FCC grid (fcc_flag 1 / 2) the difference components are the LATTICE differences 4 / 5 / 6 instead: the four pair
+// differences over the eight FCC neighbours at +-1 along the axis, in stored coordinates, all requested ones by ONE k_region_lat launch per sample;
+// they read along all three axes, so the region keeps one cell clear of all six faces and the widening is by one cell on every axis.  A full
+// folded grid's add whose cells read the fold row Ny - 1 first makes that row the copy of row Ny - 2 of u^n (vband_add).  A full ring is folded
+// (k_vband_pre, k_vband_fold, in greedy pieces of 8, 4, 2, 1 samples); get, set and destroy fold or drop what is pending.  Nothing a later step
+// reads changes.  All device memory is `mem`'s.
    struct VBand {
       pf_region r{};
       int64_t c[3] = {0, 0, 0}, cells = 0, cstride = 0;
       int ncomp = 0, comp[pf::PF_VBAND_MAX_COMP] = {0, 0, 0, 0};
       int npre = 0, nband = 0, nsec = 0, nprod = 0, nbin = 0, depth = 0, fill = 0; // fill: samples in the ring
       bool shell = false;
+      int lat = 0; // bit 0 / 1 / 2: the lattice difference along file x / y / z is a component
+      bool fold_row = false; // ... and the region's last row is Ny - 2: its neighbours lie in the row above (a folded grid's fold row)
       double *S = nullptr, *st = nullptr, *coef = nullptr, *xpre = nullptr;
       int32_t *bins = nullptr, *prod = nullptr;
       Real *ring = nullptr;
@@ -39,7 +45,12 @@
       if (ncomp < 1 || ncomp > pf::PF_VBAND_MAX_COMP) return set_err(PF_ERR_ARG, "%s: ncomp = %d outside 1 .. %d", what, ncomp, pf::PF_VBAND_MAX_COMP);
       if (!comp) return set_err(PF_ERR_ARG, "%s: null comp", what);
       for (int k = 0; k < ncomp; k++) {
-         if (comp[k] < 0 || comp[k] > 3) return set_err(PF_ERR_ARG, "%s: comp[%d] = %d outside 0 (the cell) .. 3 (1 / 2 / 3: the difference along file x / y / z)", what, k, comp[k]);
+         if (comp[k] < 0 || comp[k] > 6)
+            return set_err(PF_ERR_ARG, "%s: comp[%d] = %d outside 0 (the cell) .. 6 (1 / 2 / 3: the difference along file x / y / z; 4 / 5 / 6: the lattice difference of an FCC grid)", what,
+                           k, comp[k]);
+         if (comp[k] >= 4 && !fcc)
+            return set_err(PF_ERR_ARG, "%s: comp[%d] = %d: a lattice difference (4 / 5 / 6) on fcc_flag == 0 -- its neighbours are the FCC stencil's; 1 / 2 / 3 are the differences of a "
+                                       "Cartesian grid", what, k, comp[k]);
          for (int m = 0; m < k; m++) if (comp[m] == comp[k]) return set_err(PF_ERR_ARG, "%s: comp[%d] = comp[%d] = %d: a repeated component", what, m, k, comp[k]);
       }
       if (nband < 1 || nband > pf::PF_BAND_MAX_BANDS) return set_err(PF_ERR_ARG, "%s: nband = %d outside 1 .. %d", what, nband, pf::PF_BAND_MAX_BANDS);
@@ -66,16 +77,23 @@
       a->cells = pf_cut::region_check(r, N, a->c, msg, sizeof msg);
       if (a->cells < 0) return set_err(PF_ERR_ARG, "%s: %s", what, msg);
       bool diff[3] = {false, false, false};
-      for (int k = 0; k < ncomp; k++) if (comp[k]) diff[comp[k] - 1] = true;
+      for (int k = 0; k < ncomp; k++) {
+         if (comp[k] >= 1 && comp[k] <= 3) diff[comp[k] - 1] = true;
+         if (comp[k] >= 4) a->lat |= 1 << (comp[k] - 4);
+      }
       if (fcc && (diff[0] || diff[1] || diff[2]))
-         return set_err(PF_ERR_ARG, "%s: comp: a difference component (1 / 2 / 3) on fcc_flag != 0 -- an axis neighbour at +-1 is no node of the checkerboard; comp = {0} alone works on "
-                                    "every grid", what);
+         return set_err(PF_ERR_ARG, "%s: comp: a difference component (1 / 2 / 3) on fcc_flag != 0 -- an axis neighbour at +-1 is no node of the checkerboard; comp 4 / 5 / 6 are the "
+                                    "lattice differences along file x / y / z, and comp = {0} alone works on every grid", what);
       for (int k = 0; k < 3; k++) {
          const int64_t last = r->lo[k] + (a->c[k] - 1) * r->stride[k];
+         if (a->lat && (r->lo[k] < 1 || last > N[k] - 2)) // (every L_a reads neighbours along all three axes)
+            return set_err(PF_ERR_ARG, "%s: a lattice difference needs the region one cell clear of all six faces, along file %s too: pf_region.lo[%d] = %ld >= 1 and its last cell "
+                                       "%ld <= %ld", what, axis_name[k], k, (long)r->lo[k], (long)last, (long)N[k] - 2);
          if (diff[k] && (r->lo[k] < 1 || last > N[k] - 2))
             return set_err(PF_ERR_ARG, "%s: a difference along file %s needs the region one cell clear of both faces along %s: pf_region.lo[%d] = %ld >= 1 and its last cell %ld <= %ld",
                            what, axis_name[k], axis_name[k], k, (long)r->lo[k], (long)last, (long)N[k] - 2);
-         const int64_t w = diff[k] ? 1 : 0; // the cells actually read
+         const int64_t w = diff[k] || a->lat ? 1 : 0; // the cells actually read
+         if (k == 1 && a->lat && last + 1 == N[1] - 1) a->fold_row = true;
          a->shell = a->shell || r->lo[k] - w == 0 || last + w == N[k] - 1;
       }
       a->r = *r;
@@ -137,6 +155,31 @@
       return PF_OK;
    }
 
+   // the lattice differences `mask` (bit a: along file axis a) of u^n over a region -> their ring slots, ONE launch per piece for all of them: diff_to_slot's
+   // pieces, k_region_lat in k_region_diff's place
+   int lat_to_slots(const pf_region &r, const int64_t *c, int mask, Real *const *slot) {
+      const bool planes = c[1] <= 65535;
+      const int64_t n0 = planes ? std::min<int64_t>(c[0], 65535) : 1, n1 = planes ? c[1] : 65535;
+      const size_t lds = (size_t)__builtin_popcount((unsigned)mask) * 32 * 33 * sizeof(Real);
+      for (int64_t i0 = 0; i0 < c[0]; i0 += n0)
+         for (int64_t j0 = 0; j0 < c[1]; j0 += n1) {
+            const pf::RegionPiece q{r.lo[0] + i0 * r.stride[0], r.lo[1] + j0 * r.stride[1], r.lo[2], r.stride[0], r.stride[1], r.stride[2],
+                                    std::min(n0, c[0] - i0), std::min(n1, c[1] - j0), c[2]};
+            const bool tiled = swz && q.n0 >= 2 && q.n2 >= 2;
+            int bzl = 0;
+            while (bzl < 8 && ((int64_t)1 << bzl) < q.n2) bzl++;
+            const dim3 g = tiled ? dim3((unsigned)cdiv(q.n2, 32), (unsigned)q.n1, (unsigned)cdiv(q.n0, 32))
+                                 : dim3((unsigned)cdiv(q.n2, (int64_t)1 << bzl), (unsigned)cdiv(q.n1, 256 >> bzl), (unsigned)q.n0);
+            const int64_t off = (i0 * c[1] + j0) * c[2];
+            Real *o[3];
+            for (int k = 0; k < 3; k++) o[k] = slot[k] ? slot[k] + off : nullptr;
+            if (swz) hipLaunchKernelGGL((pf::k_region_lat<Real, true>), g, dim3(256), tiled ? lds : 0, s_main, (const Real *)u1, o[0], o[1], o[2], q, Ny, P, tiled ? 1 : 0, bzl, mask);
+            else hipLaunchKernelGGL((pf::k_region_lat<Real, false>), g, dim3(256), 0, s_main, (const Real *)u1, o[0], o[1], o[2], q, Ny, P, 0, bzl, mask);
+            HIPCHK(hipGetLastError());
+         }
+      return PF_OK;
+   }
+
    // NT samples from ring position t0 on
    template <int NC, int NT> void launch_vband_fold(VBand *a, int t0) {
       const unsigned gx = (unsigned)cdiv(cdiv(a->cells, 2), 256);
@@ -190,11 +233,20 @@
       if ((lean || vg) && a->shell) { // the virtual ghost shell, once for all components
          launch_flips(s_main, grids());
          HIPCHK(hipGetLastError());
+      } else if (fold && a->lat && a->fold_row) {
+         // A folded grid's row Ny - 1 is the fold's ghost, the copy of row Ny - 2 of the SAME field: it is the other half of the room, not a face of it.
+         // The engines whose shell lives in memory write it at the start of the step that reads it (launch_flips), so between two runs u^n still
+         // carries the row of two steps ago.  Written here, from the same row the next step copies again: nothing that step reads changes.
+         hipLaunchKernelGGL(pf::k_flip_y<Real>, dim3((unsigned)cdiv(Nz, 256), (unsigned)Nx), dim3(256), 0, s_main, grids().cur, Nx, Ny, P, Nz, 4);
+         HIPCHK(hipGetLastError());
       }
+      Real *lslot[3] = {nullptr, nullptr, nullptr};
       for (int k = 0; k < a->ncomp; k++) {
          Real *slot = a->ring + ((int64_t)k * a->depth + a->fill) * a->cells;
+         if (a->comp[k] >= 4) { lslot[a->comp[k] - 4] = slot; continue; }
          if ((rc = a->comp[k] == 0 ? region_to_slot(a->r, a->c, false, slot) : diff_to_slot(a->r, a->c, a->comp[k] - 1, slot))) return rc;
       }
+      if (a->lat && (rc = lat_to_slots(a->r, a->c, a->lat, lslot))) return rc; // all of them in one launch
       a->hbins[(size_t)a->fill] = (int32_t)bin;
       a->fill++;
       if (a->fill == a->depth) return vband_fold(a);

@@ -1353,7 +1353,17 @@ int pf_multi_vband_create(pf_multi *m, const pf_region *r, int32_t ncomp, const 
    std::unique_ptr<pf_vbandacc> a(new pf_vbandacc());
    if ((a->cells = pf_cut::region_check(r, N, a->rc, msg, sizeof msg)) < 0) { snprintf(full, sizeof full, "%s: %s", what, msg); return fail("%s", full); }
    // the one-cell rule against the SCENE's faces (a slab checks its part against its own planes, where a cut is no face)
-   if (comp && ncomp >= 1 && ncomp <= 4)
+   if (comp && ncomp >= 1 && ncomp <= 4) {
+      bool lat = false; // a lattice difference (4 / 5 / 6) reads along all three axes; on a Cartesian scene the first slab refuses it by name
+      for (int k = 0; k < ncomp; k++) lat = lat || (comp[k] >= 4 && comp[k] <= 6);
+      for (int ax = 0; lat && m->sd->fcc_flag != 0 && ax < 3; ax++) {
+         const int64_t last = r->lo[ax] + (a->rc[ax] - 1) * r->stride[ax];
+         if (r->lo[ax] < 1 || last > N[ax] - 2) {
+            snprintf(full, sizeof full, "%s: a lattice difference needs the region one cell clear of all six faces, along file %c too: pf_region.lo[%d] = %ld >= 1 and its last cell "
+                                        "%ld <= %ld", what, "xyz"[ax], ax, (long)r->lo[ax], (long)last, (long)N[ax] - 2);
+            return fail("%s", full);
+         }
+      }
       for (int k = 0; k < ncomp; k++) {
          const int ax = comp[k] - 1;
          if (ax < 0 || ax > 2) continue;
@@ -1364,6 +1374,7 @@ int pf_multi_vband_create(pf_multi *m, const pf_region *r, int32_t ncomp, const 
             return fail("%s", full);
          }
       }
+   }
    if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
    a->chain = m; a->region = *r; a->nbin = nbin;
    a->part.assign((size_t)S.G, nullptr);

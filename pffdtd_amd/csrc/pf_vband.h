@@ -18,6 +18,11 @@
 // registers before anything goes to LDS, so the tiled form keeps ONE 32 x 33 tile of Real and the bank picture of pf_region.h as it is (two
 // operand tiles would double the LDS for nothing: the operands are never needed apart).  On exchanged storage a difference along file x has its
 // operands one element apart (same lines), along file z one storage plane apart.
+// k_region_lat<Real, EXCH> is the same kernel for the LATTICE differences of an FCC grid (comp 4 / 5 / 6: the four pair differences over the eight
+// FCC neighbours at +-1 along file x / y / z, seven operations in Real): ONE launch per sample for ALL the requested ones -- a mask says which --,
+// each of the at most twelve distinct neighbours loaded once, the sums formed in registers, one 32 x 33 tile of Real PER REQUESTED component in the
+// tiled form (dynamic LDS; the bank picture of pf_region.h per tile), each component stored into its own ring slot.  Stored coordinates, no parity
+// logic: a folded grid's fold row is a row like any other, a checkerboard's hole is computed from holes.
 // A fold of NT pending samples is k_vband_pre<Real, NT> (npre > 0; grid.y = the component) and ONE k_vband_fold<In, NC, NT> on a grid of
 // (cdiv(cdiv(cells, 2), 256), nband): a thread owns two adjacent cells (16-byte loads and stores, lanes along cells), runs all NC components'
 // sections of its band over the NT samples in registers -- y[NC][NT] of two cells, 2 * NC * NT doubles, never go to memory -- and then walks the
@@ -28,7 +33,8 @@
 // Instantiated for NC = 1 .. 4 and NT in {1, 2, 4, 8}: a partly filled ring is folded greedily (7 = 4 + 2 + 1), the samples still in call order,
 // so the pieces never change a bit.
 //
-// PF_VBAND_DEFAULT_DEPTH: the fastest of the depths 1, 2, 4, 8 on the plane case of tools/field_directional_cost.py (profiles/field_directional.txt).
+// PF_VBAND_DEFAULT_DEPTH: the fastest of the depths 1, 2, 4, 8 on the plane case of tools/field_directional_cost.py (profiles/field_directional.txt),
+// and of its --fcc case with the lattice differences (profiles/field_directional_fcc.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -80,6 +86,89 @@ static __global__ void __launch_bounds__(256) k_region_diff(const Real *__restri
    const int64_t fx = q.lo0 + i * q.s0, fy = q.lo1 + j * q.s1, fz = q.lo2 + k * q.s2;
    const int64_t at = EXCH ? (fz * Ny + fy) * P + fx : (fx * Ny + fy) * P + fz;
    stage[(i * q.n1 + j) * q.n2 + k] = st[at + step] - st[at - step];
+}
+
+// The twelve FCC neighbours of a cell in FILE coordinates, named by the plane they lie in and the signs of its two offsets: xy_pm = (+1, -1, 0),
+// xz_mp = (-1, 0, +1), yz_pp = (0, +1, +1).  A lattice difference along an axis reads the eight of them that sit at +-1 along it.
+template <typename Real> struct LatNb {
+   Real xy_pp, xy_mm, xy_pm, xy_mp, xz_pp, xz_mm, xz_pm, xz_mp, yz_pp, yz_mm, yz_pm, yz_mp;
+};
+
+// the neighbours of the cell at storage offset `at` that `mask` (bit 0 / 1 / 2: the lattice difference along file x / y / z) needs, each loaded once;
+// sx, sy, sz: the storage offsets of one cell along file x, y, z.  The caller keeps the region one cell clear of all six faces.
+template <typename Real>
+static __device__ __forceinline__ LatNb<Real> lat_load(const Real *__restrict__ st, int64_t at, int64_t sx, int64_t sy, int64_t sz, int mask) {
+   LatNb<Real> n{};
+   if (mask & 3) { n.xy_pp = st[at + sx + sy]; n.xy_mm = st[at - sx - sy]; n.xy_pm = st[at + sx - sy]; n.xy_mp = st[at - sx + sy]; }
+   if (mask & 5) { n.xz_pp = st[at + sx + sz]; n.xz_mm = st[at - sx - sz]; n.xz_pm = st[at + sx - sz]; n.xz_mp = st[at - sx + sz]; }
+   if (mask & 6) { n.yz_pp = st[at + sy + sz]; n.yz_mm = st[at - sy - sz]; n.yz_pm = st[at + sy - sz]; n.yz_mp = st[at - sy + sz]; }
+   return n;
+}
+// L_a = ((u[c+o0] - u[c-o0]) + (u[c+o1] - u[c-o1])) + ((u[c+o2] - u[c-o2]) + (u[c+o3] - u[c-o3])), the offsets of include/pffdtd_hip.h: seven operations,
+// each rounded once in Real
+template <typename Real> static __device__ __forceinline__ Real lat_x(const LatNb<Real> &n) {
+#pragma clang fp contract(off)
+   return ((n.xy_pp - n.xy_mm) + (n.xz_pp - n.xz_mm)) + ((n.xy_pm - n.xy_mp) + (n.xz_pm - n.xz_mp));
+}
+template <typename Real> static __device__ __forceinline__ Real lat_y(const LatNb<Real> &n) {
+#pragma clang fp contract(off)
+   return ((n.xy_pp - n.xy_mm) + (n.yz_pp - n.yz_mm)) + ((n.xy_mp - n.xy_pm) + (n.yz_pm - n.yz_mp));
+}
+template <typename Real> static __device__ __forceinline__ Real lat_z(const LatNb<Real> &n) {
+#pragma clang fp contract(off)
+   return ((n.yz_pp - n.yz_mm) + (n.xz_pp - n.xz_mm)) + ((n.yz_mp - n.yz_pm) + (n.xz_mp - n.xz_pm));
+}
+
+// The lattice differences of an FCC grid (comp 4 / 5 / 6), ALL the requested ones in one launch: grid and arguments as k_region_cut, mask as
+// lat_load's, ox / oy / oz: the ring slot of the difference along file x / y / z (read only where its mask bit is set).  The tiled form keeps one
+// 32 x 33 tile of Real per REQUESTED component in dynamic LDS (popcount(mask) * 32 * 33 * sizeof(Real) bytes, in the order x, y, z): the pair
+// differences and their sums are formed in registers before anything goes to LDS, as k_region_diff.
+template <typename Real, bool EXCH>
+static __global__ void __launch_bounds__(256) k_region_lat(const Real *__restrict__ st, Real *__restrict__ ox, Real *__restrict__ oy, Real *__restrict__ oz, RegionPiece q, int64_t Ny,
+                                                           int64_t P, int tiled, int bz_log2, int mask) {
+#pragma clang fp contract(off)
+   const int64_t sx = EXCH ? 1 : Ny * P, sy = P, sz = EXCH ? Ny * P : 1;
+   if (EXCH && tiled) {
+      extern __shared__ __align__(16) unsigned char lat_lds[];
+      Real(*tile)[32][33] = reinterpret_cast<Real(*)[32][33]>(lat_lds);
+      const int tx = 0, ty = mask & 1, tz = (mask & 1) + ((mask >> 1) & 1); // a component's tile
+      const int a = threadIdx.x & 31, b = threadIdx.x >> 5; // 32 x 8
+      const int64_t j = blockIdx.y, kt = (int64_t)blockIdx.x * 32, it = (int64_t)blockIdx.z * 32;
+      const int64_t fy = q.lo1 + j * q.s1;
+#pragma unroll
+      for (int r = 0; r < 4; r++) { // lanes along file x: the storage's unit-stride axis
+         const int64_t i = it + a, k = kt + b + 8 * r;
+         if (i < q.n0 && k < q.n2) {
+            const LatNb<Real> n = lat_load(st, ((q.lo2 + k * q.s2) * Ny + fy) * P + q.lo0 + i * q.s0, sx, sy, sz, mask);
+            if (mask & 1) tile[tx][b + 8 * r][a] = lat_x(n);
+            if (mask & 2) tile[ty][b + 8 * r][a] = lat_y(n);
+            if (mask & 4) tile[tz][b + 8 * r][a] = lat_z(n);
+         }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int r = 0; r < 4; r++) { // lanes along file z: the slot's
+         const int64_t i = it + b + 8 * r, k = kt + a;
+         if (i < q.n0 && k < q.n2) {
+            const int64_t o = (i * q.n1 + j) * q.n2 + k;
+            if (mask & 1) ox[o] = tile[tx][a][b + 8 * r];
+            if (mask & 2) oy[o] = tile[ty][a][b + 8 * r];
+            if (mask & 4) oz[o] = tile[tz][a][b + 8 * r];
+         }
+      }
+      return;
+   }
+   const int bz = 1 << bz_log2;
+   const int64_t k = (int64_t)blockIdx.x * bz + (threadIdx.x & (bz - 1));
+   const int64_t j = (int64_t)blockIdx.y * (256 >> bz_log2) + (threadIdx.x >> bz_log2);
+   const int64_t i = blockIdx.z;
+   if (k >= q.n2 || j >= q.n1) return;
+   const int64_t fx = q.lo0 + i * q.s0, fy = q.lo1 + j * q.s1, fz = q.lo2 + k * q.s2;
+   const LatNb<Real> n = lat_load(st, EXCH ? (fz * Ny + fy) * P + fx : (fx * Ny + fy) * P + fz, sx, sy, sz, mask);
+   const int64_t o = (i * q.n1 + j) * q.n2 + k;
+   if (mask & 1) ox[o] = lat_x(n);
+   if (mask & 2) oy[o] = lat_y(n);
+   if (mask & 4) oz[o] = lat_z(n);
 }
 
 // grid: (cdiv(cdiv(cells, 2), 256), ncomp) blocks of 256 threads; npre >= 1.  ring, xpre: at the first of the NT samples; rcomp, xcomp, scomp: elements

@@ -421,7 +421,8 @@ class BandAccumulator:
 
 class VectorBandAccumulator:
     """Per cell of a region, on the device (pf_engine_vband_* / pf_multi_vband_*): the components `comp` (0: the cell of u^n, 1 / 2 / 3: its central
-    difference along file x / y / z) through their own sections pre_sos [ncomp, npre, 6], then per band through band_sos [nband, nsec, 6] (scipy's
+    difference along file x / y / z on a Cartesian grid, 4 / 5 / 6: the lattice difference along file x / y / z of an FCC grid -- the four pair
+    differences over the eight FCC neighbours at +-1 along the axis, in stored coordinates, ~ 8 h du/da) through their own sections pre_sos [ncomp, npre, 6], then per band through band_sos [nband, nsec, 6] (scipy's
     sos rows, a0 = 1; state per component); the products prod [nprod, 3] -- rows (i, j, mode), mode 1: the absolute value -- of two filtered
     components are summed into time bin `bin` at every add(bin).
     Made by HipEngine.vector_band_accumulator / HipMulti.vector_band_accumulator; it lives no longer than the object that made it."""
@@ -867,7 +868,7 @@ class HipEngine:
 
     def vector_band_accumulator(self, lo, hi, stride=(1, 1, 1), comp=(0,), pre_sos=None, band_sos=None, prod=((0, 0, 0),), nbin=1, depth=0):
         """Per cell of the region, on the device (pf_engine_vband_create): the components comp (0: the cell of u^n, 1 / 2 / 3: its central difference
-        along file x / y / z) through pre_sos [ncomp, npre, 6] and, per band, band_sos [nband, nsec, 6]; the products prod [nprod, 3] = (i, j, mode) of
+        along file x / y / z, 4 / 5 / 6: the lattice difference of an FCC grid along file x / y / z) through pre_sos [ncomp, npre, 6] and, per band, band_sos [nband, nsec, 6]; the products prod [nprod, 3] = (i, j, mode) of
         two filtered components summed into the time bin given to add(bin) -- a VectorBandAccumulator."""
         return VectorBandAccumulator(self, "pf_engine", lo, hi, stride, comp, pre_sos, band_sos, prod, nbin, depth)
 

@@ -52,8 +52,10 @@ Directional band maps (pffdtd_amd/directional.py): `--dir-planes` / `--dir-box` 
 every chosen axis) name regions whose cells' pressure and pressure gradient along `--dir-axes y[,x,z]` (file axes; default y) are filtered into the
 octave bands `--dir-bands 125,250,500`, multiplied and summed ON THE DEVICE into time bins of `--dir-bin-ms 5` milliseconds, at EVERY step from
 `--dir-first N` (default 0) on, and written to `--dir-file FILE` (default sim_directional.h5 beside sim_outs.h5) at every checkpoint and at the end:
-what the lateral energy fractions LF, LFC and the intensity maps are functions of (directional.parameters).  Cartesian grids only.  Everything else
-as the decay arguments: the run is cut at every step from N on, a chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (one line says
+what the lateral energy fractions LF, LFC and the intensity maps are functions of (directional.parameters).  `--dir-stencil axis` (default) is the
+central difference along the axis, on Cartesian grids only; `--dir-stencil lattice` is the FCC lattice's own difference over the eight neighbours at
++-1 along the axis, on FCC folders only (fcc_flag 1 / 2; regions one cell clear of ALL faces; on a folded grid the file carries every cell's
+physical y index and S has the room's sign).  The wrong stencil for the folder's grid is refused by name.  Everything else as the decay arguments: the run is cut at every step from N on, a chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (one line says
 so), `--resume` restores sums and filter state from the file, and without these arguments nothing about a run changes.
 
 Decimated field recordings (pffdtd_amd/recordings.py): `--rec-planes` / `--rec-box` (the syntax of the field arguments) name regions whose cells'
@@ -204,9 +206,11 @@ def _field_directional(a, sd, m, resume_at):
     try:
         regions = [r for spec in a.dir_planes for r in fields.parse_planes(spec, N)] + [fields.parse_box(spec, N) for spec in a.dir_box]
         path = a.dir_file if a.dir_file else Path(a.data_dir) / "sim_directional.h5"
-        fv = dir_mod.FieldDirectional(path, sd, regions, decay_mod.parse_bands(a.dir_bands), dir_mod.parse_axes(a.dir_axes), a.dir_bin_ms, a.dir_first, resume_at=resume_at)
+        fv = dir_mod.FieldDirectional(path, sd, regions, decay_mod.parse_bands(a.dir_bands), dir_mod.parse_axes(a.dir_axes), a.dir_bin_ms, a.dir_first, resume_at=resume_at,
+                                      stencil=a.dir_stencil)
     except ValueError as e:
-        raise SystemExit(str(e).replace("--field-", "--dir-").replace("--decay-", "--dir-"))
+        raise SystemExit(str(e).replace("--field-", "--dir-").replace("--decay-", "--dir-").replace('stencil="lattice"', "--dir-stencil lattice")
+                         .replace('stencil="axis"', "--dir-stencil axis"))
     try:
         fv.attach(m)
     except engine.PfError as e:  # (a region on a face along a chosen axis, an FCC grid: the engine names it)
@@ -345,7 +349,7 @@ def _run_chain_checkpointed(a, sd, m):
         fd.close()
     if fv:
         fv.write()
-        print(f"--field directional maps of {fv.count} samples in {fv.bands.size} bands along {','.join('xyz'[k - 1] for k in fv.axes)}, bins of {fv.bin_steps} steps: {fv.path}", flush=True)
+        print(f"--field directional maps of {fv.count} samples in {fv.bands.size} bands along {','.join('xyz'[k - 1] for k in fv.axes)}{' (lattice differences)' if fv.stencil == 'lattice' else ''}, bins of {fv.bin_steps} steps: {fv.path}", flush=True)
         fv.close()
     if fr:
         fr.write()
@@ -497,6 +501,7 @@ def main():
     p.add_argument("--dir-box", action="append", default=[], metavar="x0:x1:sx,y0:y1:sy,z0:z1:sz", help="... of this strided box")
     p.add_argument("--dir-bands", default="", metavar="F1,F2,...", help="... in the octave bands around these centre frequencies in Hz")
     p.add_argument("--dir-axes", default="", metavar="y[,x,z]", help="... with the gradient along these file axes (default y)")
+    p.add_argument("--dir-stencil", default="", choices=["", "axis", "lattice"], metavar="axis|lattice", help="... as the central difference along the axis (axis, the default: Cartesian grids) or the FCC lattice's difference (lattice: FCC folders)")
     p.add_argument("--dir-bin-ms", type=float, default=5.0, metavar="MS", help="... in time bins of MS milliseconds (default 5)")
     p.add_argument("--dir-first", type=int, default=0, metavar="N", help="... at every step from N on (default 0)")
     p.add_argument("--dir-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_directional.h5 in the data folder)")
@@ -506,8 +511,9 @@ def main():
     a.directional = bool(a.dir_planes or a.dir_box)
     if a.directional != bool(a.dir_bands) or a.dir_bin_ms <= 0 or a.dir_first < 0:
         p.error("--dir-planes / --dir-box need --dir-bands (and the other way round); --dir-bin-ms: positive, --dir-first: not negative")
-    if (a.dir_first or a.dir_file or a.dir_axes or a.dir_bin_ms != 5.0) and not a.directional:
-        p.error("--dir-axes / --dir-bin-ms / --dir-first / --dir-file need --dir-planes or --dir-box")
+    if (a.dir_first or a.dir_file or a.dir_axes or a.dir_stencil or a.dir_bin_ms != 5.0) and not a.directional:
+        p.error("--dir-axes / --dir-stencil / --dir-bin-ms / --dir-first / --dir-file need --dir-planes or --dir-box")
+    a.dir_stencil = a.dir_stencil or "axis"
     if a.directional and not a.dir_axes:
         a.dir_axes = "y"
     a.decay = bool(a.decay_planes or a.decay_box)
