@@ -550,6 +550,45 @@ int     pf_multi_decim_read      (pf_multi *m, pf_decim *a, double *frames, int6
 int     pf_multi_decim_get_state (pf_multi *m, pf_decim *a, double *acc, double *state);
 int     pf_multi_decim_set_state (pf_multi *m, pf_decim *a, const double *acc, const double *state, int64_t count);
 int     pf_multi_decim_destroy   (pf_multi *m, pf_decim *a);
+/* ---- vector decimating recorders: per cell, up to four COMPONENTS of the field, each low-pass filtered and decimated -- a B-format impulse response ----
+ * A pf_decim keeps the pressure only: an omnidirectional microphone at every cell.  A vector decimating recorder keeps the time signal of the
+ * pressure gradient beside it (pffdtd_amd/recordings.py: W and a figure-of-eight channel per axis).  It belongs to one engine (or chain) and holds a
+ * region, ncomp (1 .. 4) components comp[], npre (0 .. 8) sections PER COMPONENT pre_sos[ncomp][npre][5], ONE FIR taps[ntap] shared by the
+ * components, and factor, cap and depth with pf_decim's meaning and limits (P = ceil(ntap / factor) <= 128; depth 0 = the default).  No
+ * counterpart in the reference.
+ *   - comp[] means what it means to pf_engine_vband_create: 0 the cell, 1 / 2 / 3 the central difference along file x / y / z on fcc_flag == 0,
+ *     4 / 5 / 6 the lattice difference on fcc_flag != 0, each formed in the field's own precision in exactly pf_vbandacc's association.  The
+ *     refusals are pf_vbandacc's, by name: a repeated component, the wrong kind for the grid, a region not one cell clear of the faces the
+ *     component needs.
+ *   - add takes u^n at the same moment and under the same ghost-shell and fold-row rules as pf_engine_vband_add.  Component k's sample
+ *     x_k = (double)component runs through pre_sos[k] by pf_bandacc's three lines and then through the FIR by pf_decim's lines, in ARRIVAL order
+ *     (acc = acc + h[tap] * x, the product and the sum each rounded to double, no fused multiply-add).  The slot and tap arithmetic does not depend
+ *     on the component.  Ring depth, cap and the slot group size never change a bit; a numpy loop per component gives the same bits.
+ *   - read gives frames[nread][ncomp][cells]; get_state acc[ncomp][P][cells] and state[ncomp][npre][2][cells] (may be NULL); set_state (NULL:
+ *     zeros), pf_vdecim_count, pf_vdecim_pending, a full cap refused with PF_ERR_STATE before the cut with nothing changed, PF_ERR_ARG and
+ *     PF_ERR_STATE: all as pf_decim.
+ *   - Device memory, all of it the engine's: ncomp * (P + cap + 2 npre) rows of doubles (rows padded to an even cell count), ncomp * depth * cells
+ *     Reals, and -- npre > 0 -- ncomp * depth rows of doubles.  A 512 x 512 plane with 4 components and P = 98 holds 0.8 GB of acc alone; a create
+ *     that does not fit fails with the allocator's error and leaves nothing behind.
+ *   - A chain: one per slab over its part, as pf_vbandacc: a difference across the cut reads the slab's ghost plane, and the one-cell rule is checked
+ *     against the scene's faces; add is all or nothing, and a full cap and the size of a read are decided before any slab is asked, as pf_decim. */
+typedef struct pf_vdecim pf_vdecim;
+int     pf_engine_vdecim_create   (pf_engine *e, const pf_region *r, int32_t ncomp, const int32_t *comp, int32_t npre, const double *pre_sos, int32_t ntap, const double *taps,
+                                   int32_t factor, int64_t cap, int32_t depth, pf_vdecim **out);
+int     pf_engine_vdecim_add      (pf_engine *e, pf_vdecim *a);
+int     pf_engine_vdecim_read     (pf_engine *e, pf_vdecim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread);
+int     pf_engine_vdecim_get_state(pf_engine *e, pf_vdecim *a, double *acc, double *state);
+int     pf_engine_vdecim_set_state(pf_engine *e, pf_vdecim *a, const double *acc, const double *state, int64_t count);
+int64_t pf_vdecim_count           (const pf_vdecim *a);
+int64_t pf_vdecim_pending         (const pf_vdecim *a);
+int     pf_engine_vdecim_destroy  (pf_engine *e, pf_vdecim *a);
+int     pf_multi_vdecim_create    (pf_multi *m, const pf_region *r, int32_t ncomp, const int32_t *comp, int32_t npre, const double *pre_sos, int32_t ntap, const double *taps,
+                                   int32_t factor, int64_t cap, int32_t depth, pf_vdecim **out);
+int     pf_multi_vdecim_add       (pf_multi *m, pf_vdecim *a);
+int     pf_multi_vdecim_read      (pf_multi *m, pf_vdecim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread);
+int     pf_multi_vdecim_get_state (pf_multi *m, pf_vdecim *a, double *acc, double *state);
+int     pf_multi_vdecim_set_state (pf_multi *m, pf_vdecim *a, const double *acc, const double *state, int64_t count);
+int     pf_multi_vdecim_destroy   (pf_multi *m, pf_vdecim *a);
 int  pf_engine_timing(pf_engine *e, pf_timing *t, int32_t reset);
 /* switch the per-launch HIP events of pf_opts.timing on / off between runs (a host times its headline region without them
  * and collects kernel durations in a region of its own) */

@@ -77,6 +77,20 @@ struct pf_decim {
 int pf__engine_decim_read_x(pf_engine *e, pf_decim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride);
 int pf__engine_decim_get_state_x(pf_engine *e, pf_decim *a, double *acc, double *state, int64_t pitch, int64_t rowstride);
 int pf__engine_decim_set_state_x(pf_engine *e, pf_decim *a, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count);
+// A vector decimating recorder's handle (pffdtd_hip.h: pf_vdecim): as pf_decim; frames are [ncomp][cells], acc [ncomp][P][cells].
+struct pf_vdecim {
+   pf_engine *eng = nullptr;
+   void *impl = nullptr;
+   pf_multi *chain = nullptr;
+   std::vector<pf_vdecim *> part;
+   pf_region region{};
+   int64_t rc[3] = {0, 0, 0}, cells = 0;
+   int64_t factor = 1, cap = 0, count = 0, rd = 0;
+};
+// pf_engine_vdecim_read / _get_state / _set_state with the caller's region rows `pitch` and frame / acc / state rows `rowstride` doubles apart (0: dense)
+int pf__engine_vdecim_read_x(pf_engine *e, pf_vdecim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride);
+int pf__engine_vdecim_get_state_x(pf_engine *e, pf_vdecim *a, double *acc, double *state, int64_t pitch, int64_t rowstride);
+int pf__engine_vdecim_set_state_x(pf_engine *e, pf_vdecim *a, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count);
 int pf__engine_between_runs(pf_engine *e); // 1: not inside a split-phase step or pass (what pf_engine_accum_add needs)
 enum : int {
    PF_DBG_BRANCH_SELECTS = 0x1,       // three-step wall regions: fd_regs' select form (a branch count per lane) even where every material has the same count

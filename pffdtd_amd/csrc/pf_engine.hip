@@ -54,6 +54,7 @@ struct pf_engine {
    std::vector<pf_bandacc *> bands; // ... and of its band accumulators
    std::vector<pf_vbandacc *> vbands; // ... and of its vector band accumulators
    std::vector<pf_decim *> decims; // ... and of its decimating recorders
+   std::vector<pf_vdecim *> vdecims; // ... and of its vector decimating recorders
 };
 pfeng::EngineBase *pf__new_engine_f64(const pf_simdata *sd, const pf_opts_x *o, int *rc); // pf_engine_f64.hip
 
@@ -127,7 +128,7 @@ int pf__engine_create_x(const pf_simdata *sd, const pf_opts_x *opts, pf_engine *
       return set_err(PF_ERR_ARG, "real_bytes must be 4 or 8 (got %d)", sd->real_bytes);
    }
    if (rc) { std::string keep = g_err; delete impl; g_err = keep; return rc; }
-   *out = new pf_engine{impl, {}, {}, {}, {}};
+   *out = new pf_engine{impl, {}, {}, {}, {}, {}};
    return PF_OK;
 }
 
@@ -214,6 +215,25 @@ int pf__engine_decim_set_state_x(pf_engine *e, pf_decim *a, const double *acc, c
    const int rc = decim_mine(e, a, "pf_engine_decim_set_state");
    return rc ? rc : e->impl->decim_set_state(a->impl, acc, state, pitch, rowstride, count);
 }
+// vector decimating recorders: the same rule
+static int vdecim_mine(pf_engine *e, const pf_vdecim *a, const char *what) {
+   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
+   if (!a) return set_err(PF_ERR_ARG, "%s: null pf_vdecim", what);
+   if (a->eng != e) return set_err(PF_ERR_ARG, "%s: the pf_vdecim belongs to another engine%s", what, a->chain ? " (it is a chain's: pf_multi_vdecim_*)" : "");
+   return PF_OK;
+}
+int pf__engine_vdecim_read_x(pf_engine *e, pf_vdecim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride) {
+   const int rc = vdecim_mine(e, a, "pf_engine_vdecim_read");
+   return rc ? rc : e->impl->vdecim_read(a->impl, frames, max_frames, first, nread, pitch, rowstride);
+}
+int pf__engine_vdecim_get_state_x(pf_engine *e, pf_vdecim *a, double *acc, double *state, int64_t pitch, int64_t rowstride) {
+   const int rc = vdecim_mine(e, a, "pf_engine_vdecim_get_state");
+   return rc ? rc : e->impl->vdecim_get_state(a->impl, acc, state, pitch, rowstride);
+}
+int pf__engine_vdecim_set_state_x(pf_engine *e, pf_vdecim *a, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count) {
+   const int rc = vdecim_mine(e, a, "pf_engine_vdecim_set_state");
+   return rc ? rc : e->impl->vdecim_set_state(a->impl, acc, state, pitch, rowstride, count);
+}
 int pf__engine_between_runs(pf_engine *e) { return e && e->impl && e->impl->between_runs() ? 1 : 0; }
 
 extern "C" {
@@ -224,6 +244,7 @@ void pf_engine_destroy(pf_engine *e) {
    for (pf_bandacc *a : e->bands) delete a;
    for (pf_vbandacc *a : e->vbands) delete a;
    for (pf_decim *a : e->decims) delete a;
+   for (pf_vdecim *a : e->vdecims) delete a;
    delete e->impl;
    delete e;
 }
@@ -366,6 +387,50 @@ int pf_engine_decim_destroy(pf_engine *e, pf_decim *a) {
    int rc = decim_mine(e, a, "pf_engine_decim_destroy");
    if (rc || (rc = e->impl->decim_destroy(a->impl))) return rc;
    e->decims.erase(std::find(e->decims.begin(), e->decims.end(), a));
+   delete a;
+   return PF_OK;
+}
+
+int pf_engine_vdecim_create(pf_engine *e, const pf_region *r, int32_t ncomp, const int32_t *comp, int32_t npre, const double *pre_sos, int32_t ntap, const double *taps,
+                            int32_t factor, int64_t cap, int32_t depth, pf_vdecim **out) {
+   const char *what = "pf_engine_vdecim_create";
+   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
+   if (!out) return set_err(PF_ERR_ARG, "%s: null out", what);
+   *out = nullptr;
+   void *impl = nullptr;
+   const int rc = e->impl->vdecim_create(r, ncomp, comp, npre, pre_sos, ntap, taps, factor, cap, depth, &impl);
+   if (rc) return rc;
+   pf_vdecim *a = new pf_vdecim();
+   a->eng = e; a->impl = impl; a->region = *r; a->factor = factor; a->cap = cap;
+   a->cells = pf_cut::region_counts(r, a->rc);
+   e->vdecims.push_back(a);
+   *out = a;
+   return PF_OK;
+}
+int pf_engine_vdecim_add(pf_engine *e, pf_vdecim *a) {
+   const int rc = vdecim_mine(e, a, "pf_engine_vdecim_add");
+   return rc ? rc : e->impl->vdecim_add(a->impl);
+}
+int pf_engine_vdecim_read(pf_engine *e, pf_vdecim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread) {
+   return pf__engine_vdecim_read_x(e, a, frames, max_frames, first, nread, 0, 0);
+}
+int pf_engine_vdecim_get_state(pf_engine *e, pf_vdecim *a, double *acc, double *state) { return pf__engine_vdecim_get_state_x(e, a, acc, state, 0, 0); }
+int pf_engine_vdecim_set_state(pf_engine *e, pf_vdecim *a, const double *acc, const double *state, int64_t count) {
+   return pf__engine_vdecim_set_state_x(e, a, acc, state, 0, 0, count);
+}
+// (an engine's handle asks the engine's object; a chain's keeps the two numbers itself)
+static void vdecim_numbers(const pf_vdecim *a, int64_t *count, int64_t *pending) {
+   *count = *pending = -1;
+   if (!a) return;
+   if (a->chain) { *count = a->count; *pending = (a->count + a->factor - 1) / a->factor - a->rd; }
+   else if (a->eng && a->eng->impl) a->eng->impl->vdecim_info(a->impl, count, pending);
+}
+int64_t pf_vdecim_count(const pf_vdecim *a) { int64_t c, p; vdecim_numbers(a, &c, &p); return c; }
+int64_t pf_vdecim_pending(const pf_vdecim *a) { int64_t c, p; vdecim_numbers(a, &c, &p); return p; }
+int pf_engine_vdecim_destroy(pf_engine *e, pf_vdecim *a) {
+   int rc = vdecim_mine(e, a, "pf_engine_vdecim_destroy");
+   if (rc || (rc = e->impl->vdecim_destroy(a->impl))) return rc;
+   e->vdecims.erase(std::find(e->vdecims.begin(), e->vdecims.end(), a));
    delete a;
    return PF_OK;
 }

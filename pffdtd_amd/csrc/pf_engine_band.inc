@@ -117,9 +117,10 @@
       return PF_OK;
    }
 
+   // (A: any of the region observers -- Band, VBand, Decim, VDecim --, for its c, cells and cstride.)
    // `nrows` device rows, cstride doubles apart, <-> the caller's: dense (pitch, rowstride = 0) or -- a slab's part of a chain's array -- the region's
    // rows `pitch` and the device rows `rowstride` doubles apart
-   int band_rows(const char *what, Band *a, double *dev, int64_t nrows, double *host, int64_t pitch, int64_t rowstride, bool out) {
+   template <typename A> int band_rows(const char *what, A *a, double *dev, int64_t nrows, double *host, int64_t pitch, int64_t rowstride, bool out) {
       if (pitch <= 0) pitch = a->c[2];
       if (rowstride <= 0) rowstride = a->cells;
       if (pitch < a->c[2]) return set_err(PF_ERR_ARG, "%s: pitch %ld < the region's %ld cells along z", what, (long)pitch, (long)a->c[2]);

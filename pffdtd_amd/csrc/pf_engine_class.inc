@@ -33,6 +33,7 @@
 #include "pf_band.h"
 #include "pf_vband.h"
 #include "pf_decim.h"
+#include "pf_vdecim.h"
 
 // shared between the two units (defined in pf_engine.hip)
 extern "C" void pf__set_error(const char *msg);
@@ -81,6 +82,14 @@ struct EngineBase {
    virtual int decim_set_state(void *a, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count) = 0;
    virtual int decim_info(void *a, int64_t *count, int64_t *pending) const = 0;
    virtual int decim_destroy(void *a) = 0;
+   virtual int vdecim_create(const pf_region *r, int ncomp, const int32_t *comp, int npre, const double *pre_sos, int ntap, const double *taps, int factor, int64_t cap, int depth,
+                             void **out) = 0; // vector decimating recorders (pf_engine_vdecim.inc)
+   virtual int vdecim_add(void *a) = 0;
+   virtual int vdecim_read(void *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride) = 0;
+   virtual int vdecim_get_state(void *a, double *acc, double *state, int64_t pitch, int64_t rowstride) = 0;
+   virtual int vdecim_set_state(void *a, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count) = 0;
+   virtual int vdecim_info(void *a, int64_t *count, int64_t *pending) const = 0;
+   virtual int vdecim_destroy(void *a) = 0;
    virtual bool between_runs() const = 0; // not inside a split-phase step or pass
    virtual int save_state(pf_state *st) = 0;
    virtual int load_state(const pf_state *st) = 0;
@@ -1105,6 +1114,7 @@ template <typename Real> struct Engine : EngineBase {
 #include "pf_engine_band.inc"
 #include "pf_engine_vband.inc"
 #include "pf_engine_decim.inc"
+#include "pf_engine_vdecim.inc"
    void *stream(int which) override { return which == 1 ? (void *)s_edge : (void *)s_main; }
 };
 

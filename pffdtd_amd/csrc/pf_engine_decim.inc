@@ -140,31 +140,6 @@
       return PF_OK;
    }
 
-   // `nrows` device rows, cstride doubles apart, <-> the caller's (band_rows of pf_engine_band.inc with this object's counts)
-   int decim_rows(const char *what, Decim *a, double *dev, int64_t nrows, double *host, int64_t pitch, int64_t rowstride, bool out) {
-      if (pitch <= 0) pitch = a->c[2];
-      if (rowstride <= 0) rowstride = a->cells;
-      if (pitch < a->c[2]) return set_err(PF_ERR_ARG, "%s: pitch %ld < the region's %ld cells along z", what, (long)pitch, (long)a->c[2]);
-      if (nrows == 0) return PF_OK;
-      const size_t row = (size_t)a->cells * sizeof(double);
-      if (pitch == a->c[2]) { // a row's cells are contiguous in the caller's array
-         if (out) HIPCHK(hipMemcpy2D(host, (size_t)rowstride * sizeof(double), dev, (size_t)a->cstride * sizeof(double), row, (size_t)nrows, hipMemcpyDeviceToHost));
-         else HIPCHK(hipMemcpy2D(dev, (size_t)a->cstride * sizeof(double), host, (size_t)rowstride * sizeof(double), row, (size_t)nrows, hipMemcpyHostToDevice));
-         return PF_OK;
-      }
-      std::vector<double> tmp;
-      try { tmp.resize((size_t)a->cells); } catch (const std::bad_alloc &) { return set_err(PF_ERR_ARG, "%s: no host memory for a row of the region", what); }
-      for (int64_t m = 0; m < nrows; m++) {
-         if (out) HIPCHK(hipMemcpy(tmp.data(), dev + m * a->cstride, row, hipMemcpyDeviceToHost));
-         for (int64_t rw = 0; rw < a->c[0] * a->c[1]; rw++) {
-            double *hp = host + m * rowstride + rw * pitch, *tp = tmp.data() + rw * a->c[2];
-            if (out) memcpy(hp, tp, (size_t)a->c[2] * sizeof(double)); else memcpy(tp, hp, (size_t)a->c[2] * sizeof(double));
-         }
-         if (!out) HIPCHK(hipMemcpy(dev + m * a->cstride, tmp.data(), row, hipMemcpyHostToDevice));
-      }
-      return PF_OK;
-   }
-
    // the oldest min(max_frames, pending) frames in order, [nread][cells]; they are marked read
    int decim_read(void *h, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride) override {
       const char *what = "pf_engine_decim_read";
@@ -176,8 +151,8 @@
       if (rc || (rc = decim_fold(a))) return rc;
       const int64_t n = std::min(max_frames, a->pending()), row0 = a->rd % a->cap, n1 = std::min(n, a->cap - row0); // rows row0 .., then the ring of frames wraps
       if (rowstride <= 0) rowstride = a->cells;
-      if ((rc = decim_rows(what, a, a->frames + row0 * a->cstride, n1, frames, pitch, rowstride, true))) return rc;
-      if ((rc = decim_rows(what, a, a->frames, n - n1, frames + n1 * rowstride, pitch, rowstride, true))) return rc;
+      if ((rc = band_rows(what, a, a->frames + row0 * a->cstride, n1, frames, pitch, rowstride, true))) return rc;
+      if ((rc = band_rows(what, a, a->frames, n - n1, frames + n1 * rowstride, pitch, rowstride, true))) return rc;
       *first = a->rd;
       *nread = n;
       a->rd += n;
@@ -191,8 +166,8 @@
       Decim *a;
       int rc = decim_enter(what, h, &a);
       if (rc || (rc = decim_fold(a))) return rc;
-      if ((rc = decim_rows(what, a, a->acc, a->P, acc, pitch, rowstride, true))) return rc;
-      return state ? decim_rows(what, a, a->st, (int64_t)a->npre * 2, state, pitch, rowstride, true) : PF_OK;
+      if ((rc = band_rows(what, a, a->acc, a->P, acc, pitch, rowstride, true))) return rc;
+      return state ? band_rows(what, a, a->st, (int64_t)a->npre * 2, state, pitch, rowstride, true) : PF_OK;
    }
 
    // null: zeros.  Pending samples and unread frames are dropped; the next frame to complete is ceil(count / D)
@@ -203,9 +178,9 @@
       int rc = decim_enter(what, h, &a);
       if (rc) return rc;
       a->fill = 0;
-      if (acc) { if ((rc = decim_rows(what, a, a->acc, a->P, const_cast<double *>(acc), pitch, rowstride, false))) return rc; }
+      if (acc) { if ((rc = band_rows(what, a, a->acc, a->P, const_cast<double *>(acc), pitch, rowstride, false))) return rc; }
       else HIPCHK(hipMemset(a->acc, 0, (size_t)a->P * a->cstride * sizeof(double)));
-      if (state) { if ((rc = decim_rows(what, a, a->st, (int64_t)a->npre * 2, const_cast<double *>(state), pitch, rowstride, false))) return rc; }
+      if (state) { if ((rc = band_rows(what, a, a->st, (int64_t)a->npre * 2, const_cast<double *>(state), pitch, rowstride, false))) return rc; }
       else if (a->npre) HIPCHK(hipMemset(a->st, 0, (size_t)a->npre * 2 * a->cstride * sizeof(double)));
       HIPCHK(hipDeviceSynchronize());
       a->count = count;

@@ -253,31 +253,6 @@
       return PF_OK;
    }
 
-   // `nrows` device rows, cstride doubles apart, <-> the caller's (band_rows of pf_engine_band.inc with this object's counts)
-   int vband_rows(const char *what, VBand *a, double *dev, int64_t nrows, double *host, int64_t pitch, int64_t rowstride, bool out) {
-      if (pitch <= 0) pitch = a->c[2];
-      if (rowstride <= 0) rowstride = a->cells;
-      if (pitch < a->c[2]) return set_err(PF_ERR_ARG, "%s: pitch %ld < the region's %ld cells along z", what, (long)pitch, (long)a->c[2]);
-      if (nrows == 0) return PF_OK;
-      const size_t row = (size_t)a->cells * sizeof(double);
-      if (pitch == a->c[2]) { // a row's cells are contiguous in the caller's array
-         if (out) HIPCHK(hipMemcpy2D(host, (size_t)rowstride * sizeof(double), dev, (size_t)a->cstride * sizeof(double), row, (size_t)nrows, hipMemcpyDeviceToHost));
-         else HIPCHK(hipMemcpy2D(dev, (size_t)a->cstride * sizeof(double), host, (size_t)rowstride * sizeof(double), row, (size_t)nrows, hipMemcpyHostToDevice));
-         return PF_OK;
-      }
-      std::vector<double> tmp;
-      try { tmp.resize((size_t)a->cells); } catch (const std::bad_alloc &) { return set_err(PF_ERR_ARG, "%s: no host memory for a row of the region", what); }
-      for (int64_t m = 0; m < nrows; m++) {
-         if (out) HIPCHK(hipMemcpy(tmp.data(), dev + m * a->cstride, row, hipMemcpyDeviceToHost));
-         for (int64_t rw = 0; rw < a->c[0] * a->c[1]; rw++) {
-            double *hp = host + m * rowstride + rw * pitch, *tp = tmp.data() + rw * a->c[2];
-            if (out) memcpy(hp, tp, (size_t)a->c[2] * sizeof(double)); else memcpy(tp, hp, (size_t)a->c[2] * sizeof(double));
-         }
-         if (!out) HIPCHK(hipMemcpy(dev + m * a->cstride, tmp.data(), row, hipMemcpyHostToDevice));
-      }
-      return PF_OK;
-   }
-
    // sums [nprod][nband][nbin][cells], state [ncomp][npre + nband*nsec][2][cells] (may be null)
    int vband_get(void *h, double *sums, double *state, int64_t pitch, int64_t rowstride) override {
       const char *what = "pf_engine_vband_get";
@@ -285,8 +260,8 @@
       VBand *a;
       int rc = vband_enter(what, h, &a);
       if (rc || (rc = vband_fold(a))) return rc;
-      if ((rc = vband_rows(what, a, a->S, a->erows(), sums, pitch, rowstride, true))) return rc;
-      return state ? vband_rows(what, a, a->st, a->srows(), state, pitch, rowstride, true) : PF_OK;
+      if ((rc = band_rows(what, a, a->S, a->erows(), sums, pitch, rowstride, true))) return rc;
+      return state ? band_rows(what, a, a->st, a->srows(), state, pitch, rowstride, true) : PF_OK;
    }
 
    // null: zeros.  Pending samples are dropped.
@@ -296,9 +271,9 @@
       int rc = vband_enter(what, h, &a);
       if (rc) return rc;
       a->fill = 0;
-      if (sums) { if ((rc = vband_rows(what, a, a->S, a->erows(), const_cast<double *>(sums), pitch, rowstride, false))) return rc; }
+      if (sums) { if ((rc = band_rows(what, a, a->S, a->erows(), const_cast<double *>(sums), pitch, rowstride, false))) return rc; }
       else HIPCHK(hipMemset(a->S, 0, (size_t)a->erows() * a->cstride * sizeof(double)));
-      if (state) { if ((rc = vband_rows(what, a, a->st, a->srows(), const_cast<double *>(state), pitch, rowstride, false))) return rc; }
+      if (state) { if ((rc = band_rows(what, a, a->st, a->srows(), const_cast<double *>(state), pitch, rowstride, false))) return rc; }
       else if (a->srows()) HIPCHK(hipMemset(a->st, 0, (size_t)a->srows() * a->cstride * sizeof(double)));
       HIPCHK(hipDeviceSynchronize());
       return PF_OK;

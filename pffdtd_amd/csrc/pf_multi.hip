@@ -628,6 +628,13 @@ void decim_add_slab(Shared &S, int g, pf_decim *a) {
    ECHK(g, pf_engine_decim_add(S.eng[g], a->part[g]));
 }
 
+// ... and of a vector decimating recorder
+void vdecim_add_slab(Shared &S, int g, pf_vdecim *a) {
+   if (S.err.load() || !S.eng[g] || !a->part[g]) return;
+   MCHK(g, hipSetDevice(S.dev[g]));
+   ECHK(g, pf_engine_vdecim_add(S.eng[g], a->part[g]));
+}
+
 void finish_slab(Shared &S, int g) {
    if (!S.eng[g]) return;
    hipSetDevice(S.dev[g]);
@@ -711,7 +718,7 @@ struct pf_multi {
    std::mutex mu;
    std::condition_variable cv_cmd, cv_done;
    int64_t cmd_seq = 0, cmd_n0 = 0, cmd_ns = 0;
-   int cmd_kind = 0;                 // 1 run, 2 quit, 3 save the state, 4 load it, 5 cut a region of a field, 6 add a sample to a field accumulator, 7 to a band accumulator, 8 to a vector band accumulator, 9 to a decimating recorder
+   int cmd_kind = 0;                 // 1 run, 2 quit, 3 save the state, 4 load it, 5 cut a region of a field, 6 add a sample to a field accumulator, 7 to a band accumulator, 8 to a vector band accumulator, 9 to a decimating recorder, 10 to a vector decimating recorder
    pf_accum *cmd_accum = nullptr;    // 6: the chain's accumulator and the sample's weights
    const double *cmd_w = nullptr;
    pf_bandacc *cmd_band = nullptr;   // 7: the chain's band accumulator and the sample's bin
@@ -721,6 +728,8 @@ struct pf_multi {
    std::vector<pf_vbandacc *> vbands; // the chain's vector band accumulators still alive
    pf_decim *cmd_decim = nullptr;    // 9: the chain's decimating recorder
    std::vector<pf_decim *> decims;   // the chain's decimating recorders still alive
+   pf_vdecim *cmd_vdecim = nullptr;  // 10: the chain's vector decimating recorder
+   std::vector<pf_vdecim *> vdecims; // the chain's vector decimating recorders still alive
    std::vector<pf_accum *> accums;   // the chain's field accumulators still alive (pf_multi_destroy frees those left)
    pf_state *cmd_state = nullptr;    // ... from / into these global arrays
    pf_region cmd_region{};           // 5: the region (checked), its counts, the field, the caller's dense array
@@ -760,6 +769,7 @@ void worker(pf_multi *m, int g) {
       else if (kind == 7) band_add_slab(S, g, m->cmd_band, m->cmd_bin);
       else if (kind == 8) vband_add_slab(S, g, m->cmd_vband, m->cmd_bin);
       else if (kind == 9) decim_add_slab(S, g, m->cmd_decim);
+      else if (kind == 10) vdecim_add_slab(S, g, m->cmd_vdecim);
       else run_slabs(S, g, g + 1, local, n0, ns);
       S.bar.wait(local, S.err, S.bar_timeout);
       { std::lock_guard<std::mutex> lk(m->mu); m->done++; }
@@ -1625,6 +1635,180 @@ int pf_multi_decim_destroy(pf_multi *m, pf_decim *a) {
    return rc;
 }
 
+// ---- vector decimating recorders of a chain: the per-slab parts as the vector band accumulators' (region_part(...).local; a difference across the cut
+// reads the slab's ghost plane; the one-cell rule against the SCENE's faces is checked here), everything else as the decimating recorders': the chain
+// keeps `count` and `rd`, and what a full `cap` refuses and how many frames a read gives are decided before any slab is asked.  A slab's rows of
+// frames [n][ncomp][cells], acc [ncomp][P][cells] and state [ncomp][npre][2][cells] are all one region's cells apart.
+static int vdecim_chain(pf_multi *m, const pf_vdecim *a, const char *what) {
+   if (!a) return fail("%s: null pf_vdecim", what);
+   if (a->chain != m) return fail("%s: the pf_vdecim belongs to another engine or chain", what);
+   return PF_OK;
+}
+
+int pf_multi_vdecim_create(pf_multi *m, const pf_region *r, int32_t ncomp, const int32_t *comp, int32_t npre, const double *pre_sos, int32_t ntap, const double *taps,
+                           int32_t factor, int64_t cap, int32_t depth, pf_vdecim **out) {
+   const char *what = "pf_multi_vdecim_create";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_vdecim_create(S.eng[0], r, ncomp, comp, npre, pre_sos, ntap, taps, factor, cap, depth, out);
+   if (!r) return fail("%s: null pf_region", what);
+   if (!out) return fail("%s: null out", what);
+   *out = nullptr;
+   const int64_t N[3] = {m->sd->Nx, m->sd->Ny, m->sd->Nz};
+   char msg[256], full[400];
+   std::unique_ptr<pf_vdecim> a(new pf_vdecim());
+   if ((a->cells = pf_cut::region_check(r, N, a->rc, msg, sizeof msg)) < 0) { snprintf(full, sizeof full, "%s: %s", what, msg); return fail("%s", full); }
+   // the one-cell rule against the SCENE's faces (a slab checks its part against its own planes, where a cut is no face): pf_multi_vband_create's
+   if (comp && ncomp >= 1 && ncomp <= 4) {
+      bool lat = false;
+      for (int k = 0; k < ncomp; k++) lat = lat || (comp[k] >= 4 && comp[k] <= 6);
+      for (int ax = 0; lat && m->sd->fcc_flag != 0 && ax < 3; ax++) {
+         const int64_t last = r->lo[ax] + (a->rc[ax] - 1) * r->stride[ax];
+         if (r->lo[ax] < 1 || last > N[ax] - 2) {
+            snprintf(full, sizeof full, "%s: a lattice difference needs the region one cell clear of all six faces, along file %c too: pf_region.lo[%d] = %ld >= 1 and its last cell "
+                                        "%ld <= %ld", what, "xyz"[ax], ax, (long)r->lo[ax], (long)last, (long)N[ax] - 2);
+            return fail("%s", full);
+         }
+      }
+      for (int k = 0; k < ncomp; k++) {
+         const int ax = comp[k] - 1;
+         if (ax < 0 || ax > 2) continue;
+         const int64_t last = r->lo[ax] + (a->rc[ax] - 1) * r->stride[ax];
+         if (r->lo[ax] < 1 || last > N[ax] - 2) {
+            snprintf(full, sizeof full, "%s: a difference along file %c needs the region one cell clear of both faces along %c: pf_region.lo[%d] = %ld >= 1 and its last cell %ld <= %ld",
+                     what, "xyz"[ax], "xyz"[ax], ax, (long)r->lo[ax], (long)last, (long)N[ax] - 2);
+            return fail("%s", full);
+         }
+      }
+   }
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   a->chain = m; a->region = *r; a->factor = factor; a->cap = cap;
+   a->part.assign((size_t)S.G, nullptr);
+   for (int g = 0; g < S.G; g++) {
+      const pf_cut::RegionPart p = pf_cut::region_part(*r, a->rc, S.slabs[g], S.along_z);
+      if (p.empty) continue;
+      const int rc = pf_engine_vdecim_create(S.eng[g], &p.local, ncomp, comp, npre, pre_sos, ntap, taps, factor, cap, depth, &a->part[g]); // (a bad count, tap or coefficient: the first slab's message names it)
+      if (rc) {
+         const std::string keep = pf_last_error();
+         for (int h = 0; h < g; h++) if (a->part[h]) pf_engine_vdecim_destroy(S.eng[h], a->part[h]);
+         pf__set_error(keep.c_str());
+         return rc;
+      }
+   }
+   m->vdecims.push_back(a.get());
+   *out = a.release();
+   return PF_OK;
+}
+
+int pf_multi_vdecim_add(pf_multi *m, pf_vdecim *a) {
+   const char *what = "pf_multi_vdecim_add";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_vdecim_add(S.eng[0], a);
+   if (vdecim_chain(m, a, what)) return PF_ERR_ARG;
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   // all or nothing: the slab threads are idle, so every engine can be asked here, before any of them takes the sample
+   for (int g = 0; g < S.G; g++)
+      if (!pf__engine_between_runs(S.eng[g])) {
+         char b[256];
+         snprintf(b, sizeof b, "%s: slab %d is inside a pair or triple (u^{n+1} is not complete in memory): no slab took the sample; advance a step, or create the chain with "
+                               "PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES", what, g);
+         pf__set_error(b);
+         return PF_ERR_STATE;
+      }
+   if (a->count % a->factor == 0 && (a->count + a->factor - 1) / a->factor - a->rd == a->cap) {
+      char b[256];
+      snprintf(b, sizeof b, "%s: sample %ld would complete frame %ld while cap = %ld frames are complete and unread: read some first", what, (long)a->count,
+               (long)(a->count / a->factor), (long)a->cap);
+      pf__set_error(b);
+      return PF_ERR_STATE;
+   }
+   if (m->one_thread) { for (int g = 0; g < S.G; g++) vdecim_add_slab(S, g, a); }
+   else {
+      { std::lock_guard<std::mutex> lk(m->mu); m->cmd_vdecim = a; }
+      post(m, 10, 0, 0);
+      wait_done(m);
+      if (m->broken && !S.err.load()) S.set_error(PF_ERR_HIP, "slab chain hung: a slab's host thread never came back");
+   }
+   const int rc = accum_status(S);
+   if (rc == PF_OK) a->count++;
+   return rc;
+}
+
+int pf_multi_vdecim_read(pf_multi *m, pf_vdecim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread) {
+   const char *what = "pf_multi_vdecim_read";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_vdecim_read(S.eng[0], a, frames, max_frames, first, nread);
+   if (vdecim_chain(m, a, what)) return PF_ERR_ARG;
+   if (!first || !nread) return fail(!first ? "%s: null first" : "%s: null nread", what);
+   if (max_frames < 0) return fail("%s: max_frames < 0", what);
+   if (max_frames > 0 && !frames) return fail("%s: null frames array", what);
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   for (int g = 0; g < S.G; g++)
+      if (!pf__engine_between_runs(S.eng[g])) { fail("%s: a slab is inside a pair or triple: valid between passes only", what); return PF_ERR_STATE; }
+   const int64_t n = std::min(max_frames, (a->count + a->factor - 1) / a->factor - a->rd);
+   for (int g = 0; g < S.G; g++) {
+      if (!a->part[g]) continue;
+      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
+      int64_t f1 = 0, n1 = 0;
+      const int rc = pf__engine_vdecim_read_x(S.eng[g], a->part[g], frames ? frames + p.out_off : nullptr, n, &f1, &n1, p.out_pitch, a->cells);
+      if (rc) return rc;
+      if (n1 != n || (n && f1 != a->rd)) { fail("%s: internal: a slab's frames are not the chain's", what); return PF_ERR_STATE; }
+   }
+   *first = a->rd;
+   *nread = n;
+   a->rd += n;
+   return PF_OK;
+}
+
+int pf_multi_vdecim_get_state(pf_multi *m, pf_vdecim *a, double *acc, double *state) {
+   const char *what = "pf_multi_vdecim_get_state";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_vdecim_get_state(S.eng[0], a, acc, state);
+   if (vdecim_chain(m, a, what)) return PF_ERR_ARG;
+   if (!acc) return fail("%s: null acc array", what);
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   for (int g = 0; g < S.G; g++) {
+      if (!a->part[g]) continue;
+      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
+      const int rc = pf__engine_vdecim_get_state_x(S.eng[g], a->part[g], acc + p.out_off, state ? state + p.out_off : nullptr, p.out_pitch, a->cells);
+      if (rc) return rc;
+   }
+   return PF_OK;
+}
+
+int pf_multi_vdecim_set_state(pf_multi *m, pf_vdecim *a, const double *acc, const double *state, int64_t count) {
+   const char *what = "pf_multi_vdecim_set_state";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_vdecim_set_state(S.eng[0], a, acc, state, count);
+   if (vdecim_chain(m, a, what)) return PF_ERR_ARG;
+   if (count < 0) return fail("%s: count < 0", what);
+   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+   for (int g = 0; g < S.G; g++)
+      if (!pf__engine_between_runs(S.eng[g])) { fail("%s: a slab is inside a pair or triple: valid between passes only", what); return PF_ERR_STATE; }
+   for (int g = 0; g < S.G; g++) {
+      if (!a->part[g]) continue;
+      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
+      const int rc = pf__engine_vdecim_set_state_x(S.eng[g], a->part[g], acc ? acc + p.out_off : nullptr, state ? state + p.out_off : nullptr, p.out_pitch, a->cells, count);
+      if (rc) return rc;
+   }
+   a->count = count;
+   a->rd = (count + a->factor - 1) / a->factor;
+   return PF_OK;
+}
+
+int pf_multi_vdecim_destroy(pf_multi *m, pf_vdecim *a) {
+   const char *what = "pf_multi_vdecim_destroy";
+   if (!m) return fail("%s: null object", what);
+   Shared &S = m->S;
+   if (S.G == 1) return pf_engine_vdecim_destroy(S.eng[0], a);
+   if (vdecim_chain(m, a, what)) return PF_ERR_ARG;
+   int rc = PF_OK;
+   for (int g = 0; g < S.G; g++)
+      if (a->part[g] && S.eng[g]) { const int r1 = pf_engine_vdecim_destroy(S.eng[g], a->part[g]); if (r1 && !rc) rc = r1; }
+   m->vdecims.erase(std::find(m->vdecims.begin(), m->vdecims.end(), a));
+   delete a;
+   return rc;
+}
+
 int pf_multi_get_info(pf_multi *m, pf_multi_info *info) {
    if (!m || !info) return fail("pf_multi_get_info: null argument");
    const Shared &S = m->S;
@@ -1673,6 +1857,7 @@ void pf_multi_destroy(pf_multi *m) {
    for (pf_bandacc *a : m->bands) delete a;
    for (pf_vbandacc *a : m->vbands) delete a;
    for (pf_decim *a : m->decims) delete a;
+   for (pf_vdecim *a : m->vdecims) delete a;
    for (auto &c : S.comm) if (c) { g_rccl.CommDestroy(c); c = nullptr; }
    delete m;
 }

@@ -105,6 +105,9 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_grid_bytes", "p
            "pf_engine_decim_create", "pf_engine_decim_add", "pf_engine_decim_read", "pf_engine_decim_get_state", "pf_engine_decim_set_state", "pf_engine_decim_destroy",
            "pf_decim_count", "pf_decim_pending",
            "pf_multi_decim_create", "pf_multi_decim_add", "pf_multi_decim_read", "pf_multi_decim_get_state", "pf_multi_decim_set_state", "pf_multi_decim_destroy",
+           "pf_engine_vdecim_create", "pf_engine_vdecim_add", "pf_engine_vdecim_read", "pf_engine_vdecim_get_state", "pf_engine_vdecim_set_state", "pf_engine_vdecim_destroy",
+           "pf_vdecim_count", "pf_vdecim_pending",
+           "pf_multi_vdecim_create", "pf_multi_vdecim_add", "pf_multi_vdecim_read", "pf_multi_vdecim_get_state", "pf_multi_vdecim_set_state", "pf_multi_vdecim_destroy",
            "pf_engine_energy_cfg", "pf_engine_run_energy", "pf_run_sim_devices", "pf_slab_partition", "pf_slab_partition_w", "pf_slab_partition_axis", "pf_slab_wall_scale",
            "pf_multi_create", "pf_multi_run", "pf_multi_get_info", "pf_multi_get_slab", "pf_multi_destroy",
            "pf_rccl_unique_id", "pf_rccl_comm_create", "pf_rccl_exchange", "pf_rccl_comm_destroy"]
@@ -214,13 +217,19 @@ def lib():
             getattr(L, pre + "_decim_get_state").argtypes = [vp, vp, vp, vp]
             getattr(L, pre + "_decim_set_state").argtypes = [vp, vp, vp, vp, i64]
             getattr(L, pre + "_decim_destroy").argtypes = [vp, vp]
+            getattr(L, pre + "_vdecim_create").argtypes = [vp, ctypes.POINTER(PfRegion), i32, vp, i32, vp, i32, vp, i32, i64, i32, ctypes.POINTER(vp)]
+            getattr(L, pre + "_vdecim_add").argtypes = [vp, vp]
+            getattr(L, pre + "_vdecim_read").argtypes = [vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+            getattr(L, pre + "_vdecim_get_state").argtypes = [vp, vp, vp, vp]
+            getattr(L, pre + "_vdecim_set_state").argtypes = [vp, vp, vp, vp, i64]
+            getattr(L, pre + "_vdecim_destroy").argtypes = [vp, vp]
         L.pf_accum_count.restype = i64
         L.pf_accum_count.argtypes = [vp]
         L.pf_bandacc_count.restype = i64
         L.pf_bandacc_count.argtypes = [vp]
         L.pf_vbandacc_count.restype = i64
         L.pf_vbandacc_count.argtypes = [vp]
-        for f in (L.pf_decim_count, L.pf_decim_pending):
+        for f in (L.pf_decim_count, L.pf_decim_pending, L.pf_vdecim_count, L.pf_vdecim_pending):
             f.restype = i64
             f.argtypes = [vp]
         dp = ctypes.POINTER(ctypes.c_double)
@@ -599,6 +608,59 @@ class DecimatingRecorder:
             pass
 
 
+class VectorDecimatingRecorder(DecimatingRecorder):
+    """Per cell of a region, on the device (pf_engine_vdecim_* / pf_multi_vdecim_*): the components `comp` of a VectorBandAccumulator (0: the cell of
+    u^n, 1 / 2 / 3: its central difference along file x / y / z on a Cartesian grid, 4 / 5 / 6: the lattice difference of an FCC grid) through their
+    own sections pre_sos [ncomp, npre, 6], then each through the FIR `taps`, every `factor`-th output kept as a frame [ncomp, c0, c1, c2]; up to
+    `cap` frames wait on the device for read().  add, set_state, count, pending and close are a DecimatingRecorder's.
+    Made by HipEngine.vector_decimating_recorder / HipMulti.vector_decimating_recorder; it lives no longer than the object that made it."""
+
+    def __init__(self, owner, prefix, lo, hi, stride, comp, pre_sos, taps, factor, cap, depth):
+        try:
+            r = PfRegion((ctypes.c_int64 * 3)(*[int(v) for v in lo]), (ctypes.c_int64 * 3)(*[int(v) for v in hi]), (ctypes.c_int64 * 3)(*[int(v) for v in stride]))
+        except TypeError as e:
+            raise PfError(f"vector_decimating_recorder: lo, hi and stride are three integers each ({e})")
+        comp = np.ascontiguousarray(np.asarray(comp).reshape(-1), dtype=np.int32)
+        p = np.asarray([] if pre_sos is None else pre_sos, dtype=np.float64)
+        if p.size == 0:
+            pre = np.zeros((comp.size, 0, 5))
+        else:
+            if p.ndim != 3 or p.shape[0] != comp.size:
+                raise PfError(f"vector_decimating_recorder: pre_sos has shape {p.shape}: [ncomp = {comp.size}, npre, 6] is expected (pad a shorter cascade with 1 0 0 1 0 0)")
+            pre = _sos5("pre_sos", p, 2)
+        h = np.ascontiguousarray([] if taps is None else taps, dtype=np.float64)
+        if h.ndim != 1:
+            raise PfError(f"vector_decimating_recorder: taps has shape {h.shape}: a vector of ntap values is expected")
+        L = lib()
+        self._owner, self._f = owner, {k: getattr(L, f"{prefix}_vdecim_{k}") for k in ("create", "add", "read", "get_state", "set_state", "destroy")}
+        self._a = ctypes.c_void_p()
+        self.ncomp, self.comp = int(comp.size), tuple(int(c) for c in comp)
+        self.npre, self.ntap, self.factor = int(pre.shape[1]), int(h.size), int(factor)
+        self.cap = int(cap) if cap else 64  # frames kept on the device between two reads
+        vp = ctypes.c_void_p
+        _check(self._f["create"](owner._h, ctypes.byref(r), self.ncomp, comp.ctypes.data_as(vp) if comp.size else None, self.npre, pre.ctypes.data_as(vp) if pre.size else None,
+                                 self.ntap, h.ctypes.data_as(vp) if h.size else None, self.factor, self.cap, int(depth), ctypes.byref(self._a)))
+        counts = (ctypes.c_int64 * 3)()
+        L.pf_region_count(ctypes.byref(r), counts)
+        self.cells = tuple(int(c) for c in counts)
+        self.slots = -(-self.ntap // self.factor)  # P
+        self.acc_shape = (self.ncomp, self.slots) + self.cells  # of get_state()'s acc
+        self.state_shape = (self.ncomp, self.npre, 2) + self.cells  # ... and state
+
+    def read(self, max_frames=None):
+        """-> (first, frames float64 [nread, ncomp, c0, c1, c2]): the oldest complete frames in order (all of them, or max_frames), marked read"""
+        n = self.pending if max_frames is None else int(max_frames)
+        out = np.empty((max(n, 0), self.ncomp) + self.cells, dtype=np.float64)
+        first, nread = ctypes.c_int64(), ctypes.c_int64()
+        _check(self._f["read"](self._owner._h, self._a, out.ctypes.data_as(ctypes.c_void_p) if out.size else None, n, ctypes.byref(first), ctypes.byref(nread)))
+        return int(first.value), out[:nread.value]
+
+    def _number(self, name):
+        if not (self._a.value and self._alive()):
+            raise PfError(f"VectorDecimatingRecorder.{name}: the recorder or its owner is closed")
+        return int(getattr(lib(), f"pf_vdecim_{name}")(self._a))
+
+
 def device_count():
     return int(lib().pf_device_count())
 
@@ -707,6 +769,11 @@ class HipMulti:
         """Low-pass filtered, decimated frames of a region of the whole scene (pf_multi_decim_create): every slab keeps the part it owns.  add raises
         PfError (code 4) and takes no sample while a slab is inside a pair or triple, or when `cap` frames wait unread."""
         return DecimatingRecorder(self, "pf_multi", lo, hi, stride, pre_sos, taps, factor, cap, depth)
+
+    def vector_decimating_recorder(self, lo, hi, stride=(1, 1, 1), comp=(0,), pre_sos=None, taps=None, factor=1, cap=0, depth=0):
+        """Low-pass filtered, decimated frames of up to four components of a region of the whole scene (pf_multi_vdecim_create): every slab keeps the
+        part it owns, a difference across a cut reads the slab's ghost plane.  add raises PfError (code 4) where a slab stands inside a pair or triple."""
+        return VectorDecimatingRecorder(self, "pf_multi", lo, hi, stride, comp, pre_sos, taps, factor, cap, depth)
 
     def slab(self, g):
         """-> dict(x0, x1, device, paired, steps_per_pass, engine): engine = a non-owning HipEngine view of slab g's engine (state_grids, timing)"""
@@ -876,6 +943,11 @@ class HipEngine:
         """Per cell of the region, on the device (pf_engine_decim_create): every sample u^n through the sections pre_sos [npre, 6] and the FIR `taps`,
         every factor-th output kept as a frame, up to `cap` (0: 64) of them between two reads -- a DecimatingRecorder."""
         return DecimatingRecorder(self, "pf_engine", lo, hi, stride, pre_sos, taps, factor, cap, depth)
+
+    def vector_decimating_recorder(self, lo, hi, stride=(1, 1, 1), comp=(0,), pre_sos=None, taps=None, factor=1, cap=0, depth=0):
+        """Per cell of the region, on the device (pf_engine_vdecim_create): the components comp (as vector_band_accumulator's) through their own sections
+        pre_sos [ncomp, npre, 6] and each through the FIR `taps`, every factor-th output kept as a frame [ncomp, c0, c1, c2] -- a VectorDecimatingRecorder."""
+        return VectorDecimatingRecorder(self, "pf_engine", lo, hi, stride, comp, pre_sos, taps, factor, cap, depth)
 
     def set_grid(self, which, a):
         a = np.ascontiguousarray(a, dtype=self.dtype)

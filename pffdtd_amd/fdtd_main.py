@@ -64,7 +64,11 @@ pressure is low-pass filtered ON THE DEVICE at EVERY step from `--rec-first N` (
 every cell at the rate 1 / (D Ts), not aliased, in `--rec-dtype f4|f8`, appended to `--rec-file FILE` (default sim_recordings.h5 beside sim_outs.h5)
 as the run goes and completed at every checkpoint and at the end.  Everything else as the decay arguments: the run is cut at every step from N on,
 a chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (one line says so), `--resume` restores the outputs in flight and the filter state
-from the file, and without these arguments nothing about a run changes.
+from the file, and without these arguments nothing about a run changes.  `--rec-axes x,y,z` (one to three file axes) records the B-format impulse
+response instead: channel 0 is W, the pressure, and one channel per axis is the pressure of a figure-of-eight microphone along it, from the
+difference `--rec-stencil axis|lattice` names (the rules of `--dir-stencil`; regions one cell clear of the faces the difference reads); frames are
+[F, 1 + A, c0, c1, c2], and recordings.virtual_microphone points a first-order microphone anywhere at every cell.  Without `--rec-axes` the file is
+the pressure's, as before.
 """
 import argparse
 import os
@@ -226,12 +230,14 @@ def _field_recording(a, sd, m, resume_at):
     try:
         regions = [r for spec in a.rec_planes for r in fields.parse_planes(spec, N)] + [fields.parse_box(spec, N) for spec in a.rec_box]
         path = a.rec_file if a.rec_file else Path(a.data_dir) / "sim_recordings.h5"
-        fr = rec_mod.FieldRecording(path, sd, regions, a.rec_factor, a.rec_fpass, a.rec_atten, a.rec_first, dtype=a.rec_dtype, resume_at=resume_at)
+        fr = rec_mod.FieldRecording(path, sd, regions, a.rec_factor, a.rec_fpass, a.rec_atten, a.rec_first, dtype=a.rec_dtype, resume_at=resume_at,
+                                    axes=dir_mod.parse_axes(a.rec_axes) if a.rec_axes else None, stencil=a.rec_stencil)
     except ValueError as e:
-        raise SystemExit(str(e).replace("--field-", "--rec-"))
+        raise SystemExit(str(e).replace("--field-", "--rec-").replace("--dir-", "--rec-").replace('stencil="lattice"', "--rec-stencil lattice")
+                         .replace('stencil="axis"', "--rec-stencil axis"))
     try:
         fr.attach(m)
-    except engine.PfError as e:  # (a factor or a tap count the engine refuses: it names the field)
+    except engine.PfError as e:  # (a factor or a tap count the engine refuses, a region on a face along a recorded axis: it names the field)
         raise SystemExit(f"--rec-planes / --rec-box: {e}")
     return fr
 
@@ -353,7 +359,8 @@ def _run_chain_checkpointed(a, sd, m):
         fv.close()
     if fr:
         fr.write()
-        print(f"--field recording of {fr.count} samples, {fr.frames} frames at every {fr.factor}th step through {fr.taps.size} taps: {fr.path}", flush=True)
+        chan = "" if fr.axes is None else f", channels W {' '.join('XYZ'[k - 1] for k in fr.axes.tolist())} ({fr.stencil} differences)"
+        print(f"--field recording of {fr.count} samples, {fr.frames} frames at every {fr.factor}th step through {fr.taps.size} taps{chan}: {fr.path}", flush=True)
         fr.close()
     return time.perf_counter() - t0, {"air_ms_total": air_all * 1e3, "step_ms_total": step_all * 1e3}
 

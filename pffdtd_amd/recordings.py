@@ -6,6 +6,8 @@ D-th step on the device as the run goes, in one HDF5 file -- what can be listene
     fr.take(obj, n)                              obj: a HipEngine or HipMulti that has taken the steps 0 .. n-1; n >= first: every such step is a sample
     fr.write()                                   what is complete so far, and the state a resumed run continues from
     frames, Fs_out, t0 = read(path, i)           region i: float [F, c0, c1, c2] at Fs_out = 1 / (factor Ts); frame m belongs to the time t0 + m / Fs_out
+    FieldRecording(..., axes=[1, 2, 3], stencil="axis")                   B-format: W and one figure-of-eight channel per file axis, frames [F, 1 + A, c0, c1, c2]
+    virtual_microphone(frames, axes, direction, pattern=0.5)             host numpy: a first-order microphone pointed anywhere, at every cell
 
 A receiver per cell at the grid's rate is ten times or more oversampled against fmax; raw frames every D steps (fields.FieldWriter) fold everything
 above the new Nyquist frequency into the band of interest.  Here every step is a sample: it runs through what ProcessOutputs.initial_process applies
@@ -25,7 +27,15 @@ The file holds
                          to u_out), appended as drained
     r{i:03d}_acc  float64 [P, c0, c1, c2]   and   r{i:03d}_state  float64 [npre, 2, c0, c1, c2]: the outputs in flight and the sections' state, raw
 write() drains, copies the file to a temporary name, puts sampling, blocks, acc and state there and moves it into place with os.replace.
-With resume_at (the step a resumed run continues at) the file must match in regions, Ts, first, factor, taps and pre_sos, and its count must be
+With `axes` (1 .. 3 file axes, directional.parse_axes) one engine.VectorDecimatingRecorder per region (pf_engine_vdecim_*) keeps the cell and one
+difference per axis -- the central difference, or with stencil="lattice" the lattice difference of an FCC grid -- through the sections
+directional.gradient_sections gives, stacked as FieldDirectional stacks them (omni, then the gradient per axis): channel 0 is W, the pressure, channel
+1 + a the pressure of a figure-of-eight microphone along file axis axes[a].  The stencil and fcc_flag rules are FieldDirectional's.  Such a file
+additionally holds axes int64 [A], stencil int64, fcc_flag int64; pre_sos is [1 + A, npre, 6], a block [nf, 1 + A, c0, c1, c2], acc [1 + A, P, ...] and
+state [1 + A, npre, 2, ...].  On a folded grid (fcc_flag 2) the file's frames of a y channel are negated in the odd cells -- exact, as directional.py
+negates its odd-y products -- and r{i:03d}_iy int64 [c0, c1, c2] holds every cell's physical row; acc and state stay raw, in storage form.  Without
+`axes` the file has exactly the datasets above and the scalar recorder runs.
+With resume_at (the step a resumed run continues at) the file must match in regions, axes, stencil, Ts, first, factor, taps and pre_sos, and its count must be
 the number of sample steps below resume_at; otherwise it is refused with the field's name.  Blocks at or beyond ceil(count / factor) are dropped.
 """
 import os
@@ -36,6 +46,7 @@ from scipy.signal import firwin, freqz, kaiserord
 
 from . import h5io
 from .decay import pre_sections
+from .directional import LATTICE_SPAN, STENCILS, fold_coordinates, gradient_sections, parse_axes
 from .engine import PfError
 
 MAX_SLOTS = 128  # P = ceil(ntap / factor): the outputs a recorder holds in flight (include/pffdtd_hip.h)
@@ -75,7 +86,8 @@ def decimation_filter(Ts, factor, fpass_hz, atten_db=80.0):
 
 
 class FieldRecording:
-    def __init__(self, path, sd, regions, factor, fpass_hz, atten_db=80.0, first=0, lowcut_hz=10.0, lowcut_order=4, dtype="f4", resume_at=None, cap=32):
+    def __init__(self, path, sd, regions, factor, fpass_hz, atten_db=80.0, first=0, lowcut_hz=10.0, lowcut_order=4, dtype="f4", resume_at=None, cap=32, axes=None,
+                 stencil="axis"):
         self.path, self.sd = os.fspath(path), sd
         self.regions = [tuple(tuple(int(v) for v in t) for t in r) for r in regions]
         self.first, self.Ts, self.cap = int(first), float(sd.Ts), int(cap)
@@ -86,11 +98,40 @@ class FieldRecording:
         self.dtype = DTYPES[dtype]
         self.taps, self.info = decimation_filter(self.Ts, factor, fpass_hz, atten_db)
         self.factor = int(factor)
-        self.pre_sos = pre_sections(self.Ts, bool(getattr(sd, "diff", False)), float(lowcut_hz), int(lowcut_order))
+        self.axes, self.stencil, self.fcc_flag, self.comp = None, stencil, int(getattr(sd, "fcc_flag", 0)), None
+        if stencil not in STENCILS:
+            raise ValueError(f"FieldRecording: stencil: {stencil!r} is neither \"axis\" nor \"lattice\"")
+        if axes is None:
+            if stencil != "axis":
+                raise ValueError("FieldRecording: stencil: stencil=\"lattice\" chooses the difference of the channels `axes` asks for; without axes the pressure alone is recorded")
+            self.pre_sos = pre_sections(self.Ts, bool(getattr(sd, "diff", False)), float(lowcut_hz), int(lowcut_order))
+        else:
+            self._vector_setup(axes, float(lowcut_hz), int(lowcut_order))
         self.table = np.array([lo + hi + st for lo, hi, st in self.regions], dtype=np.int64).reshape(-1, 9)
         self.recs, self._restore, self.blocks, self._part, self._part0 = None, None, [], [], 0
         if resume_at is not None:
             self._restore = self._read_matching(int(resume_at))
+
+    def _vector_setup(self, axes, lowcut_hz, lowcut_order):
+        """axes: W and one figure-of-eight channel per file axis -- the components, and the sections per component as FieldDirectional stacks them"""
+        sd, stencil = self.sd, self.stencil
+        self.axes = np.ascontiguousarray(axes, dtype=np.int64).reshape(-1)
+        if self.axes.size < 1 or self.axes.size > 3 or np.any(self.axes < 1) or np.any(self.axes > 3) or len(set(self.axes.tolist())) != self.axes.size:
+            raise ValueError(f"FieldRecording: axes: {self.axes.tolist()} is not one to three different axes out of 1, 2, 3 (x, y, z)")
+        if stencil == "axis" and self.fcc_flag != 0:
+            raise ValueError("FieldRecording: fcc_flag: the central difference along an axis exists on Cartesian grids only (fcc_flag 0); an FCC grid takes "
+                             "stencil=\"lattice\", the difference over the lattice's own neighbours")
+        if stencil == "lattice" and self.fcc_flag == 0:
+            raise ValueError("FieldRecording: stencil=\"lattice\": the lattice difference exists on FCC grids only (fcc_flag 1 or 2); a Cartesian grid takes "
+                             "stencil=\"axis\"")
+        if getattr(sd, "h", None) is None or getattr(sd, "c", None) is None:
+            raise ValueError("FieldRecording: h, c: the scene's constants hold no grid spacing or speed of sound (sim_consts.h5: h, c)")
+        omni, grad = gradient_sections(self.Ts, float(sd.h), float(sd.c), bool(getattr(sd, "diff", False)), lowcut_hz, lowcut_order,
+                                       span=LATTICE_SPAN if stencil == "lattice" else 2)
+        if omni.shape[0] > 8:
+            raise ValueError(f"FieldRecording: lowcut_order: {omni.shape[0]} sections per component, a vector decimating recorder holds 8")
+        self.pre_sos = np.ascontiguousarray(np.stack([omni] + [grad] * self.axes.size))
+        self.comp = np.concatenate([[0], self.axes + (3 if stencil == "lattice" else 0)]).astype(np.int64)
 
     # ---- the sample steps ----
     def next_step(self, n):
@@ -105,13 +146,32 @@ class FieldRecording:
         return max(0, n - self.first)
 
     # ---- the recorders ----
+    def _frame_cells(self, r):
+        """the shape of one frame of a recorder: its cells, with the channels in front where `axes` asks for them"""
+        return r.cells if self.axes is None else (1 + self.axes.size,) + r.cells
+
+    def _as_filed(self, i, fr):
+        """frames as the file stores them: times infac, in `dtype`; on a folded grid a y channel negated in the odd cells (the stored +y of such a
+        cell is the room's -y: exact)"""
+        fr = fr * self.sd.infac
+        if self.axes is not None and self.fcc_flag == 2:
+            upper = fold_coordinates(self.regions[i], self.sd.Ny)[3]
+            for k, c in enumerate(self.comp.tolist()):
+                if c in (2, 5):
+                    fr[:, k][..., upper] = -fr[:, k][..., upper]
+        return fr.astype(self.dtype)
+
     def attach(self, obj):
         """one decimating recorder per region on obj (a HipEngine or a HipMulti); a resumed run's outputs in flight and filter state go into them.
         A new run starts the file; a resumed one keeps the blocks below its first frame."""
         if self.recs is not None:
             return
-        self.recs = [obj.decimating_recorder(lo, hi, st, pre_sos=self.pre_sos, taps=self.taps, factor=self.factor, cap=self.cap) for lo, hi, st in self.regions]
-        self._part = [np.zeros((0,) + r.cells, dtype=self.dtype) for r in self.recs]  # the frames of the block that is not full yet, as the file stores them
+        if self.axes is None:
+            self.recs = [obj.decimating_recorder(lo, hi, st, pre_sos=self.pre_sos, taps=self.taps, factor=self.factor, cap=self.cap) for lo, hi, st in self.regions]
+        else:
+            self.recs = [obj.vector_decimating_recorder(lo, hi, st, comp=self.comp, pre_sos=self.pre_sos, taps=self.taps, factor=self.factor, cap=self.cap)
+                         for lo, hi, st in self.regions]
+        self._part = [np.zeros((0,) + self._frame_cells(r), dtype=self.dtype) for r in self.recs]  # the frames of the block that is not full yet, as the file stores them
         self._part0 = 0  # ... and its first frame
         if self._restore is not None:
             count, acc, state, nfull, part = self._restore
@@ -161,7 +221,7 @@ class FieldRecording:
         for i, r in enumerate(self.recs):
             _, fr = r.read()
             if fr.shape[0]:
-                self._part[i] = np.concatenate([self._part[i], (fr * self.sd.infac).astype(self.dtype)])
+                self._part[i] = np.concatenate([self._part[i], self._as_filed(i, fr)])
         full = False
         while self._part[0].shape[0] >= self.cap:
             for i in range(len(self.recs)):
@@ -185,7 +245,14 @@ class FieldRecording:
         h5io.write(path, "sampling", np.array([self.first, self.factor, self.count, self.frames], dtype=np.int64))
         h5io.write(path, "taps", self.taps)
         h5io.write(path, "pre_sos", self.pre_sos if self.pre_sos.size else np.zeros((1, 6)))  # (no section: one row of zeros)
-        h5io.write(path, "npre", np.int64(self.pre_sos.shape[0]))
+        h5io.write(path, "npre", np.int64(self.pre_sos.shape[-2]))
+        if self.axes is not None:
+            h5io.write(path, "axes", self.axes)
+            h5io.write(path, "stencil", np.int64(STENCILS.index(self.stencil)))
+            h5io.write(path, "fcc_flag", np.int64(self.fcc_flag))
+            if self.fcc_flag == 2:
+                for i, r in enumerate(self.regions):
+                    h5io.write(path, f"r{i:03d}_iy", np.ascontiguousarray(fold_coordinates(r, self.sd.Ny)[1], dtype=np.int64))
         h5io.write(path, "frame_bytes", np.int64(np.dtype(self.dtype).itemsize))
         h5io.write(path, "design", np.array([self.info[k] for k in ("fpass", "atten", "stop_db", "ripple_db", "delay")], dtype=np.float64))
         self._write_blocks(path)
@@ -220,6 +287,11 @@ class FieldRecording:
         f = read_file(self.path, raw=True)
         if not np.array_equal(f["regions"], self.table):
             raise ValueError(f"{self.path}: regions: the file holds the frames of other regions")
+        if (f["axes"] is None) != (self.axes is None) or (self.axes is not None and not np.array_equal(f["axes"], self.axes)):
+            raise ValueError(f"{self.path}: axes: the file holds the channels of axes {None if f['axes'] is None else f['axes'].tolist()}, "
+                             f"{None if self.axes is None else self.axes.tolist()} asked for")
+        if f["stencil"] != self.stencil:
+            raise ValueError(f"{self.path}: stencil: the file holds the frames of stencil=\"{f['stencil']}\", \"{self.stencil}\" is asked for")
         if f["Ts"] != self.Ts:
             raise ValueError(f"{self.path}: Ts: {f['Ts']!r} in the file, {self.Ts!r} in the scene")
         first, factor, count, _ = (int(v) for v in f["sampling"])
@@ -232,7 +304,7 @@ class FieldRecording:
         if h5io._CODE_TO_NP[f["frame_code"]] != self.dtype:
             raise ValueError(f"{self.path}: dtype: the file's frames are {np.dtype(h5io._CODE_TO_NP[f['frame_code']]).name}, {np.dtype(self.dtype).name} asked for")
         if not np.array_equal(f["pre_sos"], self.pre_sos):
-            raise ValueError(f"{self.path}: pre_sos: the file's frames went through other shared sections (low-cut, integrator)")
+            raise ValueError(f"{self.path}: pre_sos: the file's frames went through other sections (low-cut, integrator, grid spacing)")
         if count != self.samples_below(resume_at):
             raise ValueError(f"{self.path}: count: the file holds {count} samples, {self.samples_below(resume_at)} sample steps lie below step {resume_at}")
         done = -(-count // factor)  # frames complete at the resumed step; blocks at or beyond it are a later run's
@@ -248,22 +320,30 @@ class FieldRecording:
 
 
 def read_file(path, raw=False):
-    """-> dict(regions [R, 9], Ts, sampling [first, factor, count, frames], taps, pre_sos [npre, 6], design [5], blocks [B]; raw: also acc and state per
-    region, state None without sections) of a file FieldRecording wrote"""
+    """-> dict(regions [R, 9], Ts, sampling [first, factor, count, frames], taps, pre_sos [npre, 6], design [5], blocks [B], axes None, stencil "axis",
+    fcc_flag 0; raw: also acc and state per region, state None without sections) of a file FieldRecording wrote.  A file written with `axes`: axes
+    int64 [A], stencil "axis" / "lattice", fcc_flag, pre_sos [1 + A, npre, 6], and -- fcc_flag 2 -- iy, per region int64 [c0, c1, c2]"""
     regions = np.asarray(h5io.read(path, "regions", h5io.I64)).reshape(-1, 9)
     npre, nblocks = int(h5io.read(path, "npre", h5io.I64)), int(h5io.read(path, "nblocks", h5io.I64))
+    axes = np.asarray(h5io.read(path, "axes", h5io.I64)).reshape(-1) if h5io.exists(path, "axes") else None
+    pre = np.asarray(h5io.read(path, "pre_sos", h5io.F64))
     out = {"regions": regions, "Ts": float(h5io.read(path, "Ts", h5io.F64)), "sampling": np.asarray(h5io.read(path, "sampling", h5io.I64)).reshape(4),
-           "taps": np.asarray(h5io.read(path, "taps", h5io.F64)).reshape(-1), "pre_sos": np.asarray(h5io.read(path, "pre_sos", h5io.F64)).reshape(-1, 6)[:npre],
+           "taps": np.asarray(h5io.read(path, "taps", h5io.F64)).reshape(-1), "pre_sos": pre.reshape(-1, 6)[:npre] if axes is None else pre.reshape(1 + axes.size, -1, 6),
+           "axes": axes, "stencil": STENCILS[int(h5io.read(path, "stencil", h5io.I64))] if axes is not None else "axis",
+           "fcc_flag": int(h5io.read(path, "fcc_flag", h5io.I64)) if axes is not None else 0,
            "design": np.asarray(h5io.read(path, "design", h5io.F64)).reshape(5), "blocks": np.asarray(h5io.read(path, "blocks", h5io.I64)).reshape(-1)[:nblocks],
            "frame_code": h5io.F32 if int(h5io.read(path, "frame_bytes", h5io.I64)) == 4 else h5io.F64}
     if raw:
         out["acc"] = [np.asarray(h5io.read(path, f"r{i:03d}_acc", h5io.F64)) for i in range(len(regions))]
         out["state"] = [np.asarray(h5io.read(path, f"r{i:03d}_state", h5io.F64)) if npre else None for i in range(len(regions))]
+    if out["fcc_flag"] == 2:
+        out["iy"] = [np.asarray(h5io.read(path, f"r{i:03d}_iy", h5io.I64)) for i in range(len(regions))]
     return out
 
 
 def read(path, i):
-    """-> (frames [F, c0, c1, c2] of region i, the blocks concatenated; Fs_out = 1 / (factor Ts); t0 = (first - delay) Ts, the time of frame 0)"""
+    """-> (frames [F, c0, c1, c2] of region i -- [F, 1 + A, c0, c1, c2] of a file written with `axes`: W, then the figure-of-eight channel per axis --,
+    the blocks concatenated; Fs_out = 1 / (factor Ts); t0 = (first - delay) Ts, the time of frame 0)"""
     f = read_file(path)
     first, factor = int(f["sampling"][0]), int(f["sampling"][1])
     parts = [np.asarray(h5io.read(path, f"r{i:03d}_f{int(m0):07d}", f["frame_code"])) for m0 in f["blocks"]]
@@ -273,8 +353,33 @@ def read(path, i):
             raise ValueError(f"{path}: blocks: block {int(m0)} of region {i} does not follow frame {at - 1}")
         at += p.shape[0]
     counts = tuple(int(-(-(hi - lo) // st)) for lo, hi, st in zip(f["regions"][i, 0:3], f["regions"][i, 3:6], f["regions"][i, 6:9]))
+    if f["axes"] is not None:
+        counts = (1 + f["axes"].size,) + counts
     frames = np.concatenate(parts) if parts else np.zeros((0,) + counts, dtype=h5io._CODE_TO_NP[f["frame_code"]])
     return frames, 1.0 / (factor * f["Ts"]), (first - f["design"][4]) * f["Ts"]
+
+
+def virtual_microphone(frames, axes, direction, pattern=0.5):
+    """frames [F, 1 + A, ...] as read() gives them for a file written with `axes` (1 / 2 / 3 = file x / y / z, in the file's order), direction: a unit
+    vector in file axes -> [F, ...]: pattern * W + (1 - pattern) * sum_a d_a V_a, the signal of a first-order microphone pointed along `direction`
+    at every cell.  pattern 1: omni, 0.5: cardioid, 0: figure-of-eight.  A direction with a component along an axis that was not recorded is refused
+    by name."""
+    frames = np.asarray(frames)
+    axes = [int(a) for a in np.asarray(axes).reshape(-1)]
+    d = np.asarray(direction, dtype=np.float64).reshape(-1)
+    if frames.ndim < 2 or frames.shape[1] != 1 + len(axes):
+        raise ValueError(f"virtual_microphone: frames: shape {frames.shape} is not [F, 1 + {len(axes)}, ...] for axes {axes}")
+    if d.size != 3 or not np.isfinite(d).all() or abs(float(np.sqrt((d * d).sum())) - 1.0) > 1e-9:
+        raise ValueError(f"virtual_microphone: direction: {d.tolist()} is not a unit vector (x, y, z) in file axes")
+    if not 0.0 <= float(pattern) <= 1.0:
+        raise ValueError(f"virtual_microphone: pattern: {pattern} outside 0 (figure-of-eight) .. 1 (omni)")
+    for a in (1, 2, 3):
+        if a not in axes and d[a - 1] != 0.0:
+            raise ValueError(f"virtual_microphone: direction: a component {d[a - 1]:g} along file {'xyz'[a - 1]}, but axis {a} was not recorded (axes {axes})")
+    out = float(pattern) * frames[:, 0].astype(np.float64)
+    for k, a in enumerate(axes):
+        out = out + (1.0 - float(pattern)) * d[a - 1] * frames[:, 1 + k]
+    return out
 
 
 def add_arguments(p):
@@ -287,6 +392,8 @@ def add_arguments(p):
     p.add_argument("--rec-first", type=int, default=0, metavar="N", help="... at every step from N on (default 0)")
     p.add_argument("--rec-dtype", choices=sorted(DTYPES), default="f4", help="... stored as float32 (f4, the default) or float64 (f8)")
     p.add_argument("--rec-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_recordings.h5 in the data folder)")
+    p.add_argument("--rec-axes", default="", metavar="x,y,z", help="... as a B-format impulse response: W and a figure-of-eight channel along each of these file axes (one to three)")
+    p.add_argument("--rec-stencil", choices=STENCILS, default="axis", help="... from the central difference along the axis (Cartesian grids, the default) or the lattice difference (FCC grids)")
 
 
 def check_arguments(p, a):
@@ -294,5 +401,12 @@ def check_arguments(p, a):
     a.rec = bool(a.rec_planes or a.rec_box)
     if a.rec != bool(a.rec_factor) or a.rec != bool(a.rec_fpass) or a.rec_first < 0 or a.rec_atten <= 0:
         p.error("--rec-planes / --rec-box need --rec-factor and --rec-fpass (and the other way round); --rec-atten: positive, --rec-first: not negative")
-    if (a.rec_first or a.rec_file or a.rec_atten != 80.0 or a.rec_dtype != "f4") and not a.rec:
-        p.error("--rec-atten / --rec-first / --rec-dtype / --rec-file need --rec-planes or --rec-box")
+    if (a.rec_first or a.rec_file or a.rec_atten != 80.0 or a.rec_dtype != "f4" or a.rec_axes or a.rec_stencil != "axis") and not a.rec:
+        p.error("--rec-atten / --rec-first / --rec-dtype / --rec-file / --rec-axes / --rec-stencil need --rec-planes or --rec-box")
+    if a.rec_stencil != "axis" and not a.rec_axes:
+        p.error("--rec-stencil chooses the difference of the channels --rec-axes asks for: it needs --rec-axes")
+    if a.rec_axes:
+        try:
+            parse_axes(a.rec_axes)
+        except ValueError as e:
+            p.error(str(e).replace("--dir-axes", "--rec-axes"))
