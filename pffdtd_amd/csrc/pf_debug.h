@@ -21,76 +21,64 @@ extern "C" void pf_internal_hooks(int32_t debug, int32_t test_drop_exchange, int
 pf_opts_x pf__take_hooks(const pf_opts *o); // *o (NULL: the defaults) + the calling thread's pending switches + PFFDTD_DEBUG
 int pf__engine_create_x(const pf_simdata *sd, const pf_opts_x *o, pf_engine **out);
 int pf__engine_get_region_x(pf_engine *e, int32_t which, const pf_region *r, void *host, int64_t pitch); // pf_engine_get_region with the output's rows `pitch` elements apart (0: dense)
-// A field accumulator's handle (pffdtd_hip.h: pf_accum).  An engine's: `eng` and the engine's own object `impl`.  A chain's: `chain` and one engine
-// handle per slab, null where the region misses the slab -- part[g] sums region_part(...).local of slab g.  `count` is kept here, by the C ABI.
-struct pf_accum {
+// The region observers: field accumulators, band accumulators, vector band accumulators, decimating recorders and vector decimating recorders.  Their
+// kinds (an engine's object and a handle are their kind's alone) and what a message calls their handle types and their chain functions (pf_multi_<name>_*).
+namespace pfeng {
+enum : int { OBS_ACCUM, OBS_BAND, OBS_VBAND, OBS_DECIM, OBS_VDECIM };
+static const char *const obs_type[5] = {"pf_accum", "pf_bandacc", "pf_vbandacc", "pf_decim", "pf_vdecim"};
+static const char *const obs_name[5] = {"accum", "bandacc", "vband", "decim", "vdecim"};
+}
+// What the five handle types of pffdtd_hip.h share.  An engine's handle: `eng` and the engine's own object `impl`.  A chain's: `chain` and, in the
+// derived type's `part`, one engine handle per slab, null where the region misses the slab -- part[g] observes region_part(...).local of slab g; its
+// rows land in the caller's arrays at out_off, the region's rows out_pitch and the device rows `cells` (of the whole region) apart.  `count` is kept
+// here, by the C ABI; an engine's recorder keeps its own (pf_decim_count asks it).
+struct pf_observer {
    pf_engine *eng = nullptr;
    void *impl = nullptr;
    pf_multi *chain = nullptr;
-   std::vector<pf_accum *> part;
    pf_region region{};
    int64_t rc[3] = {0, 0, 0}, cells = 0; // the region's counts
-   int32_t nchan = 0;
    int64_t count = 0;
+   virtual ~pf_observer() {}
 };
-// pf_engine_accum_get / _set with the caller's rows `pitch` and channels `chstride` doubles apart (0: dense) -- a slab's cells of a chain's array; count: as given
+struct pf_accum : pf_observer {
+   static constexpr int kind = pfeng::OBS_ACCUM;
+   std::vector<pf_accum *> part;
+   int32_t nchan = 0;
+};
+struct pf_bandacc : pf_observer { // rows_e = nband * nbin, rows_s = (npre + nband * nsec) * 2 rows of `cells` doubles
+   static constexpr int kind = pfeng::OBS_BAND;
+   std::vector<pf_bandacc *> part;
+   int64_t nbin = 0;
+};
+struct pf_vbandacc : pf_observer {
+   static constexpr int kind = pfeng::OBS_VBAND;
+   std::vector<pf_vbandacc *> part;
+   int64_t nbin = 0;
+};
+// A chain's recorder: the slabs' parts advance together, and the chain keeps `count` and `rd` (the next frame a read gives) itself -- its refusals
+// are host arithmetic.
+struct pf_decim : pf_observer {
+   static constexpr int kind = pfeng::OBS_DECIM;
+   std::vector<pf_decim *> part;
+   int64_t factor = 1, cap = 0, rd = 0;
+};
+struct pf_vdecim : pf_observer { // frames are [ncomp][cells], acc [ncomp][P][cells]
+   static constexpr int kind = pfeng::OBS_VDECIM;
+   std::vector<pf_vdecim *> part;
+   int64_t factor = 1, cap = 0, rd = 0;
+};
+// pf_engine_*_get / _set / _read / _get_state / _set_state with the caller's region rows `pitch` and channel / sum / state / frame / acc rows `rowstride`
+// doubles apart (0: dense) -- a slab's cells of a chain's arrays; count: as given.  The recorders': `a` is a pf_decim (scalar) or a pf_vdecim.
 int pf__engine_accum_get_x(pf_engine *e, pf_accum *a, double *host, int64_t pitch, int64_t chstride);
 int pf__engine_accum_set_x(pf_engine *e, pf_accum *a, const double *host, int64_t pitch, int64_t chstride, int64_t count);
-// A band accumulator's handle (pffdtd_hip.h: pf_bandacc): as pf_accum.  rows_e = nband * nbin, rows_s = (npre + nband * nsec) * 2 rows of `cells` doubles.
-struct pf_bandacc {
-   pf_engine *eng = nullptr;
-   void *impl = nullptr;
-   pf_multi *chain = nullptr;
-   std::vector<pf_bandacc *> part;
-   pf_region region{};
-   int64_t rc[3] = {0, 0, 0}, cells = 0;
-   int64_t nbin = 0, count = 0;
-};
-// pf_engine_bandacc_get / _set with the caller's region rows `pitch` and sum / state rows `rowstride` doubles apart (0: dense) -- a slab's cells of a chain's arrays
 int pf__engine_bandacc_get_x(pf_engine *e, pf_bandacc *a, double *sums, double *state, int64_t pitch, int64_t rowstride);
 int pf__engine_bandacc_set_x(pf_engine *e, pf_bandacc *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride, int64_t count);
-// A vector band accumulator's handle (pffdtd_hip.h: pf_vbandacc): as pf_bandacc.
-struct pf_vbandacc {
-   pf_engine *eng = nullptr;
-   void *impl = nullptr;
-   pf_multi *chain = nullptr;
-   std::vector<pf_vbandacc *> part;
-   pf_region region{};
-   int64_t rc[3] = {0, 0, 0}, cells = 0;
-   int64_t nbin = 0, count = 0;
-};
-// pf_engine_vband_get / _set with the caller's region rows `pitch` and sum / state rows `rowstride` doubles apart (0: dense) -- a slab's cells of a chain's arrays
 int pf__engine_vband_get_x(pf_engine *e, pf_vbandacc *a, double *sums, double *state, int64_t pitch, int64_t rowstride);
 int pf__engine_vband_set_x(pf_engine *e, pf_vbandacc *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride, int64_t count);
-// A decimating recorder's handle (pffdtd_hip.h: pf_decim): as pf_bandacc.  An engine's: count and the frames read are the engine object's.  A chain's: the
-// slabs' parts advance together, and the chain keeps `count` and `rd` (the next frame a read gives) itself -- its refusals are host arithmetic.
-struct pf_decim {
-   pf_engine *eng = nullptr;
-   void *impl = nullptr;
-   pf_multi *chain = nullptr;
-   std::vector<pf_decim *> part;
-   pf_region region{};
-   int64_t rc[3] = {0, 0, 0}, cells = 0;
-   int64_t factor = 1, cap = 0, count = 0, rd = 0;
-};
-// pf_engine_decim_read / _get_state / _set_state with the caller's region rows `pitch` and frame / acc / state rows `rowstride` doubles apart (0: dense)
-int pf__engine_decim_read_x(pf_engine *e, pf_decim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride);
-int pf__engine_decim_get_state_x(pf_engine *e, pf_decim *a, double *acc, double *state, int64_t pitch, int64_t rowstride);
-int pf__engine_decim_set_state_x(pf_engine *e, pf_decim *a, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count);
-// A vector decimating recorder's handle (pffdtd_hip.h: pf_vdecim): as pf_decim; frames are [ncomp][cells], acc [ncomp][P][cells].
-struct pf_vdecim {
-   pf_engine *eng = nullptr;
-   void *impl = nullptr;
-   pf_multi *chain = nullptr;
-   std::vector<pf_vdecim *> part;
-   pf_region region{};
-   int64_t rc[3] = {0, 0, 0}, cells = 0;
-   int64_t factor = 1, cap = 0, count = 0, rd = 0;
-};
-// pf_engine_vdecim_read / _get_state / _set_state with the caller's region rows `pitch` and frame / acc / state rows `rowstride` doubles apart (0: dense)
-int pf__engine_vdecim_read_x(pf_engine *e, pf_vdecim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride);
-int pf__engine_vdecim_get_state_x(pf_engine *e, pf_vdecim *a, double *acc, double *state, int64_t pitch, int64_t rowstride);
-int pf__engine_vdecim_set_state_x(pf_engine *e, pf_vdecim *a, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count);
+int pf__engine_rec_read_x(pf_engine *e, pf_observer *a, bool scalar, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride);
+int pf__engine_rec_get_state_x(pf_engine *e, pf_observer *a, bool scalar, double *acc, double *state, int64_t pitch, int64_t rowstride);
+int pf__engine_rec_set_state_x(pf_engine *e, pf_observer *a, bool scalar, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count);
 int pf__engine_between_runs(pf_engine *e); // 1: not inside a split-phase step or pass (what pf_engine_accum_add needs)
 enum : int {
    PF_DBG_BRANCH_SELECTS = 0x1,       // three-step wall regions: fd_regs' select form (a branch count per lane) even where every material has the same count

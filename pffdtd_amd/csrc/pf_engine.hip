@@ -50,11 +50,7 @@ extern "C" int pf__axis_exchange_pays(const pf_simdata *sd, int64_t *counts) {
 
 struct pf_engine {
    pfeng::EngineBase *impl;
-   std::vector<pf_accum *> accums; // the handles of its field accumulators still alive (pf_engine_destroy frees those left)
-   std::vector<pf_bandacc *> bands; // ... and of its band accumulators
-   std::vector<pf_vbandacc *> vbands; // ... and of its vector band accumulators
-   std::vector<pf_decim *> decims; // ... and of its decimating recorders
-   std::vector<pf_vdecim *> vdecims; // ... and of its vector decimating recorders
+   std::vector<pf_observer *> observers; // the handles of its region observers still alive (pf_engine_destroy frees those left)
 };
 pfeng::EngineBase *pf__new_engine_f64(const pf_simdata *sd, const pf_opts_x *o, int *rc); // pf_engine_f64.hip
 
@@ -128,7 +124,7 @@ int pf__engine_create_x(const pf_simdata *sd, const pf_opts_x *opts, pf_engine *
       return set_err(PF_ERR_ARG, "real_bytes must be 4 or 8 (got %d)", sd->real_bytes);
    }
    if (rc) { std::string keep = g_err; delete impl; g_err = keep; return rc; }
-   *out = new pf_engine{impl, {}, {}, {}, {}, {}};
+   *out = new pf_engine{impl, {}};
    return PF_OK;
 }
 
@@ -138,302 +134,199 @@ int pf__engine_get_region_x(pf_engine *e, int32_t which, const pf_region *r, voi
    return e->impl->get_region(which, r, host, pitch);
 }
 
-// field accumulators: the handle must be this engine's (a chain's handle, or another engine's, is refused before the engine sees it)
-static int accum_mine(pf_engine *e, const pf_accum *a, const char *what) {
+// region observers (pf_debug.h): the handle must be this engine's (a chain's handle, or another engine's, is refused before the engine sees it; one of
+// another kind is refused by the engine, which looks its object up by kind)
+static int mine(pf_engine *e, const pf_observer *a, int kind, const char *what) {
    if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
-   if (!a) return set_err(PF_ERR_ARG, "%s: null pf_accum", what);
-   if (a->eng != e) return set_err(PF_ERR_ARG, "%s: the pf_accum belongs to another engine%s", what, a->chain ? " (it is a chain's: pf_multi_accum_*)" : "");
+   if (!a) return set_err(PF_ERR_ARG, "%s: null %s", what, pfeng::obs_type[kind]);
+   if (a->eng != e) {
+      char chain[64] = "";
+      if (a->chain) snprintf(chain, sizeof chain, " (it is a chain's: pf_multi_%s_*)", pfeng::obs_name[kind]);
+      return set_err(PF_ERR_ARG, "%s: the %s belongs to another engine%s", what, pfeng::obs_type[kind], chain);
+   }
    return PF_OK;
 }
-// internal (pf_multi.hip): a slab's cells of a chain's [nchan][cells] array -- rows `pitch`, channels `chstride` doubles apart
+// make(&impl): the engine's create call
+template <typename T, typename Make> static int create(pf_engine *e, const char *what, const pf_region *r, T **out, Make make) {
+   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
+   if (!out) return set_err(PF_ERR_ARG, "%s: null out", what);
+   *out = nullptr;
+   void *impl = nullptr;
+   const int rc = make(&impl);
+   if (rc) return rc;
+   T *a = new T();
+   a->eng = e; a->impl = impl; a->region = *r;
+   a->cells = pf_cut::region_counts(r, a->rc);
+   e->observers.push_back(a);
+   *out = a;
+   return PF_OK;
+}
+// the accumulators' add and set: the engine's call, then the count the C ABI keeps
+template <typename Add> static int add_counted(pf_engine *e, pf_observer *a, int kind, const char *what, Add add) {
+   int rc = mine(e, a, kind, what);
+   if (rc || (rc = add())) return rc;
+   a->count++;
+   return PF_OK;
+}
+template <typename Set> static int set_counted(pf_engine *e, pf_observer *a, int kind, const char *what, int64_t count, Set set) {
+   int rc = mine(e, a, kind, what);
+   if (rc) return rc;
+   if (count < 0) return set_err(PF_ERR_ARG, "%s: count = %ld < 0", what, (long)count);
+   if ((rc = set())) return rc;
+   a->count = count;
+   return PF_OK;
+}
+static int destroy(pf_engine *e, pf_observer *a, int kind, const char *what) {
+   int rc = mine(e, a, kind, what);
+   if (rc || (rc = e->impl->observer_destroy(what, kind, a->impl))) return rc;
+   e->observers.erase(std::find(e->observers.begin(), e->observers.end(), a));
+   delete a;
+   return PF_OK;
+}
+// (an engine's recorder asks the engine's object; a chain's keeps the two numbers itself)
+template <typename T> static void rec_numbers(const T *a, int64_t *count, int64_t *pending) {
+   *count = *pending = -1;
+   if (!a) return;
+   if (a->chain) { *count = a->count; *pending = (a->count + a->factor - 1) / a->factor - a->rd; }
+   else if (a->eng && a->eng->impl) a->eng->impl->vdecim_info(T::kind == pfeng::OBS_DECIM, a->impl, count, pending);
+}
+#define PF_REC(scalar, fn) const char *what = (scalar) ? "pf_engine_decim_" fn : "pf_engine_vdecim_" fn; const int kind = (scalar) ? pfeng::OBS_DECIM : pfeng::OBS_VDECIM
+
+// internal (pf_multi.hip): a slab's cells of a chain's arrays
 int pf__engine_accum_get_x(pf_engine *e, pf_accum *a, double *host, int64_t pitch, int64_t chstride) {
-   const int rc = accum_mine(e, a, "pf_engine_accum_get");
+   const int rc = mine(e, a, pfeng::OBS_ACCUM, "pf_engine_accum_get");
    return rc ? rc : e->impl->accum_get(a->impl, host, pitch, chstride);
 }
 int pf__engine_accum_set_x(pf_engine *e, pf_accum *a, const double *host, int64_t pitch, int64_t chstride, int64_t count) {
-   int rc = accum_mine(e, a, "pf_engine_accum_set");
-   if (rc) return rc;
-   if (count < 0) return set_err(PF_ERR_ARG, "pf_engine_accum_set: count = %ld < 0", (long)count);
-   if ((rc = e->impl->accum_set(a->impl, host, pitch, chstride))) return rc;
-   a->count = count;
-   return PF_OK;
-}
-// band accumulators: the same rule
-static int band_mine(pf_engine *e, const pf_bandacc *a, const char *what) {
-   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
-   if (!a) return set_err(PF_ERR_ARG, "%s: null pf_bandacc", what);
-   if (a->eng != e) return set_err(PF_ERR_ARG, "%s: the pf_bandacc belongs to another engine%s", what, a->chain ? " (it is a chain's: pf_multi_bandacc_*)" : "");
-   return PF_OK;
+   return set_counted(e, a, pfeng::OBS_ACCUM, "pf_engine_accum_set", count, [&] { return e->impl->accum_set(a->impl, host, pitch, chstride); });
 }
 int pf__engine_bandacc_get_x(pf_engine *e, pf_bandacc *a, double *sums, double *state, int64_t pitch, int64_t rowstride) {
-   const int rc = band_mine(e, a, "pf_engine_bandacc_get");
+   const int rc = mine(e, a, pfeng::OBS_BAND, "pf_engine_bandacc_get");
    return rc ? rc : e->impl->band_get(a->impl, sums, state, pitch, rowstride);
 }
 int pf__engine_bandacc_set_x(pf_engine *e, pf_bandacc *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride, int64_t count) {
-   int rc = band_mine(e, a, "pf_engine_bandacc_set");
-   if (rc) return rc;
-   if (count < 0) return set_err(PF_ERR_ARG, "pf_engine_bandacc_set: count = %ld < 0", (long)count);
-   if ((rc = e->impl->band_set(a->impl, sums, state, pitch, rowstride))) return rc;
-   a->count = count;
-   return PF_OK;
-}
-// vector band accumulators: the same rule
-static int vband_mine(pf_engine *e, const pf_vbandacc *a, const char *what) {
-   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
-   if (!a) return set_err(PF_ERR_ARG, "%s: null pf_vbandacc", what);
-   if (a->eng != e) return set_err(PF_ERR_ARG, "%s: the pf_vbandacc belongs to another engine%s", what, a->chain ? " (it is a chain's: pf_multi_vband_*)" : "");
-   return PF_OK;
+   return set_counted(e, a, pfeng::OBS_BAND, "pf_engine_bandacc_set", count, [&] { return e->impl->band_set(a->impl, sums, state, pitch, rowstride); });
 }
 int pf__engine_vband_get_x(pf_engine *e, pf_vbandacc *a, double *sums, double *state, int64_t pitch, int64_t rowstride) {
-   const int rc = vband_mine(e, a, "pf_engine_vband_get");
+   const int rc = mine(e, a, pfeng::OBS_VBAND, "pf_engine_vband_get");
    return rc ? rc : e->impl->vband_get(a->impl, sums, state, pitch, rowstride);
 }
 int pf__engine_vband_set_x(pf_engine *e, pf_vbandacc *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride, int64_t count) {
-   int rc = vband_mine(e, a, "pf_engine_vband_set");
-   if (rc) return rc;
-   if (count < 0) return set_err(PF_ERR_ARG, "pf_engine_vband_set: count = %ld < 0", (long)count);
-   if ((rc = e->impl->vband_set(a->impl, sums, state, pitch, rowstride))) return rc;
-   a->count = count;
-   return PF_OK;
+   return set_counted(e, a, pfeng::OBS_VBAND, "pf_engine_vband_set", count, [&] { return e->impl->vband_set(a->impl, sums, state, pitch, rowstride); });
 }
-// decimating recorders: the same rule
-static int decim_mine(pf_engine *e, const pf_decim *a, const char *what) {
-   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
-   if (!a) return set_err(PF_ERR_ARG, "%s: null pf_decim", what);
-   if (a->eng != e) return set_err(PF_ERR_ARG, "%s: the pf_decim belongs to another engine%s", what, a->chain ? " (it is a chain's: pf_multi_decim_*)" : "");
-   return PF_OK;
+int pf__engine_rec_read_x(pf_engine *e, pf_observer *a, bool scalar, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride) {
+   PF_REC(scalar, "read");
+   const int rc = mine(e, a, kind, what);
+   return rc ? rc : e->impl->vdecim_read(what, scalar, a->impl, frames, max_frames, first, nread, pitch, rowstride);
 }
-int pf__engine_decim_read_x(pf_engine *e, pf_decim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride) {
-   const int rc = decim_mine(e, a, "pf_engine_decim_read");
-   return rc ? rc : e->impl->decim_read(a->impl, frames, max_frames, first, nread, pitch, rowstride);
+int pf__engine_rec_get_state_x(pf_engine *e, pf_observer *a, bool scalar, double *acc, double *state, int64_t pitch, int64_t rowstride) {
+   PF_REC(scalar, "get_state");
+   const int rc = mine(e, a, kind, what);
+   return rc ? rc : e->impl->vdecim_get_state(what, scalar, a->impl, acc, state, pitch, rowstride);
 }
-int pf__engine_decim_get_state_x(pf_engine *e, pf_decim *a, double *acc, double *state, int64_t pitch, int64_t rowstride) {
-   const int rc = decim_mine(e, a, "pf_engine_decim_get_state");
-   return rc ? rc : e->impl->decim_get_state(a->impl, acc, state, pitch, rowstride);
+int pf__engine_rec_set_state_x(pf_engine *e, pf_observer *a, bool scalar, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count) {
+   PF_REC(scalar, "set_state");
+   const int rc = mine(e, a, kind, what);
+   return rc ? rc : e->impl->vdecim_set_state(what, scalar, a->impl, acc, state, pitch, rowstride, count);
 }
-int pf__engine_decim_set_state_x(pf_engine *e, pf_decim *a, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count) {
-   const int rc = decim_mine(e, a, "pf_engine_decim_set_state");
-   return rc ? rc : e->impl->decim_set_state(a->impl, acc, state, pitch, rowstride, count);
+static int rec_add(pf_engine *e, pf_observer *a, bool scalar) {
+   PF_REC(scalar, "add");
+   const int rc = mine(e, a, kind, what);
+   return rc ? rc : e->impl->vdecim_add(what, scalar, a->impl);
 }
-// vector decimating recorders: the same rule
-static int vdecim_mine(pf_engine *e, const pf_vdecim *a, const char *what) {
-   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
-   if (!a) return set_err(PF_ERR_ARG, "%s: null pf_vdecim", what);
-   if (a->eng != e) return set_err(PF_ERR_ARG, "%s: the pf_vdecim belongs to another engine%s", what, a->chain ? " (it is a chain's: pf_multi_vdecim_*)" : "");
-   return PF_OK;
-}
-int pf__engine_vdecim_read_x(pf_engine *e, pf_vdecim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride) {
-   const int rc = vdecim_mine(e, a, "pf_engine_vdecim_read");
-   return rc ? rc : e->impl->vdecim_read(a->impl, frames, max_frames, first, nread, pitch, rowstride);
-}
-int pf__engine_vdecim_get_state_x(pf_engine *e, pf_vdecim *a, double *acc, double *state, int64_t pitch, int64_t rowstride) {
-   const int rc = vdecim_mine(e, a, "pf_engine_vdecim_get_state");
-   return rc ? rc : e->impl->vdecim_get_state(a->impl, acc, state, pitch, rowstride);
-}
-int pf__engine_vdecim_set_state_x(pf_engine *e, pf_vdecim *a, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count) {
-   const int rc = vdecim_mine(e, a, "pf_engine_vdecim_set_state");
-   return rc ? rc : e->impl->vdecim_set_state(a->impl, acc, state, pitch, rowstride, count);
-}
+#undef PF_REC
 int pf__engine_between_runs(pf_engine *e) { return e && e->impl && e->impl->between_runs() ? 1 : 0; }
 
 extern "C" {
 
 void pf_engine_destroy(pf_engine *e) {
    if (!e) return;
-   for (pf_accum *a : e->accums) delete a; // (their device memory is the engine's: freed with it)
-   for (pf_bandacc *a : e->bands) delete a;
-   for (pf_vbandacc *a : e->vbands) delete a;
-   for (pf_decim *a : e->decims) delete a;
-   for (pf_vdecim *a : e->vdecims) delete a;
+   for (pf_observer *a : e->observers) delete a; // (their device memory is the engine's: freed with it)
    delete e->impl;
    delete e;
 }
 
 int pf_engine_accum_create(pf_engine *e, const pf_region *r, int32_t nchan, int32_t depth, pf_accum **out) {
-   const char *what = "pf_engine_accum_create";
-   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
-   if (!out) return set_err(PF_ERR_ARG, "%s: null out", what);
-   *out = nullptr;
-   void *impl = nullptr;
-   const int rc = e->impl->accum_create(r, nchan, depth, &impl);
-   if (rc) return rc;
-   pf_accum *a = new pf_accum();
-   a->eng = e; a->impl = impl; a->region = *r; a->nchan = nchan;
-   a->cells = pf_cut::region_counts(r, a->rc);
-   e->accums.push_back(a);
-   *out = a;
-   return PF_OK;
+   const int rc = create(e, "pf_engine_accum_create", r, out, [&](void **impl) { return e->impl->accum_create(r, nchan, depth, impl); });
+   if (rc == PF_OK) (*out)->nchan = nchan;
+   return rc;
 }
 int pf_engine_accum_add(pf_engine *e, pf_accum *a, const double *w) {
-   int rc = accum_mine(e, a, "pf_engine_accum_add");
-   if (rc || (rc = e->impl->accum_add(a->impl, w))) return rc;
-   a->count++;
-   return PF_OK;
+   return add_counted(e, a, pfeng::OBS_ACCUM, "pf_engine_accum_add", [&] { return e->impl->accum_add(a->impl, w); });
 }
 int pf_engine_accum_get(pf_engine *e, pf_accum *a, double *host) { return pf__engine_accum_get_x(e, a, host, 0, 0); }
 int pf_engine_accum_set(pf_engine *e, pf_accum *a, const double *host, int64_t count) { return pf__engine_accum_set_x(e, a, host, 0, 0, count); }
 int64_t pf_accum_count(const pf_accum *a) { return a ? a->count : -1; }
-int pf_engine_accum_destroy(pf_engine *e, pf_accum *a) {
-   int rc = accum_mine(e, a, "pf_engine_accum_destroy");
-   if (rc || (rc = e->impl->accum_destroy(a->impl))) return rc;
-   e->accums.erase(std::find(e->accums.begin(), e->accums.end(), a));
-   delete a;
-   return PF_OK;
-}
+int pf_engine_accum_destroy(pf_engine *e, pf_accum *a) { return destroy(e, a, pfeng::OBS_ACCUM, "pf_engine_accum_destroy"); }
 
 int pf_engine_bandacc_create(pf_engine *e, const pf_region *r, int32_t npre, const double *pre_sos, int32_t nband, int32_t nsec, const double *band_sos, int64_t nbin,
                              int32_t depth, pf_bandacc **out) {
-   const char *what = "pf_engine_bandacc_create";
-   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
-   if (!out) return set_err(PF_ERR_ARG, "%s: null out", what);
-   *out = nullptr;
-   void *impl = nullptr;
-   const int rc = e->impl->band_create(r, npre, pre_sos, nband, nsec, band_sos, nbin, depth, &impl);
-   if (rc) return rc;
-   pf_bandacc *a = new pf_bandacc();
-   a->eng = e; a->impl = impl; a->region = *r; a->nbin = nbin;
-   a->cells = pf_cut::region_counts(r, a->rc);
-   e->bands.push_back(a);
-   *out = a;
-   return PF_OK;
+   const int rc = create(e, "pf_engine_bandacc_create", r, out, [&](void **impl) { return e->impl->band_create(r, npre, pre_sos, nband, nsec, band_sos, nbin, depth, impl); });
+   if (rc == PF_OK) (*out)->nbin = nbin;
+   return rc;
 }
 int pf_engine_bandacc_add(pf_engine *e, pf_bandacc *a, int64_t bin) {
-   int rc = band_mine(e, a, "pf_engine_bandacc_add");
-   if (rc || (rc = e->impl->band_add(a->impl, bin))) return rc;
-   a->count++;
-   return PF_OK;
+   return add_counted(e, a, pfeng::OBS_BAND, "pf_engine_bandacc_add", [&] { return e->impl->band_add(a->impl, bin); });
 }
 int pf_engine_bandacc_get(pf_engine *e, pf_bandacc *a, double *sums, double *state) { return pf__engine_bandacc_get_x(e, a, sums, state, 0, 0); }
 int pf_engine_bandacc_set(pf_engine *e, pf_bandacc *a, const double *sums, const double *state, int64_t count) { return pf__engine_bandacc_set_x(e, a, sums, state, 0, 0, count); }
 int64_t pf_bandacc_count(const pf_bandacc *a) { return a ? a->count : -1; }
-int pf_engine_bandacc_destroy(pf_engine *e, pf_bandacc *a) {
-   int rc = band_mine(e, a, "pf_engine_bandacc_destroy");
-   if (rc || (rc = e->impl->band_destroy(a->impl))) return rc;
-   e->bands.erase(std::find(e->bands.begin(), e->bands.end(), a));
-   delete a;
-   return PF_OK;
-}
+int pf_engine_bandacc_destroy(pf_engine *e, pf_bandacc *a) { return destroy(e, a, pfeng::OBS_BAND, "pf_engine_bandacc_destroy"); }
 
 int pf_engine_vband_create(pf_engine *e, const pf_region *r, int32_t ncomp, const int32_t *comp, int32_t npre, const double *pre_sos, int32_t nband, int32_t nsec,
                            const double *band_sos, int32_t nprod, const int32_t *prod, int64_t nbin, int32_t depth, pf_vbandacc **out) {
-   const char *what = "pf_engine_vband_create";
-   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
-   if (!out) return set_err(PF_ERR_ARG, "%s: null out", what);
-   *out = nullptr;
-   void *impl = nullptr;
-   const int rc = e->impl->vband_create(r, ncomp, comp, npre, pre_sos, nband, nsec, band_sos, nprod, prod, nbin, depth, &impl);
-   if (rc) return rc;
-   pf_vbandacc *a = new pf_vbandacc();
-   a->eng = e; a->impl = impl; a->region = *r; a->nbin = nbin;
-   a->cells = pf_cut::region_counts(r, a->rc);
-   e->vbands.push_back(a);
-   *out = a;
-   return PF_OK;
+   const int rc = create(e, "pf_engine_vband_create", r, out,
+                         [&](void **impl) { return e->impl->vband_create(r, ncomp, comp, npre, pre_sos, nband, nsec, band_sos, nprod, prod, nbin, depth, impl); });
+   if (rc == PF_OK) (*out)->nbin = nbin;
+   return rc;
 }
 int pf_engine_vband_add(pf_engine *e, pf_vbandacc *a, int64_t bin) {
-   int rc = vband_mine(e, a, "pf_engine_vband_add");
-   if (rc || (rc = e->impl->vband_add(a->impl, bin))) return rc;
-   a->count++;
-   return PF_OK;
+   return add_counted(e, a, pfeng::OBS_VBAND, "pf_engine_vband_add", [&] { return e->impl->vband_add(a->impl, bin); });
 }
 int pf_engine_vband_get(pf_engine *e, pf_vbandacc *a, double *sums, double *state) { return pf__engine_vband_get_x(e, a, sums, state, 0, 0); }
 int pf_engine_vband_set(pf_engine *e, pf_vbandacc *a, const double *sums, const double *state, int64_t count) { return pf__engine_vband_set_x(e, a, sums, state, 0, 0, count); }
 int64_t pf_vbandacc_count(const pf_vbandacc *a) { return a ? a->count : -1; }
-int pf_engine_vband_destroy(pf_engine *e, pf_vbandacc *a) {
-   int rc = vband_mine(e, a, "pf_engine_vband_destroy");
-   if (rc || (rc = e->impl->vband_destroy(a->impl))) return rc;
-   e->vbands.erase(std::find(e->vbands.begin(), e->vbands.end(), a));
-   delete a;
-   return PF_OK;
-}
+int pf_engine_vband_destroy(pf_engine *e, pf_vbandacc *a) { return destroy(e, a, pfeng::OBS_VBAND, "pf_engine_vband_destroy"); }
 
+// the scalar recorder is the vector recorder with the one component 0 and a handle type of its own
 int pf_engine_decim_create(pf_engine *e, const pf_region *r, int32_t npre, const double *pre_sos, int32_t ntap, const double *taps, int32_t factor, int64_t cap,
                            int32_t depth, pf_decim **out) {
+   static const int32_t cell[1] = {0};
    const char *what = "pf_engine_decim_create";
-   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
-   if (!out) return set_err(PF_ERR_ARG, "%s: null out", what);
-   *out = nullptr;
-   void *impl = nullptr;
-   const int rc = e->impl->decim_create(r, npre, pre_sos, ntap, taps, factor, cap, depth, &impl);
-   if (rc) return rc;
-   pf_decim *a = new pf_decim();
-   a->eng = e; a->impl = impl; a->region = *r; a->factor = factor; a->cap = cap;
-   a->cells = pf_cut::region_counts(r, a->rc);
-   e->decims.push_back(a);
-   *out = a;
-   return PF_OK;
+   const int rc = create(e, what, r, out, [&](void **impl) { return e->impl->vdecim_create(what, true, r, 1, cell, npre, pre_sos, ntap, taps, factor, cap, depth, impl); });
+   if (rc == PF_OK) { (*out)->factor = factor; (*out)->cap = cap; }
+   return rc;
 }
-int pf_engine_decim_add(pf_engine *e, pf_decim *a) {
-   const int rc = decim_mine(e, a, "pf_engine_decim_add");
-   return rc ? rc : e->impl->decim_add(a->impl);
-}
+int pf_engine_decim_add(pf_engine *e, pf_decim *a) { return rec_add(e, a, true); }
 int pf_engine_decim_read(pf_engine *e, pf_decim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread) {
-   return pf__engine_decim_read_x(e, a, frames, max_frames, first, nread, 0, 0);
+   return pf__engine_rec_read_x(e, a, true, frames, max_frames, first, nread, 0, 0);
 }
-int pf_engine_decim_get_state(pf_engine *e, pf_decim *a, double *acc, double *state) { return pf__engine_decim_get_state_x(e, a, acc, state, 0, 0); }
+int pf_engine_decim_get_state(pf_engine *e, pf_decim *a, double *acc, double *state) { return pf__engine_rec_get_state_x(e, a, true, acc, state, 0, 0); }
 int pf_engine_decim_set_state(pf_engine *e, pf_decim *a, const double *acc, const double *state, int64_t count) {
-   return pf__engine_decim_set_state_x(e, a, acc, state, 0, 0, count);
+   return pf__engine_rec_set_state_x(e, a, true, acc, state, 0, 0, count);
 }
-// (an engine's handle asks the engine's object; a chain's keeps the two numbers itself)
-static void decim_numbers(const pf_decim *a, int64_t *count, int64_t *pending) {
-   *count = *pending = -1;
-   if (!a) return;
-   if (a->chain) { *count = a->count; *pending = (a->count + a->factor - 1) / a->factor - a->rd; }
-   else if (a->eng && a->eng->impl) a->eng->impl->decim_info(a->impl, count, pending);
-}
-int64_t pf_decim_count(const pf_decim *a) { int64_t c, p; decim_numbers(a, &c, &p); return c; }
-int64_t pf_decim_pending(const pf_decim *a) { int64_t c, p; decim_numbers(a, &c, &p); return p; }
-int pf_engine_decim_destroy(pf_engine *e, pf_decim *a) {
-   int rc = decim_mine(e, a, "pf_engine_decim_destroy");
-   if (rc || (rc = e->impl->decim_destroy(a->impl))) return rc;
-   e->decims.erase(std::find(e->decims.begin(), e->decims.end(), a));
-   delete a;
-   return PF_OK;
-}
+int64_t pf_decim_count(const pf_decim *a) { int64_t c, p; rec_numbers(a, &c, &p); return c; }
+int64_t pf_decim_pending(const pf_decim *a) { int64_t c, p; rec_numbers(a, &c, &p); return p; }
+int pf_engine_decim_destroy(pf_engine *e, pf_decim *a) { return destroy(e, a, pfeng::OBS_DECIM, "pf_engine_decim_destroy"); }
 
 int pf_engine_vdecim_create(pf_engine *e, const pf_region *r, int32_t ncomp, const int32_t *comp, int32_t npre, const double *pre_sos, int32_t ntap, const double *taps,
                             int32_t factor, int64_t cap, int32_t depth, pf_vdecim **out) {
    const char *what = "pf_engine_vdecim_create";
-   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
-   if (!out) return set_err(PF_ERR_ARG, "%s: null out", what);
-   *out = nullptr;
-   void *impl = nullptr;
-   const int rc = e->impl->vdecim_create(r, ncomp, comp, npre, pre_sos, ntap, taps, factor, cap, depth, &impl);
-   if (rc) return rc;
-   pf_vdecim *a = new pf_vdecim();
-   a->eng = e; a->impl = impl; a->region = *r; a->factor = factor; a->cap = cap;
-   a->cells = pf_cut::region_counts(r, a->rc);
-   e->vdecims.push_back(a);
-   *out = a;
-   return PF_OK;
+   const int rc = create(e, what, r, out, [&](void **impl) { return e->impl->vdecim_create(what, false, r, ncomp, comp, npre, pre_sos, ntap, taps, factor, cap, depth, impl); });
+   if (rc == PF_OK) { (*out)->factor = factor; (*out)->cap = cap; }
+   return rc;
 }
-int pf_engine_vdecim_add(pf_engine *e, pf_vdecim *a) {
-   const int rc = vdecim_mine(e, a, "pf_engine_vdecim_add");
-   return rc ? rc : e->impl->vdecim_add(a->impl);
-}
+int pf_engine_vdecim_add(pf_engine *e, pf_vdecim *a) { return rec_add(e, a, false); }
 int pf_engine_vdecim_read(pf_engine *e, pf_vdecim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread) {
-   return pf__engine_vdecim_read_x(e, a, frames, max_frames, first, nread, 0, 0);
+   return pf__engine_rec_read_x(e, a, false, frames, max_frames, first, nread, 0, 0);
 }
-int pf_engine_vdecim_get_state(pf_engine *e, pf_vdecim *a, double *acc, double *state) { return pf__engine_vdecim_get_state_x(e, a, acc, state, 0, 0); }
+int pf_engine_vdecim_get_state(pf_engine *e, pf_vdecim *a, double *acc, double *state) { return pf__engine_rec_get_state_x(e, a, false, acc, state, 0, 0); }
 int pf_engine_vdecim_set_state(pf_engine *e, pf_vdecim *a, const double *acc, const double *state, int64_t count) {
-   return pf__engine_vdecim_set_state_x(e, a, acc, state, 0, 0, count);
+   return pf__engine_rec_set_state_x(e, a, false, acc, state, 0, 0, count);
 }
-// (an engine's handle asks the engine's object; a chain's keeps the two numbers itself)
-static void vdecim_numbers(const pf_vdecim *a, int64_t *count, int64_t *pending) {
-   *count = *pending = -1;
-   if (!a) return;
-   if (a->chain) { *count = a->count; *pending = (a->count + a->factor - 1) / a->factor - a->rd; }
-   else if (a->eng && a->eng->impl) a->eng->impl->vdecim_info(a->impl, count, pending);
-}
-int64_t pf_vdecim_count(const pf_vdecim *a) { int64_t c, p; vdecim_numbers(a, &c, &p); return c; }
-int64_t pf_vdecim_pending(const pf_vdecim *a) { int64_t c, p; vdecim_numbers(a, &c, &p); return p; }
-int pf_engine_vdecim_destroy(pf_engine *e, pf_vdecim *a) {
-   int rc = vdecim_mine(e, a, "pf_engine_vdecim_destroy");
-   if (rc || (rc = e->impl->vdecim_destroy(a->impl))) return rc;
-   e->vdecims.erase(std::find(e->vdecims.begin(), e->vdecims.end(), a));
-   delete a;
-   return PF_OK;
-}
+int64_t pf_vdecim_count(const pf_vdecim *a) { int64_t c, p; rec_numbers(a, &c, &p); return c; }
+int64_t pf_vdecim_pending(const pf_vdecim *a) { int64_t c, p; rec_numbers(a, &c, &p); return p; }
+int pf_engine_vdecim_destroy(pf_engine *e, pf_vdecim *a) { return destroy(e, a, pfeng::OBS_VDECIM, "pf_engine_vdecim_destroy"); }
 
 #define PF_NEED(e) if (!(e) || !(e)->impl) return set_err(PF_ERR_ARG, "null engine")
 

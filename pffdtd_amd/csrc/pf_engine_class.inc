@@ -32,7 +32,6 @@
 #include "pf_accum.h"
 #include "pf_band.h"
 #include "pf_vband.h"
-#include "pf_decim.h"
 #include "pf_vdecim.h"
 
 // shared between the two units (defined in pf_engine.hip)
@@ -63,33 +62,24 @@ struct EngineBase {
    virtual int accum_add(void *a, const double *w) = 0;
    virtual int accum_get(void *a, double *host, int64_t pitch, int64_t chstride) = 0;
    virtual int accum_set(void *a, const double *host, int64_t pitch, int64_t chstride) = 0;
-   virtual int accum_destroy(void *a) = 0;
    virtual int band_create(const pf_region *r, int npre, const double *pre_sos, int nband, int nsec, const double *band_sos, int64_t nbin, int depth, void **out) = 0; // band accumulators (pf_engine_band.inc)
    virtual int band_add(void *a, int64_t bin) = 0;
    virtual int band_get(void *a, double *sums, double *state, int64_t pitch, int64_t rowstride) = 0;
    virtual int band_set(void *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride) = 0;
-   virtual int band_destroy(void *a) = 0;
    virtual int vband_create(const pf_region *r, int ncomp, const int32_t *comp, int npre, const double *pre_sos, int nband, int nsec, const double *band_sos, int nprod,
                             const int32_t *prod, int64_t nbin, int depth, void **out) = 0; // vector band accumulators (pf_engine_vband.inc)
    virtual int vband_add(void *a, int64_t bin) = 0;
    virtual int vband_get(void *a, double *sums, double *state, int64_t pitch, int64_t rowstride) = 0;
    virtual int vband_set(void *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride) = 0;
-   virtual int vband_destroy(void *a) = 0;
-   virtual int decim_create(const pf_region *r, int npre, const double *pre_sos, int ntap, const double *taps, int factor, int64_t cap, int depth, void **out) = 0; // decimating recorders (pf_engine_decim.inc)
-   virtual int decim_add(void *a) = 0;
-   virtual int decim_read(void *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride) = 0;
-   virtual int decim_get_state(void *a, double *acc, double *state, int64_t pitch, int64_t rowstride) = 0;
-   virtual int decim_set_state(void *a, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count) = 0;
-   virtual int decim_info(void *a, int64_t *count, int64_t *pending) const = 0;
-   virtual int decim_destroy(void *a) = 0;
-   virtual int vdecim_create(const pf_region *r, int ncomp, const int32_t *comp, int npre, const double *pre_sos, int ntap, const double *taps, int factor, int64_t cap, int depth,
-                             void **out) = 0; // vector decimating recorders (pf_engine_vdecim.inc)
-   virtual int vdecim_add(void *a) = 0;
-   virtual int vdecim_read(void *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride) = 0;
-   virtual int vdecim_get_state(void *a, double *acc, double *state, int64_t pitch, int64_t rowstride) = 0;
-   virtual int vdecim_set_state(void *a, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count) = 0;
-   virtual int vdecim_info(void *a, int64_t *count, int64_t *pending) const = 0;
-   virtual int vdecim_destroy(void *a) = 0;
+   // the decimating recorders, scalar (`scalar`: the handle is a pf_decim, ncomp = 1, comp = {0}) and vector (pf_engine_vdecim.inc); what: the public function's name
+   virtual int vdecim_create(const char *what, bool scalar, const pf_region *r, int ncomp, const int32_t *comp, int npre, const double *pre_sos, int ntap, const double *taps,
+                             int factor, int64_t cap, int depth, void **out) = 0;
+   virtual int vdecim_add(const char *what, bool scalar, void *a) = 0;
+   virtual int vdecim_read(const char *what, bool scalar, void *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride) = 0;
+   virtual int vdecim_get_state(const char *what, bool scalar, void *a, double *acc, double *state, int64_t pitch, int64_t rowstride) = 0;
+   virtual int vdecim_set_state(const char *what, bool scalar, void *a, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count) = 0;
+   virtual int vdecim_info(bool scalar, void *a, int64_t *count, int64_t *pending) const = 0;
+   virtual int observer_destroy(const char *what, int kind, void *a) = 0; // any of the five kinds (pf_engine_observe.inc); kind: OBS_*
    virtual bool between_runs() const = 0; // not inside a split-phase step or pass
    virtual int save_state(pf_state *st) = 0;
    virtual int load_state(const pf_state *st) = 0;
@@ -1110,10 +1100,10 @@ template <typename Real> struct Engine : EngineBase {
    }
 #include "pf_engine_state.inc"
 #include "pf_engine_region.inc"
+#include "pf_engine_observe.inc"
 #include "pf_engine_accum.inc"
 #include "pf_engine_band.inc"
 #include "pf_engine_vband.inc"
-#include "pf_engine_decim.inc"
 #include "pf_engine_vdecim.inc"
    void *stream(int which) override { return which == 1 ? (void *)s_edge : (void *)s_main; }
 };

@@ -38,10 +38,12 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <cstdarg>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -600,39 +602,12 @@ void region_slab(Shared &S, int g, int which, const pf_region &r, const int64_t 
    ECHK(g, pf__engine_get_region_x(S.eng[g], which, &p.local, out, p.out_pitch));
 }
 
-// a sample of a field accumulator: slab g adds u^n of its part on its own device (the caller has seen every slab between two passes: all or nothing)
-void accum_add_slab(Shared &S, int g, pf_accum *a, const double *w) {
-   if (S.err.load() || !S.eng[g] || !a->part[g]) return;
+// a sample of a region observer: slab g adds u^n of its part on its own device (the caller has seen every slab between two passes: all or nothing).
+// add(g): the engine's call for the slab's part, PF_OK where the region misses the slab
+void sample_slab(Shared &S, int g, const std::function<int(int)> &add) {
+   if (S.err.load() || !S.eng[g]) return;
    MCHK(g, hipSetDevice(S.dev[g]));
-   ECHK(g, pf_engine_accum_add(S.eng[g], a->part[g], w));
-}
-
-// ... and of a band accumulator
-void band_add_slab(Shared &S, int g, pf_bandacc *a, int64_t bin) {
-   if (S.err.load() || !S.eng[g] || !a->part[g]) return;
-   MCHK(g, hipSetDevice(S.dev[g]));
-   ECHK(g, pf_engine_bandacc_add(S.eng[g], a->part[g], bin));
-}
-
-// ... and of a vector band accumulator
-void vband_add_slab(Shared &S, int g, pf_vbandacc *a, int64_t bin) {
-   if (S.err.load() || !S.eng[g] || !a->part[g]) return;
-   MCHK(g, hipSetDevice(S.dev[g]));
-   ECHK(g, pf_engine_vband_add(S.eng[g], a->part[g], bin));
-}
-
-// ... and of a decimating recorder
-void decim_add_slab(Shared &S, int g, pf_decim *a) {
-   if (S.err.load() || !S.eng[g] || !a->part[g]) return;
-   MCHK(g, hipSetDevice(S.dev[g]));
-   ECHK(g, pf_engine_decim_add(S.eng[g], a->part[g]));
-}
-
-// ... and of a vector decimating recorder
-void vdecim_add_slab(Shared &S, int g, pf_vdecim *a) {
-   if (S.err.load() || !S.eng[g] || !a->part[g]) return;
-   MCHK(g, hipSetDevice(S.dev[g]));
-   ECHK(g, pf_engine_vdecim_add(S.eng[g], a->part[g]));
+   ECHK(g, add(g));
 }
 
 void finish_slab(Shared &S, int g) {
@@ -718,19 +693,9 @@ struct pf_multi {
    std::mutex mu;
    std::condition_variable cv_cmd, cv_done;
    int64_t cmd_seq = 0, cmd_n0 = 0, cmd_ns = 0;
-   int cmd_kind = 0;                 // 1 run, 2 quit, 3 save the state, 4 load it, 5 cut a region of a field, 6 add a sample to a field accumulator, 7 to a band accumulator, 8 to a vector band accumulator, 9 to a decimating recorder, 10 to a vector decimating recorder
-   pf_accum *cmd_accum = nullptr;    // 6: the chain's accumulator and the sample's weights
-   const double *cmd_w = nullptr;
-   pf_bandacc *cmd_band = nullptr;   // 7: the chain's band accumulator and the sample's bin
-   int64_t cmd_bin = 0;
-   std::vector<pf_bandacc *> bands;  // the chain's band accumulators still alive
-   pf_vbandacc *cmd_vband = nullptr; // 8: the chain's vector band accumulator (its bin: cmd_bin)
-   std::vector<pf_vbandacc *> vbands; // the chain's vector band accumulators still alive
-   pf_decim *cmd_decim = nullptr;    // 9: the chain's decimating recorder
-   std::vector<pf_decim *> decims;   // the chain's decimating recorders still alive
-   pf_vdecim *cmd_vdecim = nullptr;  // 10: the chain's vector decimating recorder
-   std::vector<pf_vdecim *> vdecims; // the chain's vector decimating recorders still alive
-   std::vector<pf_accum *> accums;   // the chain's field accumulators still alive (pf_multi_destroy frees those left)
+   int cmd_kind = 0;                 // 1 run, 2 quit, 3 save the state, 4 load it, 5 cut a region of a field, 6 add a sample to a region observer
+   std::function<int(int)> cmd_sample; // 6: the engine's add call for slab g's part of the chain's observer (sample_slab)
+   std::vector<pf_observer *> observers; // the chain's region observers still alive (pf_multi_destroy frees those left)
    pf_state *cmd_state = nullptr;    // ... from / into these global arrays
    pf_region cmd_region{};           // 5: the region (checked), its counts, the field, the caller's dense array
    int64_t cmd_rc[3] = {0, 0, 0};
@@ -765,11 +730,7 @@ void worker(pf_multi *m, int g) {
       if (kind == 2) break;
       if (kind == 3 || kind == 4) state_slab(S, g, m->sd, m->cmd_state, kind == 4);
       else if (kind == 5) region_slab(S, g, m->cmd_which, m->cmd_region, m->cmd_rc, m->cmd_host);
-      else if (kind == 6) accum_add_slab(S, g, m->cmd_accum, m->cmd_w);
-      else if (kind == 7) band_add_slab(S, g, m->cmd_band, m->cmd_bin);
-      else if (kind == 8) vband_add_slab(S, g, m->cmd_vband, m->cmd_bin);
-      else if (kind == 9) decim_add_slab(S, g, m->cmd_decim);
-      else if (kind == 10) vdecim_add_slab(S, g, m->cmd_vdecim);
+      else if (kind == 6) sample_slab(S, g, m->cmd_sample);
       else run_slabs(S, g, g + 1, local, n0, ns);
       S.bar.wait(local, S.err, S.bar_timeout);
       { std::lock_guard<std::mutex> lk(m->mu); m->done++; }
@@ -1093,76 +1054,120 @@ int pf_multi_get_region(pf_multi *m, int32_t which, const pf_region *r, void *ho
    return PF_OK;
 }
 
-// ---- field accumulators of a chain: one engine accumulator per slab that owns cells of the region, over region_part(...).local; get and set move a
-// slab's sums to and from its cells of the caller's [nchan][cells] array (offset out_off, rows out_pitch apart, channels `cells` apart).  Create, get,
-// set and destroy walk the slabs on the caller's thread (the engine calls choose their device); add is a command of the slab threads.
-static int accum_chain(pf_multi *m, const pf_accum *a, const char *what) { // G > 1: the handle is this chain's
-   if (!a) return fail("%s: null pf_accum", what);
-   if (a->chain != m) return fail("%s: the pf_accum belongs to another engine or chain", what);
+} // extern "C"
+
+// ---- region observers of a chain (pf_debug.h: field, band and vector band accumulators, decimating recorders scalar and vector): one engine observer per
+// slab that owns cells of the region, over region_part(...).local -- no cut code of their own; a difference across the cut reads the slab's ghost plane,
+// which between runs holds the neighbour's u^n (the exchange of the step that wrote u^n received it into that plane: pf_engine_halo_ptrs; a load scatters
+// the planes [xlo, xhi), ghost planes included).  get, set and read move a slab's rows to and from its cells of the caller's arrays (offset out_off, the
+// region's rows out_pitch apart, the device rows `cells` of the whole region apart).  Create, get, set, read and destroy walk the slabs on the caller's
+// thread (the engine calls choose their device); add is a command of the slab threads.  A recorder's parts take every sample together, so their counts and
+// frames agree and the chain keeps `count` and `rd` itself: what a full `cap` refuses and how many frames a read gives are decided here, before any slab is
+// asked.
+namespace {
+
+int failv(int code, const char *fmt, ...) {
+   char buf[512];
+   va_list ap;
+   va_start(ap, fmt);
+   vsnprintf(buf, sizeof buf, fmt, ap);
+   va_end(ap);
+   pf__set_error(buf);
+   return code;
+}
+template <typename H> int chain_mine(pf_multi *m, const H *a, const char *what) { // G > 1: the handle is this chain's
+   if (!a) return failv(PF_ERR_ARG, "%s: null %s", what, pfeng::obs_type[H::kind]);
+   if (a->chain != m) return failv(PF_ERR_ARG, "%s: the %s belongs to another engine or chain", what, pfeng::obs_type[H::kind]);
    return PF_OK;
 }
 // an error the slabs raised: a refusal (PF_ERR_STATE, PF_ERR_ARG) leaves every engine as it was and the chain usable
-static int accum_status(Shared &S) {
+int accum_status(Shared &S) {
    const int code = S.err.load();
    if (!code) return PF_OK;
    pf__set_error(S.err_msg.c_str());
    if (code == PF_ERR_STATE || code == PF_ERR_ARG) S.err.store(0);
    return code;
 }
+int raised(Shared &S) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+template <typename T> T *at(T *p, int64_t off) { return p ? p + off : nullptr; }
+int none() { return PF_OK; }
 #define PF_ACCUM_ENTER(what)                                                                                                        \
    if (!m) return fail("%s: null object", what);                                                                                    \
    Shared &S = m->S;                                                                                                                \
    if (S.only >= 0) { fail("%s: a one-rank cost model (pf_opts.only_slab) has no field of the scene", what); return PF_ERR_STATE; }
 
-int pf_multi_accum_create(pf_multi *m, const pf_region *r, int32_t nchan, int32_t depth, pf_accum **out) {
-   const char *what = "pf_multi_accum_create";
-   PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_accum_create(S.eng[0], r, nchan, depth, out);
+// check(rc): the kind's own check of the region against the SCENE; make_part(g, local, &part): the engine's create call for slab g (a bad count, index, tap or
+// coefficient: the first slab's message names it); destroy_part: the engine's destroy call
+template <typename H, typename Check, typename Make>
+int chain_create(pf_multi *m, const char *what, const pf_region *r, H **out, Check check, Make make_part, int (*destroy_part)(pf_engine *, H *)) {
+   Shared &S = m->S;
    if (!r) return fail("%s: null pf_region", what);
    if (!out) return fail("%s: null out", what);
    *out = nullptr;
    const int64_t N[3] = {m->sd->Nx, m->sd->Ny, m->sd->Nz};
-   char msg[256], full[320];
-   std::unique_ptr<pf_accum> a(new pf_accum());
-   if ((a->cells = pf_cut::region_check(r, N, a->rc, msg, sizeof msg)) < 0) { snprintf(full, sizeof full, "%s: %s", what, msg); return fail("%s", full); }
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   a->chain = m; a->region = *r; a->nchan = nchan;
+   char msg[256];
+   std::unique_ptr<H> a(new H());
+   if ((a->cells = pf_cut::region_check(r, N, a->rc, msg, sizeof msg)) < 0) return failv(PF_ERR_ARG, "%s: %s", what, msg);
+   if (const int rc = check(a->rc)) return rc;
+   if (S.err.load()) return raised(S);
+   a->chain = m; a->region = *r;
    a->part.assign((size_t)S.G, nullptr);
    for (int g = 0; g < S.G; g++) {
       const pf_cut::RegionPart p = pf_cut::region_part(*r, a->rc, S.slabs[g], S.along_z);
       if (p.empty) continue;
-      const int rc = pf_engine_accum_create(S.eng[g], &p.local, nchan, depth, &a->part[g]); // (nchan, depth out of range: the first slab's message names them)
+      const int rc = make_part(g, &p.local, &a->part[g]);
       if (rc) {
          const std::string keep = pf_last_error();
-         for (int h = 0; h < g; h++) if (a->part[h]) pf_engine_accum_destroy(S.eng[h], a->part[h]);
+         for (int h = 0; h < g; h++) if (a->part[h]) destroy_part(S.eng[h], a->part[h]);
          pf__set_error(keep.c_str());
          return rc;
       }
    }
-   m->accums.push_back(a.get());
+   m->observers.push_back(a.get());
    *out = a.release();
    return PF_OK;
 }
 
-int pf_multi_accum_add(pf_multi *m, pf_accum *a, const double *w) {
-   const char *what = "pf_multi_accum_add";
-   PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_accum_add(S.eng[0], a, w);
-   if (accum_chain(m, a, what)) return PF_ERR_ARG;
-   if (!w) return fail("%s: null weights", what);
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
+// the one-cell rule of the vector kinds against the SCENE's faces (a slab checks its part against its own planes, where a cut is no face)
+int scene_face_check(const char *what, const pf_simdata *sd, const pf_region *r, const int64_t *rc, int ncomp, const int32_t *comp) {
+   if (!comp || ncomp < 1 || ncomp > 4) return PF_OK; // (the first slab's message names it)
+   const int64_t N[3] = {sd->Nx, sd->Ny, sd->Nz};
+   bool lat = false; // a lattice difference (4 / 5 / 6) reads along all three axes; on a Cartesian scene the first slab refuses it by name
+   for (int k = 0; k < ncomp; k++) lat = lat || (comp[k] >= 4 && comp[k] <= 6);
+   for (int ax = 0; lat && sd->fcc_flag != 0 && ax < 3; ax++) {
+      const int64_t last = r->lo[ax] + (rc[ax] - 1) * r->stride[ax];
+      if (r->lo[ax] < 1 || last > N[ax] - 2)
+         return failv(PF_ERR_ARG, "%s: a lattice difference needs the region one cell clear of all six faces, along file %c too: pf_region.lo[%d] = %ld >= 1 and its last cell "
+                                  "%ld <= %ld", what, "xyz"[ax], ax, (long)r->lo[ax], (long)last, (long)N[ax] - 2);
+   }
+   for (int k = 0; k < ncomp; k++) {
+      const int ax = comp[k] - 1;
+      if (ax < 0 || ax > 2) continue;
+      const int64_t last = r->lo[ax] + (rc[ax] - 1) * r->stride[ax];
+      if (r->lo[ax] < 1 || last > N[ax] - 2)
+         return failv(PF_ERR_ARG, "%s: a difference along file %c needs the region one cell clear of both faces along %c: pf_region.lo[%d] = %ld >= 1 and its last cell %ld <= %ld",
+                      what, "xyz"[ax], "xyz"[ax], ax, (long)r->lo[ax], (long)last, (long)N[ax] - 2);
+   }
+   return PF_OK;
+}
+
+// pre(): the kind's refusals that need no engine (the bin range, null weights); late(): the recorders' cap refusal, after the slabs were asked;
+// add(engine, part): the engine's add call, its arguments held by value (a slab thread calls it)
+template <typename H, typename Pre, typename Late, typename Add> int chain_add(pf_multi *m, H *a, const char *what, Pre pre, Late late, Add add) {
+   Shared &S = m->S;
+   if (chain_mine(m, a, what)) return PF_ERR_ARG;
+   if (const int rc = pre()) return rc;
+   if (S.err.load()) return raised(S);
    // all or nothing: the slab threads are idle, so every engine can be asked here, before any of them takes the sample
    for (int g = 0; g < S.G; g++)
-      if (!pf__engine_between_runs(S.eng[g])) {
-         char b[256];
-         snprintf(b, sizeof b, "%s: slab %d is inside a pair or triple (u^{n+1} is not complete in memory): no slab took the sample; advance a step, or create the chain with "
-                               "PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES", what, g);
-         pf__set_error(b);
-         return PF_ERR_STATE;
-      }
-   if (m->one_thread) { for (int g = 0; g < S.G; g++) accum_add_slab(S, g, a, w); }
+      if (!pf__engine_between_runs(S.eng[g]))
+         return failv(PF_ERR_STATE, "%s: slab %d is inside a pair or triple (u^{n+1} is not complete in memory): no slab took the sample; advance a step, or create the chain with "
+                                    "PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES", what, g);
+   if (const int rc = late()) return rc;
+   const std::function<int(int)> sample = [&S, a, add](int g) { return a->part[g] ? add(S.eng[g], a->part[g]) : (int)PF_OK; };
+   if (m->one_thread) { for (int g = 0; g < S.G; g++) sample_slab(S, g, sample); }
    else {
-      { std::lock_guard<std::mutex> lk(m->mu); m->cmd_accum = a; m->cmd_w = w; }
+      { std::lock_guard<std::mutex> lk(m->mu); m->cmd_sample = sample; }
       post(m, 6, 0, 0);
       wait_done(m);
       if (m->broken && !S.err.load()) S.set_error(PF_ERR_HIP, "slab chain hung: a slab's host thread never came back");
@@ -1172,61 +1177,136 @@ int pf_multi_accum_add(pf_multi *m, pf_accum *a, const double *w) {
    return rc;
 }
 
-int pf_multi_accum_get(pf_multi *m, pf_accum *a, double *host) {
-   const char *what = "pf_multi_accum_get";
-   PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_accum_get(S.eng[0], a, host);
-   if (accum_chain(m, a, what)) return PF_ERR_ARG;
-   if (!host) return fail("%s: null host array", what);
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   for (int g = 0; g < S.G; g++) {
-      if (!a->part[g]) continue;
-      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
-      const int rc = pf__engine_accum_get_x(S.eng[g], a->part[g], host + p.out_off, p.out_pitch, a->cells);
-      if (rc) return rc;
-   }
-   return PF_OK;
-}
-
-int pf_multi_accum_set(pf_multi *m, pf_accum *a, const double *host, int64_t count) {
-   const char *what = "pf_multi_accum_set";
-   PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_accum_set(S.eng[0], a, host, count);
-   if (accum_chain(m, a, what)) return PF_ERR_ARG;
-   if (count < 0) return fail("%s: count < 0", what);
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   for (int g = 0; g < S.G; g++)
-      if (!pf__engine_between_runs(S.eng[g])) { fail("%s: a slab is inside a pair or triple: valid between passes only", what); return PF_ERR_STATE; }
-   for (int g = 0; g < S.G; g++) {
-      if (!a->part[g]) continue;
-      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
-      const int rc = pf__engine_accum_set_x(S.eng[g], a->part[g], host ? host + p.out_off : nullptr, p.out_pitch, a->cells, count);
-      if (rc) return rc;
-   }
-   a->count = count;
-   return PF_OK;
-}
-
-int pf_multi_accum_destroy(pf_multi *m, pf_accum *a) {
-   const char *what = "pf_multi_accum_destroy";
-   if (!m) return fail("%s: null object", what);
+// get, set, read, get_state, set_state: check(): the null and range checks of the caller's arguments; between: the slabs must stand between two passes
+// (what writes or marks as read; a get has no such test); rows(engine, part, out_off, out_pitch): the engine's call for a slab's part
+template <typename H, typename Check, typename Rows> int chain_rows(pf_multi *m, H *a, const char *what, bool between, Check check, Rows rows) {
    Shared &S = m->S;
-   if (S.G == 1) return pf_engine_accum_destroy(S.eng[0], a);
-   if (accum_chain(m, a, what)) return PF_ERR_ARG;
+   if (chain_mine(m, a, what)) return PF_ERR_ARG;
+   if (const int rc = check()) return rc;
+   if (S.err.load()) return raised(S);
+   for (int g = 0; between && g < S.G; g++)
+      if (!pf__engine_between_runs(S.eng[g])) return failv(PF_ERR_STATE, "%s: a slab is inside a pair or triple: valid between passes only", what);
+   for (int g = 0; g < S.G; g++) {
+      if (!a->part[g]) continue;
+      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
+      const int rc = rows(S.eng[g], a->part[g], p.out_off, p.out_pitch);
+      if (rc) return rc;
+   }
+   return PF_OK;
+}
+
+template <typename H> int chain_destroy(pf_multi *m, H *a, const char *what, int (*destroy_part)(pf_engine *, H *)) {
+   Shared &S = m->S;
+   if (chain_mine(m, a, what)) return PF_ERR_ARG;
    int rc = PF_OK;
    for (int g = 0; g < S.G; g++)
-      if (a->part[g] && S.eng[g]) { const int r1 = pf_engine_accum_destroy(S.eng[g], a->part[g]); if (r1 && !rc) rc = r1; }
-   m->accums.erase(std::find(m->accums.begin(), m->accums.end(), a));
+      if (a->part[g] && S.eng[g]) { const int r1 = destroy_part(S.eng[g], a->part[g]); if (r1 && !rc) rc = r1; }
+   m->observers.erase(std::find(m->observers.begin(), m->observers.end(), a));
    delete a;
    return rc;
 }
 
-// ---- band accumulators of a chain: the field accumulators' scheme.  A slab's rows of sums and of state land in the caller's arrays at out_off, the
-// region's rows out_pitch apart, the sum / state rows `cells` (of the whole region) apart.
-static int band_chain(pf_multi *m, const pf_bandacc *a, const char *what) {
-   if (!a) return fail("%s: null pf_bandacc", what);
-   if (a->chain != m) return fail("%s: the pf_bandacc belongs to another engine or chain", what);
+// the two kinds of band accumulator (H: pf_bandacc, pf_vbandacc) and of recorder (H: pf_decim -- scalar --, pf_vdecim): all but create
+template <typename H> int bands_add(pf_multi *m, H *a, const char *what, int64_t bin, int (*add)(pf_engine *, H *, int64_t)) {
+   return chain_add(m, a, what, [&] { return bin < -1 || bin >= a->nbin ? failv(PF_ERR_ARG, "%s: bin = %ld outside -1 .. %ld", what, (long)bin, (long)a->nbin - 1) : (int)PF_OK; },
+                    none, [=](pf_engine *e, H *part) { return add(e, part, bin); });
+}
+template <typename H> int bands_get(pf_multi *m, H *a, const char *what, double *sums, double *state, int (*get)(pf_engine *, H *, double *, double *, int64_t, int64_t)) {
+   return chain_rows(m, a, what, false, [&] { return sums ? (int)PF_OK : fail("%s: null sums array", what); },
+                     [&](pf_engine *e, H *part, int64_t off, int64_t pitch) { return get(e, part, at(sums, off), at(state, off), pitch, a->cells); });
+}
+template <typename H>
+int bands_set(pf_multi *m, H *a, const char *what, const double *sums, const double *state, int64_t count,
+              int (*set)(pf_engine *, H *, const double *, const double *, int64_t, int64_t, int64_t)) {
+   const int rc = chain_rows(m, a, what, true, [&] { return count < 0 ? fail("%s: count < 0", what) : (int)PF_OK; },
+                             [&](pf_engine *e, H *part, int64_t off, int64_t pitch) { return set(e, part, at(sums, off), at(state, off), pitch, a->cells, count); });
+   if (rc == PF_OK) a->count = count;
+   return rc;
+}
+template <typename H> int rec_add(pf_multi *m, H *a, const char *what, int (*add)(pf_engine *, H *)) {
+   return chain_add(m, a, what, none, [&] {
+      if (a->count % a->factor == 0 && (a->count + a->factor - 1) / a->factor - a->rd == a->cap)
+         return failv(PF_ERR_STATE, "%s: sample %ld would complete frame %ld while cap = %ld frames are complete and unread: read some first", what, (long)a->count,
+                      (long)(a->count / a->factor), (long)a->cap);
+      return (int)PF_OK;
+   }, add);
+}
+template <typename H> int rec_read(pf_multi *m, H *a, const char *what, double *frames, int64_t max_frames, int64_t *first, int64_t *nread) {
+   int64_t n = 0;
+   const int rc = chain_rows(m, a, what, true, [&] {
+      if (!first || !nread) return fail(!first ? "%s: null first" : "%s: null nread", what);
+      if (max_frames < 0) return fail("%s: max_frames < 0", what);
+      if (max_frames > 0 && !frames) return fail("%s: null frames array", what);
+      n = std::min(max_frames, (a->count + a->factor - 1) / a->factor - a->rd); // (the handle is this chain's: chain_rows has looked)
+      return (int)PF_OK;
+   }, [&](pf_engine *e, H *part, int64_t off, int64_t pitch) {
+      int64_t f1 = 0, n1 = 0;
+      const int r1 = pf__engine_rec_read_x(e, part, H::kind == pfeng::OBS_DECIM, at(frames, off), n, &f1, &n1, pitch, a->cells);
+      if (r1) return r1;
+      if (n1 != n || (n && f1 != a->rd)) return failv(PF_ERR_STATE, "%s: internal: a slab's frames are not the chain's", what);
+      return (int)PF_OK;
+   });
+   if (rc) return rc;
+   *first = a->rd;
+   *nread = n;
+   a->rd += n;
    return PF_OK;
+}
+template <typename H> int rec_get_state(pf_multi *m, H *a, const char *what, double *acc, double *state) {
+   return chain_rows(m, a, what, false, [&] { return acc ? (int)PF_OK : fail("%s: null acc array", what); }, [&](pf_engine *e, H *part, int64_t off, int64_t pitch) {
+      return pf__engine_rec_get_state_x(e, part, H::kind == pfeng::OBS_DECIM, at(acc, off), at(state, off), pitch, a->cells);
+   });
+}
+template <typename H> int rec_set_state(pf_multi *m, H *a, const char *what, const double *acc, const double *state, int64_t count) {
+   const int rc = chain_rows(m, a, what, true, [&] { return count < 0 ? fail("%s: count < 0", what) : (int)PF_OK; }, [&](pf_engine *e, H *part, int64_t off, int64_t pitch) {
+      return pf__engine_rec_set_state_x(e, part, H::kind == pfeng::OBS_DECIM, at(acc, off), at(state, off), pitch, a->cells, count);
+   });
+   if (rc) return rc;
+   a->count = count;
+   a->rd = (count + a->factor - 1) / a->factor;
+   return PF_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pf_multi_accum_create(pf_multi *m, const pf_region *r, int32_t nchan, int32_t depth, pf_accum **out) {
+   const char *what = "pf_multi_accum_create";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_accum_create(S.eng[0], r, nchan, depth, out);
+   const int rc = chain_create(m, what, r, out, [](const int64_t *) { return (int)PF_OK; },
+                               [&](int g, const pf_region *local, pf_accum **part) { return pf_engine_accum_create(S.eng[g], local, nchan, depth, part); }, pf_engine_accum_destroy);
+   if (rc == PF_OK) (*out)->nchan = nchan;
+   return rc;
+}
+int pf_multi_accum_add(pf_multi *m, pf_accum *a, const double *w) {
+   const char *what = "pf_multi_accum_add";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_accum_add(S.eng[0], a, w);
+   return chain_add(m, a, what, [&] { return w ? (int)PF_OK : fail("%s: null weights", what); }, none, [=](pf_engine *e, pf_accum *part) { return pf_engine_accum_add(e, part, w); });
+}
+int pf_multi_accum_get(pf_multi *m, pf_accum *a, double *host) {
+   const char *what = "pf_multi_accum_get";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_accum_get(S.eng[0], a, host);
+   return chain_rows(m, a, what, false, [&] { return host ? (int)PF_OK : fail("%s: null host array", what); },
+                     [&](pf_engine *e, pf_accum *part, int64_t off, int64_t pitch) { return pf__engine_accum_get_x(e, part, host + off, pitch, a->cells); });
+}
+int pf_multi_accum_set(pf_multi *m, pf_accum *a, const double *host, int64_t count) {
+   const char *what = "pf_multi_accum_set";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_accum_set(S.eng[0], a, host, count);
+   const int rc = chain_rows(m, a, what, true, [&] { return count < 0 ? fail("%s: count < 0", what) : (int)PF_OK; },
+                             [&](pf_engine *e, pf_accum *part, int64_t off, int64_t pitch) { return pf__engine_accum_set_x(e, part, at(host, off), pitch, a->cells, count); });
+   if (rc == PF_OK) a->count = count;
+   return rc;
+}
+int pf_multi_accum_destroy(pf_multi *m, pf_accum *a) {
+   const char *what = "pf_multi_accum_destroy";
+   if (!m) return fail("%s: null object", what);
+   if (m->S.G == 1) return pf_engine_accum_destroy(m->S.eng[0], a);
+   return chain_destroy(m, a, what, pf_engine_accum_destroy);
 }
 
 int pf_multi_bandacc_create(pf_multi *m, const pf_region *r, int32_t npre, const double *pre_sos, int32_t nband, int32_t nsec, const double *band_sos, int64_t nbin,
@@ -1234,120 +1314,32 @@ int pf_multi_bandacc_create(pf_multi *m, const pf_region *r, int32_t npre, const
    const char *what = "pf_multi_bandacc_create";
    PF_ACCUM_ENTER(what)
    if (S.G == 1) return pf_engine_bandacc_create(S.eng[0], r, npre, pre_sos, nband, nsec, band_sos, nbin, depth, out);
-   if (!r) return fail("%s: null pf_region", what);
-   if (!out) return fail("%s: null out", what);
-   *out = nullptr;
-   const int64_t N[3] = {m->sd->Nx, m->sd->Ny, m->sd->Nz};
-   char msg[256], full[320];
-   std::unique_ptr<pf_bandacc> a(new pf_bandacc());
-   if ((a->cells = pf_cut::region_check(r, N, a->rc, msg, sizeof msg)) < 0) { snprintf(full, sizeof full, "%s: %s", what, msg); return fail("%s", full); }
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   a->chain = m; a->region = *r; a->nbin = nbin;
-   a->part.assign((size_t)S.G, nullptr);
-   for (int g = 0; g < S.G; g++) {
-      const pf_cut::RegionPart p = pf_cut::region_part(*r, a->rc, S.slabs[g], S.along_z);
-      if (p.empty) continue;
-      const int rc = pf_engine_bandacc_create(S.eng[g], &p.local, npre, pre_sos, nband, nsec, band_sos, nbin, depth, &a->part[g]); // (a bad count or coefficient: the first slab's message names it)
-      if (rc) {
-         const std::string keep = pf_last_error();
-         for (int h = 0; h < g; h++) if (a->part[h]) pf_engine_bandacc_destroy(S.eng[h], a->part[h]);
-         pf__set_error(keep.c_str());
-         return rc;
-      }
-   }
-   m->bands.push_back(a.get());
-   *out = a.release();
-   return PF_OK;
+   const int rc = chain_create(m, what, r, out, [](const int64_t *) { return (int)PF_OK; }, [&](int g, const pf_region *local, pf_bandacc **part) {
+      return pf_engine_bandacc_create(S.eng[g], local, npre, pre_sos, nband, nsec, band_sos, nbin, depth, part);
+   }, pf_engine_bandacc_destroy);
+   if (rc == PF_OK) (*out)->nbin = nbin;
+   return rc;
 }
-
 int pf_multi_bandacc_add(pf_multi *m, pf_bandacc *a, int64_t bin) {
    const char *what = "pf_multi_bandacc_add";
    PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_bandacc_add(S.eng[0], a, bin);
-   if (band_chain(m, a, what)) return PF_ERR_ARG;
-   if (bin < -1 || bin >= a->nbin) {
-      char b[160];
-      snprintf(b, sizeof b, "%s: bin = %ld outside -1 .. %ld", what, (long)bin, (long)a->nbin - 1);
-      return fail("%s", b);
-   }
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   // all or nothing: the slab threads are idle, so every engine can be asked here, before any of them takes the sample
-   for (int g = 0; g < S.G; g++)
-      if (!pf__engine_between_runs(S.eng[g])) {
-         char b[256];
-         snprintf(b, sizeof b, "%s: slab %d is inside a pair or triple (u^{n+1} is not complete in memory): no slab took the sample; advance a step, or create the chain with "
-                               "PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES", what, g);
-         pf__set_error(b);
-         return PF_ERR_STATE;
-      }
-   if (m->one_thread) { for (int g = 0; g < S.G; g++) band_add_slab(S, g, a, bin); }
-   else {
-      { std::lock_guard<std::mutex> lk(m->mu); m->cmd_band = a; m->cmd_bin = bin; }
-      post(m, 7, 0, 0);
-      wait_done(m);
-      if (m->broken && !S.err.load()) S.set_error(PF_ERR_HIP, "slab chain hung: a slab's host thread never came back");
-   }
-   const int rc = accum_status(S);
-   if (rc == PF_OK) a->count++;
-   return rc;
+   return S.G == 1 ? pf_engine_bandacc_add(S.eng[0], a, bin) : bands_add(m, a, what, bin, pf_engine_bandacc_add);
 }
-
 int pf_multi_bandacc_get(pf_multi *m, pf_bandacc *a, double *sums, double *state) {
    const char *what = "pf_multi_bandacc_get";
    PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_bandacc_get(S.eng[0], a, sums, state);
-   if (band_chain(m, a, what)) return PF_ERR_ARG;
-   if (!sums) return fail("%s: null sums array", what);
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   for (int g = 0; g < S.G; g++) {
-      if (!a->part[g]) continue;
-      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
-      const int rc = pf__engine_bandacc_get_x(S.eng[g], a->part[g], sums + p.out_off, state ? state + p.out_off : nullptr, p.out_pitch, a->cells);
-      if (rc) return rc;
-   }
-   return PF_OK;
+   return S.G == 1 ? pf_engine_bandacc_get(S.eng[0], a, sums, state) : bands_get(m, a, what, sums, state, pf__engine_bandacc_get_x);
 }
-
 int pf_multi_bandacc_set(pf_multi *m, pf_bandacc *a, const double *sums, const double *state, int64_t count) {
    const char *what = "pf_multi_bandacc_set";
    PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_bandacc_set(S.eng[0], a, sums, state, count);
-   if (band_chain(m, a, what)) return PF_ERR_ARG;
-   if (count < 0) return fail("%s: count < 0", what);
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   for (int g = 0; g < S.G; g++)
-      if (!pf__engine_between_runs(S.eng[g])) { fail("%s: a slab is inside a pair or triple: valid between passes only", what); return PF_ERR_STATE; }
-   for (int g = 0; g < S.G; g++) {
-      if (!a->part[g]) continue;
-      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
-      const int rc = pf__engine_bandacc_set_x(S.eng[g], a->part[g], sums ? sums + p.out_off : nullptr, state ? state + p.out_off : nullptr, p.out_pitch, a->cells, count);
-      if (rc) return rc;
-   }
-   a->count = count;
-   return PF_OK;
+   return S.G == 1 ? pf_engine_bandacc_set(S.eng[0], a, sums, state, count) : bands_set(m, a, what, sums, state, count, pf__engine_bandacc_set_x);
 }
-
 int pf_multi_bandacc_destroy(pf_multi *m, pf_bandacc *a) {
    const char *what = "pf_multi_bandacc_destroy";
    if (!m) return fail("%s: null object", what);
-   Shared &S = m->S;
-   if (S.G == 1) return pf_engine_bandacc_destroy(S.eng[0], a);
-   if (band_chain(m, a, what)) return PF_ERR_ARG;
-   int rc = PF_OK;
-   for (int g = 0; g < S.G; g++)
-      if (a->part[g] && S.eng[g]) { const int r1 = pf_engine_bandacc_destroy(S.eng[g], a->part[g]); if (r1 && !rc) rc = r1; }
-   m->bands.erase(std::find(m->bands.begin(), m->bands.end(), a));
-   delete a;
-   return rc;
-}
-
-// ---- vector band accumulators of a chain: the band accumulators' scheme, no new cut code.  A slab's part is an engine object over
-// region_part(...).local; a difference across the cut reads the slab's ghost plane, which between runs holds the neighbour's u^n (the exchange of the
-// step that wrote u^n received it into that plane: pf_engine_halo_ptrs; a load scatters the planes [xlo, xhi), ghost planes included).
-static int vband_chain(pf_multi *m, const pf_vbandacc *a, const char *what) {
-   if (!a) return fail("%s: null pf_vbandacc", what);
-   if (a->chain != m) return fail("%s: the pf_vbandacc belongs to another engine or chain", what);
-   return PF_OK;
+   if (m->S.G == 1) return pf_engine_bandacc_destroy(m->S.eng[0], a);
+   return chain_destroy(m, a, what, pf_engine_bandacc_destroy);
 }
 
 int pf_multi_vband_create(pf_multi *m, const pf_region *r, int32_t ncomp, const int32_t *comp, int32_t npre, const double *pre_sos, int32_t nband, int32_t nsec,
@@ -1355,143 +1347,33 @@ int pf_multi_vband_create(pf_multi *m, const pf_region *r, int32_t ncomp, const 
    const char *what = "pf_multi_vband_create";
    PF_ACCUM_ENTER(what)
    if (S.G == 1) return pf_engine_vband_create(S.eng[0], r, ncomp, comp, npre, pre_sos, nband, nsec, band_sos, nprod, prod, nbin, depth, out);
-   if (!r) return fail("%s: null pf_region", what);
-   if (!out) return fail("%s: null out", what);
-   *out = nullptr;
-   const int64_t N[3] = {m->sd->Nx, m->sd->Ny, m->sd->Nz};
-   char msg[256], full[400];
-   std::unique_ptr<pf_vbandacc> a(new pf_vbandacc());
-   if ((a->cells = pf_cut::region_check(r, N, a->rc, msg, sizeof msg)) < 0) { snprintf(full, sizeof full, "%s: %s", what, msg); return fail("%s", full); }
-   // the one-cell rule against the SCENE's faces (a slab checks its part against its own planes, where a cut is no face)
-   if (comp && ncomp >= 1 && ncomp <= 4) {
-      bool lat = false; // a lattice difference (4 / 5 / 6) reads along all three axes; on a Cartesian scene the first slab refuses it by name
-      for (int k = 0; k < ncomp; k++) lat = lat || (comp[k] >= 4 && comp[k] <= 6);
-      for (int ax = 0; lat && m->sd->fcc_flag != 0 && ax < 3; ax++) {
-         const int64_t last = r->lo[ax] + (a->rc[ax] - 1) * r->stride[ax];
-         if (r->lo[ax] < 1 || last > N[ax] - 2) {
-            snprintf(full, sizeof full, "%s: a lattice difference needs the region one cell clear of all six faces, along file %c too: pf_region.lo[%d] = %ld >= 1 and its last cell "
-                                        "%ld <= %ld", what, "xyz"[ax], ax, (long)r->lo[ax], (long)last, (long)N[ax] - 2);
-            return fail("%s", full);
-         }
-      }
-      for (int k = 0; k < ncomp; k++) {
-         const int ax = comp[k] - 1;
-         if (ax < 0 || ax > 2) continue;
-         const int64_t last = r->lo[ax] + (a->rc[ax] - 1) * r->stride[ax];
-         if (r->lo[ax] < 1 || last > N[ax] - 2) {
-            snprintf(full, sizeof full, "%s: a difference along file %c needs the region one cell clear of both faces along %c: pf_region.lo[%d] = %ld >= 1 and its last cell %ld <= %ld",
-                     what, "xyz"[ax], "xyz"[ax], ax, (long)r->lo[ax], (long)last, (long)N[ax] - 2);
-            return fail("%s", full);
-         }
-      }
-   }
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   a->chain = m; a->region = *r; a->nbin = nbin;
-   a->part.assign((size_t)S.G, nullptr);
-   for (int g = 0; g < S.G; g++) {
-      const pf_cut::RegionPart p = pf_cut::region_part(*r, a->rc, S.slabs[g], S.along_z);
-      if (p.empty) continue;
-      const int rc = pf_engine_vband_create(S.eng[g], &p.local, ncomp, comp, npre, pre_sos, nband, nsec, band_sos, nprod, prod, nbin, depth, &a->part[g]); // (a bad count, index or coefficient: the first slab's message names it)
-      if (rc) {
-         const std::string keep = pf_last_error();
-         for (int h = 0; h < g; h++) if (a->part[h]) pf_engine_vband_destroy(S.eng[h], a->part[h]);
-         pf__set_error(keep.c_str());
-         return rc;
-      }
-   }
-   m->vbands.push_back(a.get());
-   *out = a.release();
-   return PF_OK;
+   const int rc = chain_create(m, what, r, out, [&](const int64_t *rc) { return scene_face_check(what, m->sd, r, rc, ncomp, comp); },
+                               [&](int g, const pf_region *local, pf_vbandacc **part) {
+                                  return pf_engine_vband_create(S.eng[g], local, ncomp, comp, npre, pre_sos, nband, nsec, band_sos, nprod, prod, nbin, depth, part);
+                               }, pf_engine_vband_destroy);
+   if (rc == PF_OK) (*out)->nbin = nbin;
+   return rc;
 }
-
 int pf_multi_vband_add(pf_multi *m, pf_vbandacc *a, int64_t bin) {
    const char *what = "pf_multi_vband_add";
    PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_vband_add(S.eng[0], a, bin);
-   if (vband_chain(m, a, what)) return PF_ERR_ARG;
-   if (bin < -1 || bin >= a->nbin) {
-      char b[160];
-      snprintf(b, sizeof b, "%s: bin = %ld outside -1 .. %ld", what, (long)bin, (long)a->nbin - 1);
-      return fail("%s", b);
-   }
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   // all or nothing: the slab threads are idle, so every engine can be asked here, before any of them takes the sample
-   for (int g = 0; g < S.G; g++)
-      if (!pf__engine_between_runs(S.eng[g])) {
-         char b[256];
-         snprintf(b, sizeof b, "%s: slab %d is inside a pair or triple (u^{n+1} is not complete in memory): no slab took the sample; advance a step, or create the chain with "
-                               "PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES", what, g);
-         pf__set_error(b);
-         return PF_ERR_STATE;
-      }
-   if (m->one_thread) { for (int g = 0; g < S.G; g++) vband_add_slab(S, g, a, bin); }
-   else {
-      { std::lock_guard<std::mutex> lk(m->mu); m->cmd_vband = a; m->cmd_bin = bin; }
-      post(m, 8, 0, 0);
-      wait_done(m);
-      if (m->broken && !S.err.load()) S.set_error(PF_ERR_HIP, "slab chain hung: a slab's host thread never came back");
-   }
-   const int rc = accum_status(S);
-   if (rc == PF_OK) a->count++;
-   return rc;
+   return S.G == 1 ? pf_engine_vband_add(S.eng[0], a, bin) : bands_add(m, a, what, bin, pf_engine_vband_add);
 }
-
 int pf_multi_vband_get(pf_multi *m, pf_vbandacc *a, double *sums, double *state) {
    const char *what = "pf_multi_vband_get";
    PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_vband_get(S.eng[0], a, sums, state);
-   if (vband_chain(m, a, what)) return PF_ERR_ARG;
-   if (!sums) return fail("%s: null sums array", what);
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   for (int g = 0; g < S.G; g++) {
-      if (!a->part[g]) continue;
-      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
-      const int rc = pf__engine_vband_get_x(S.eng[g], a->part[g], sums + p.out_off, state ? state + p.out_off : nullptr, p.out_pitch, a->cells);
-      if (rc) return rc;
-   }
-   return PF_OK;
+   return S.G == 1 ? pf_engine_vband_get(S.eng[0], a, sums, state) : bands_get(m, a, what, sums, state, pf__engine_vband_get_x);
 }
-
 int pf_multi_vband_set(pf_multi *m, pf_vbandacc *a, const double *sums, const double *state, int64_t count) {
    const char *what = "pf_multi_vband_set";
    PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_vband_set(S.eng[0], a, sums, state, count);
-   if (vband_chain(m, a, what)) return PF_ERR_ARG;
-   if (count < 0) return fail("%s: count < 0", what);
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   for (int g = 0; g < S.G; g++)
-      if (!pf__engine_between_runs(S.eng[g])) { fail("%s: a slab is inside a pair or triple: valid between passes only", what); return PF_ERR_STATE; }
-   for (int g = 0; g < S.G; g++) {
-      if (!a->part[g]) continue;
-      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
-      const int rc = pf__engine_vband_set_x(S.eng[g], a->part[g], sums ? sums + p.out_off : nullptr, state ? state + p.out_off : nullptr, p.out_pitch, a->cells, count);
-      if (rc) return rc;
-   }
-   a->count = count;
-   return PF_OK;
+   return S.G == 1 ? pf_engine_vband_set(S.eng[0], a, sums, state, count) : bands_set(m, a, what, sums, state, count, pf__engine_vband_set_x);
 }
-
 int pf_multi_vband_destroy(pf_multi *m, pf_vbandacc *a) {
    const char *what = "pf_multi_vband_destroy";
    if (!m) return fail("%s: null object", what);
-   Shared &S = m->S;
-   if (S.G == 1) return pf_engine_vband_destroy(S.eng[0], a);
-   if (vband_chain(m, a, what)) return PF_ERR_ARG;
-   int rc = PF_OK;
-   for (int g = 0; g < S.G; g++)
-      if (a->part[g] && S.eng[g]) { const int r1 = pf_engine_vband_destroy(S.eng[g], a->part[g]); if (r1 && !rc) rc = r1; }
-   m->vbands.erase(std::find(m->vbands.begin(), m->vbands.end(), a));
-   delete a;
-   return rc;
-}
-
-// ---- decimating recorders of a chain: the band accumulators' scheme, no new cut code.  A slab's part is an engine object over region_part(...).local;
-// the parts take every sample together, so their counts and frames agree and the chain keeps `count` and `rd` itself: what a full `cap` refuses and
-// how many frames a read gives are decided here, before any slab is asked.
-static int decim_chain(pf_multi *m, const pf_decim *a, const char *what) {
-   if (!a) return fail("%s: null pf_decim", what);
-   if (a->chain != m) return fail("%s: the pf_decim belongs to another engine or chain", what);
-   return PF_OK;
+   if (m->S.G == 1) return pf_engine_vband_destroy(m->S.eng[0], a);
+   return chain_destroy(m, a, what, pf_engine_vband_destroy);
 }
 
 int pf_multi_decim_create(pf_multi *m, const pf_region *r, int32_t npre, const double *pre_sos, int32_t ntap, const double *taps, int32_t factor, int64_t cap,
@@ -1499,150 +1381,37 @@ int pf_multi_decim_create(pf_multi *m, const pf_region *r, int32_t npre, const d
    const char *what = "pf_multi_decim_create";
    PF_ACCUM_ENTER(what)
    if (S.G == 1) return pf_engine_decim_create(S.eng[0], r, npre, pre_sos, ntap, taps, factor, cap, depth, out);
-   if (!r) return fail("%s: null pf_region", what);
-   if (!out) return fail("%s: null out", what);
-   *out = nullptr;
-   const int64_t N[3] = {m->sd->Nx, m->sd->Ny, m->sd->Nz};
-   char msg[256], full[320];
-   std::unique_ptr<pf_decim> a(new pf_decim());
-   if ((a->cells = pf_cut::region_check(r, N, a->rc, msg, sizeof msg)) < 0) { snprintf(full, sizeof full, "%s: %s", what, msg); return fail("%s", full); }
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   a->chain = m; a->region = *r; a->factor = factor; a->cap = cap;
-   a->part.assign((size_t)S.G, nullptr);
-   for (int g = 0; g < S.G; g++) {
-      const pf_cut::RegionPart p = pf_cut::region_part(*r, a->rc, S.slabs[g], S.along_z);
-      if (p.empty) continue;
-      const int rc = pf_engine_decim_create(S.eng[g], &p.local, npre, pre_sos, ntap, taps, factor, cap, depth, &a->part[g]); // (a bad count, tap or coefficient: the first slab's message names it)
-      if (rc) {
-         const std::string keep = pf_last_error();
-         for (int h = 0; h < g; h++) if (a->part[h]) pf_engine_decim_destroy(S.eng[h], a->part[h]);
-         pf__set_error(keep.c_str());
-         return rc;
-      }
-   }
-   m->decims.push_back(a.get());
-   *out = a.release();
-   return PF_OK;
+   const int rc = chain_create(m, what, r, out, [](const int64_t *) { return (int)PF_OK; }, [&](int g, const pf_region *local, pf_decim **part) {
+      return pf_engine_decim_create(S.eng[g], local, npre, pre_sos, ntap, taps, factor, cap, depth, part);
+   }, pf_engine_decim_destroy);
+   if (rc == PF_OK) { (*out)->factor = factor; (*out)->cap = cap; }
+   return rc;
 }
-
 int pf_multi_decim_add(pf_multi *m, pf_decim *a) {
    const char *what = "pf_multi_decim_add";
    PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_decim_add(S.eng[0], a);
-   if (decim_chain(m, a, what)) return PF_ERR_ARG;
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   // all or nothing: the slab threads are idle, so every engine can be asked here, before any of them takes the sample
-   for (int g = 0; g < S.G; g++)
-      if (!pf__engine_between_runs(S.eng[g])) {
-         char b[256];
-         snprintf(b, sizeof b, "%s: slab %d is inside a pair or triple (u^{n+1} is not complete in memory): no slab took the sample; advance a step, or create the chain with "
-                               "PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES", what, g);
-         pf__set_error(b);
-         return PF_ERR_STATE;
-      }
-   if (a->count % a->factor == 0 && (a->count + a->factor - 1) / a->factor - a->rd == a->cap) {
-      char b[256];
-      snprintf(b, sizeof b, "%s: sample %ld would complete frame %ld while cap = %ld frames are complete and unread: read some first", what, (long)a->count,
-               (long)(a->count / a->factor), (long)a->cap);
-      pf__set_error(b);
-      return PF_ERR_STATE;
-   }
-   if (m->one_thread) { for (int g = 0; g < S.G; g++) decim_add_slab(S, g, a); }
-   else {
-      { std::lock_guard<std::mutex> lk(m->mu); m->cmd_decim = a; }
-      post(m, 9, 0, 0);
-      wait_done(m);
-      if (m->broken && !S.err.load()) S.set_error(PF_ERR_HIP, "slab chain hung: a slab's host thread never came back");
-   }
-   const int rc = accum_status(S);
-   if (rc == PF_OK) a->count++;
-   return rc;
+   return S.G == 1 ? pf_engine_decim_add(S.eng[0], a) : rec_add(m, a, what, pf_engine_decim_add);
 }
-
 int pf_multi_decim_read(pf_multi *m, pf_decim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread) {
    const char *what = "pf_multi_decim_read";
    PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_decim_read(S.eng[0], a, frames, max_frames, first, nread);
-   if (decim_chain(m, a, what)) return PF_ERR_ARG;
-   if (!first || !nread) return fail(!first ? "%s: null first" : "%s: null nread", what);
-   if (max_frames < 0) return fail("%s: max_frames < 0", what);
-   if (max_frames > 0 && !frames) return fail("%s: null frames array", what);
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   for (int g = 0; g < S.G; g++)
-      if (!pf__engine_between_runs(S.eng[g])) { fail("%s: a slab is inside a pair or triple: valid between passes only", what); return PF_ERR_STATE; }
-   const int64_t n = std::min(max_frames, (a->count + a->factor - 1) / a->factor - a->rd);
-   for (int g = 0; g < S.G; g++) {
-      if (!a->part[g]) continue;
-      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
-      int64_t f1 = 0, n1 = 0;
-      const int rc = pf__engine_decim_read_x(S.eng[g], a->part[g], frames ? frames + p.out_off : nullptr, n, &f1, &n1, p.out_pitch, a->cells);
-      if (rc) return rc;
-      if (n1 != n || (n && f1 != a->rd)) { fail("%s: internal: a slab's frames are not the chain's", what); return PF_ERR_STATE; }
-   }
-   *first = a->rd;
-   *nread = n;
-   a->rd += n;
-   return PF_OK;
+   return S.G == 1 ? pf_engine_decim_read(S.eng[0], a, frames, max_frames, first, nread) : rec_read(m, a, what, frames, max_frames, first, nread);
 }
-
 int pf_multi_decim_get_state(pf_multi *m, pf_decim *a, double *acc, double *state) {
    const char *what = "pf_multi_decim_get_state";
    PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_decim_get_state(S.eng[0], a, acc, state);
-   if (decim_chain(m, a, what)) return PF_ERR_ARG;
-   if (!acc) return fail("%s: null acc array", what);
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   for (int g = 0; g < S.G; g++) {
-      if (!a->part[g]) continue;
-      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
-      const int rc = pf__engine_decim_get_state_x(S.eng[g], a->part[g], acc + p.out_off, state ? state + p.out_off : nullptr, p.out_pitch, a->cells);
-      if (rc) return rc;
-   }
-   return PF_OK;
+   return S.G == 1 ? pf_engine_decim_get_state(S.eng[0], a, acc, state) : rec_get_state(m, a, what, acc, state);
 }
-
 int pf_multi_decim_set_state(pf_multi *m, pf_decim *a, const double *acc, const double *state, int64_t count) {
    const char *what = "pf_multi_decim_set_state";
    PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_decim_set_state(S.eng[0], a, acc, state, count);
-   if (decim_chain(m, a, what)) return PF_ERR_ARG;
-   if (count < 0) return fail("%s: count < 0", what);
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   for (int g = 0; g < S.G; g++)
-      if (!pf__engine_between_runs(S.eng[g])) { fail("%s: a slab is inside a pair or triple: valid between passes only", what); return PF_ERR_STATE; }
-   for (int g = 0; g < S.G; g++) {
-      if (!a->part[g]) continue;
-      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
-      const int rc = pf__engine_decim_set_state_x(S.eng[g], a->part[g], acc ? acc + p.out_off : nullptr, state ? state + p.out_off : nullptr, p.out_pitch, a->cells, count);
-      if (rc) return rc;
-   }
-   a->count = count;
-   a->rd = (count + a->factor - 1) / a->factor;
-   return PF_OK;
+   return S.G == 1 ? pf_engine_decim_set_state(S.eng[0], a, acc, state, count) : rec_set_state(m, a, what, acc, state, count);
 }
-
 int pf_multi_decim_destroy(pf_multi *m, pf_decim *a) {
    const char *what = "pf_multi_decim_destroy";
    if (!m) return fail("%s: null object", what);
-   Shared &S = m->S;
-   if (S.G == 1) return pf_engine_decim_destroy(S.eng[0], a);
-   if (decim_chain(m, a, what)) return PF_ERR_ARG;
-   int rc = PF_OK;
-   for (int g = 0; g < S.G; g++)
-      if (a->part[g] && S.eng[g]) { const int r1 = pf_engine_decim_destroy(S.eng[g], a->part[g]); if (r1 && !rc) rc = r1; }
-   m->decims.erase(std::find(m->decims.begin(), m->decims.end(), a));
-   delete a;
-   return rc;
-}
-
-// ---- vector decimating recorders of a chain: the per-slab parts as the vector band accumulators' (region_part(...).local; a difference across the cut
-// reads the slab's ghost plane; the one-cell rule against the SCENE's faces is checked here), everything else as the decimating recorders': the chain
-// keeps `count` and `rd`, and what a full `cap` refuses and how many frames a read gives are decided before any slab is asked.  A slab's rows of
-// frames [n][ncomp][cells], acc [ncomp][P][cells] and state [ncomp][npre][2][cells] are all one region's cells apart.
-static int vdecim_chain(pf_multi *m, const pf_vdecim *a, const char *what) {
-   if (!a) return fail("%s: null pf_vdecim", what);
-   if (a->chain != m) return fail("%s: the pf_vdecim belongs to another engine or chain", what);
-   return PF_OK;
+   if (m->S.G == 1) return pf_engine_decim_destroy(m->S.eng[0], a);
+   return chain_destroy(m, a, what, pf_engine_decim_destroy);
 }
 
 int pf_multi_vdecim_create(pf_multi *m, const pf_region *r, int32_t ncomp, const int32_t *comp, int32_t npre, const double *pre_sos, int32_t ntap, const double *taps,
@@ -1650,163 +1419,38 @@ int pf_multi_vdecim_create(pf_multi *m, const pf_region *r, int32_t ncomp, const
    const char *what = "pf_multi_vdecim_create";
    PF_ACCUM_ENTER(what)
    if (S.G == 1) return pf_engine_vdecim_create(S.eng[0], r, ncomp, comp, npre, pre_sos, ntap, taps, factor, cap, depth, out);
-   if (!r) return fail("%s: null pf_region", what);
-   if (!out) return fail("%s: null out", what);
-   *out = nullptr;
-   const int64_t N[3] = {m->sd->Nx, m->sd->Ny, m->sd->Nz};
-   char msg[256], full[400];
-   std::unique_ptr<pf_vdecim> a(new pf_vdecim());
-   if ((a->cells = pf_cut::region_check(r, N, a->rc, msg, sizeof msg)) < 0) { snprintf(full, sizeof full, "%s: %s", what, msg); return fail("%s", full); }
-   // the one-cell rule against the SCENE's faces (a slab checks its part against its own planes, where a cut is no face): pf_multi_vband_create's
-   if (comp && ncomp >= 1 && ncomp <= 4) {
-      bool lat = false;
-      for (int k = 0; k < ncomp; k++) lat = lat || (comp[k] >= 4 && comp[k] <= 6);
-      for (int ax = 0; lat && m->sd->fcc_flag != 0 && ax < 3; ax++) {
-         const int64_t last = r->lo[ax] + (a->rc[ax] - 1) * r->stride[ax];
-         if (r->lo[ax] < 1 || last > N[ax] - 2) {
-            snprintf(full, sizeof full, "%s: a lattice difference needs the region one cell clear of all six faces, along file %c too: pf_region.lo[%d] = %ld >= 1 and its last cell "
-                                        "%ld <= %ld", what, "xyz"[ax], ax, (long)r->lo[ax], (long)last, (long)N[ax] - 2);
-            return fail("%s", full);
-         }
-      }
-      for (int k = 0; k < ncomp; k++) {
-         const int ax = comp[k] - 1;
-         if (ax < 0 || ax > 2) continue;
-         const int64_t last = r->lo[ax] + (a->rc[ax] - 1) * r->stride[ax];
-         if (r->lo[ax] < 1 || last > N[ax] - 2) {
-            snprintf(full, sizeof full, "%s: a difference along file %c needs the region one cell clear of both faces along %c: pf_region.lo[%d] = %ld >= 1 and its last cell %ld <= %ld",
-                     what, "xyz"[ax], "xyz"[ax], ax, (long)r->lo[ax], (long)last, (long)N[ax] - 2);
-            return fail("%s", full);
-         }
-      }
-   }
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   a->chain = m; a->region = *r; a->factor = factor; a->cap = cap;
-   a->part.assign((size_t)S.G, nullptr);
-   for (int g = 0; g < S.G; g++) {
-      const pf_cut::RegionPart p = pf_cut::region_part(*r, a->rc, S.slabs[g], S.along_z);
-      if (p.empty) continue;
-      const int rc = pf_engine_vdecim_create(S.eng[g], &p.local, ncomp, comp, npre, pre_sos, ntap, taps, factor, cap, depth, &a->part[g]); // (a bad count, tap or coefficient: the first slab's message names it)
-      if (rc) {
-         const std::string keep = pf_last_error();
-         for (int h = 0; h < g; h++) if (a->part[h]) pf_engine_vdecim_destroy(S.eng[h], a->part[h]);
-         pf__set_error(keep.c_str());
-         return rc;
-      }
-   }
-   m->vdecims.push_back(a.get());
-   *out = a.release();
-   return PF_OK;
+   const int rc = chain_create(m, what, r, out, [&](const int64_t *rc) { return scene_face_check(what, m->sd, r, rc, ncomp, comp); },
+                               [&](int g, const pf_region *local, pf_vdecim **part) {
+                                  return pf_engine_vdecim_create(S.eng[g], local, ncomp, comp, npre, pre_sos, ntap, taps, factor, cap, depth, part);
+                               }, pf_engine_vdecim_destroy);
+   if (rc == PF_OK) { (*out)->factor = factor; (*out)->cap = cap; }
+   return rc;
 }
-
 int pf_multi_vdecim_add(pf_multi *m, pf_vdecim *a) {
    const char *what = "pf_multi_vdecim_add";
    PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_vdecim_add(S.eng[0], a);
-   if (vdecim_chain(m, a, what)) return PF_ERR_ARG;
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   // all or nothing: the slab threads are idle, so every engine can be asked here, before any of them takes the sample
-   for (int g = 0; g < S.G; g++)
-      if (!pf__engine_between_runs(S.eng[g])) {
-         char b[256];
-         snprintf(b, sizeof b, "%s: slab %d is inside a pair or triple (u^{n+1} is not complete in memory): no slab took the sample; advance a step, or create the chain with "
-                               "PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES", what, g);
-         pf__set_error(b);
-         return PF_ERR_STATE;
-      }
-   if (a->count % a->factor == 0 && (a->count + a->factor - 1) / a->factor - a->rd == a->cap) {
-      char b[256];
-      snprintf(b, sizeof b, "%s: sample %ld would complete frame %ld while cap = %ld frames are complete and unread: read some first", what, (long)a->count,
-               (long)(a->count / a->factor), (long)a->cap);
-      pf__set_error(b);
-      return PF_ERR_STATE;
-   }
-   if (m->one_thread) { for (int g = 0; g < S.G; g++) vdecim_add_slab(S, g, a); }
-   else {
-      { std::lock_guard<std::mutex> lk(m->mu); m->cmd_vdecim = a; }
-      post(m, 10, 0, 0);
-      wait_done(m);
-      if (m->broken && !S.err.load()) S.set_error(PF_ERR_HIP, "slab chain hung: a slab's host thread never came back");
-   }
-   const int rc = accum_status(S);
-   if (rc == PF_OK) a->count++;
-   return rc;
+   return S.G == 1 ? pf_engine_vdecim_add(S.eng[0], a) : rec_add(m, a, what, pf_engine_vdecim_add);
 }
-
 int pf_multi_vdecim_read(pf_multi *m, pf_vdecim *a, double *frames, int64_t max_frames, int64_t *first, int64_t *nread) {
    const char *what = "pf_multi_vdecim_read";
    PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_vdecim_read(S.eng[0], a, frames, max_frames, first, nread);
-   if (vdecim_chain(m, a, what)) return PF_ERR_ARG;
-   if (!first || !nread) return fail(!first ? "%s: null first" : "%s: null nread", what);
-   if (max_frames < 0) return fail("%s: max_frames < 0", what);
-   if (max_frames > 0 && !frames) return fail("%s: null frames array", what);
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   for (int g = 0; g < S.G; g++)
-      if (!pf__engine_between_runs(S.eng[g])) { fail("%s: a slab is inside a pair or triple: valid between passes only", what); return PF_ERR_STATE; }
-   const int64_t n = std::min(max_frames, (a->count + a->factor - 1) / a->factor - a->rd);
-   for (int g = 0; g < S.G; g++) {
-      if (!a->part[g]) continue;
-      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
-      int64_t f1 = 0, n1 = 0;
-      const int rc = pf__engine_vdecim_read_x(S.eng[g], a->part[g], frames ? frames + p.out_off : nullptr, n, &f1, &n1, p.out_pitch, a->cells);
-      if (rc) return rc;
-      if (n1 != n || (n && f1 != a->rd)) { fail("%s: internal: a slab's frames are not the chain's", what); return PF_ERR_STATE; }
-   }
-   *first = a->rd;
-   *nread = n;
-   a->rd += n;
-   return PF_OK;
+   return S.G == 1 ? pf_engine_vdecim_read(S.eng[0], a, frames, max_frames, first, nread) : rec_read(m, a, what, frames, max_frames, first, nread);
 }
-
 int pf_multi_vdecim_get_state(pf_multi *m, pf_vdecim *a, double *acc, double *state) {
    const char *what = "pf_multi_vdecim_get_state";
    PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_vdecim_get_state(S.eng[0], a, acc, state);
-   if (vdecim_chain(m, a, what)) return PF_ERR_ARG;
-   if (!acc) return fail("%s: null acc array", what);
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   for (int g = 0; g < S.G; g++) {
-      if (!a->part[g]) continue;
-      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
-      const int rc = pf__engine_vdecim_get_state_x(S.eng[g], a->part[g], acc + p.out_off, state ? state + p.out_off : nullptr, p.out_pitch, a->cells);
-      if (rc) return rc;
-   }
-   return PF_OK;
+   return S.G == 1 ? pf_engine_vdecim_get_state(S.eng[0], a, acc, state) : rec_get_state(m, a, what, acc, state);
 }
-
 int pf_multi_vdecim_set_state(pf_multi *m, pf_vdecim *a, const double *acc, const double *state, int64_t count) {
    const char *what = "pf_multi_vdecim_set_state";
    PF_ACCUM_ENTER(what)
-   if (S.G == 1) return pf_engine_vdecim_set_state(S.eng[0], a, acc, state, count);
-   if (vdecim_chain(m, a, what)) return PF_ERR_ARG;
-   if (count < 0) return fail("%s: count < 0", what);
-   if (S.err.load()) { pf__set_error(S.err_msg.c_str()); return S.err.load(); }
-   for (int g = 0; g < S.G; g++)
-      if (!pf__engine_between_runs(S.eng[g])) { fail("%s: a slab is inside a pair or triple: valid between passes only", what); return PF_ERR_STATE; }
-   for (int g = 0; g < S.G; g++) {
-      if (!a->part[g]) continue;
-      const pf_cut::RegionPart p = pf_cut::region_part(a->region, a->rc, S.slabs[g], S.along_z);
-      const int rc = pf__engine_vdecim_set_state_x(S.eng[g], a->part[g], acc ? acc + p.out_off : nullptr, state ? state + p.out_off : nullptr, p.out_pitch, a->cells, count);
-      if (rc) return rc;
-   }
-   a->count = count;
-   a->rd = (count + a->factor - 1) / a->factor;
-   return PF_OK;
+   return S.G == 1 ? pf_engine_vdecim_set_state(S.eng[0], a, acc, state, count) : rec_set_state(m, a, what, acc, state, count);
 }
-
 int pf_multi_vdecim_destroy(pf_multi *m, pf_vdecim *a) {
    const char *what = "pf_multi_vdecim_destroy";
    if (!m) return fail("%s: null object", what);
-   Shared &S = m->S;
-   if (S.G == 1) return pf_engine_vdecim_destroy(S.eng[0], a);
-   if (vdecim_chain(m, a, what)) return PF_ERR_ARG;
-   int rc = PF_OK;
-   for (int g = 0; g < S.G; g++)
-      if (a->part[g] && S.eng[g]) { const int r1 = pf_engine_vdecim_destroy(S.eng[g], a->part[g]); if (r1 && !rc) rc = r1; }
-   m->vdecims.erase(std::find(m->vdecims.begin(), m->vdecims.end(), a));
-   delete a;
-   return rc;
+   if (m->S.G == 1) return pf_engine_vdecim_destroy(m->S.eng[0], a);
+   return chain_destroy(m, a, what, pf_engine_vdecim_destroy);
 }
 
 int pf_multi_get_info(pf_multi *m, pf_multi_info *info) {
@@ -1853,11 +1497,7 @@ void pf_multi_destroy(pf_multi *m) {
    }
    if (S.G == 1) { if (S.eng[0]) { pf_engine_destroy(S.eng[0]); S.eng[0] = nullptr; } }
    else for (int g = 0; g < S.G; g++) destroy_slab(S, g);
-   for (pf_accum *a : m->accums) delete a; // (the slabs' parts went with their engines)
-   for (pf_bandacc *a : m->bands) delete a;
-   for (pf_vbandacc *a : m->vbands) delete a;
-   for (pf_decim *a : m->decims) delete a;
-   for (pf_vdecim *a : m->vdecims) delete a;
+   for (pf_observer *a : m->observers) delete a; // (the slabs' parts went with their engines)
    for (auto &c : S.comm) if (c) { g_rccl.CommDestroy(c); c = nullptr; }
    delete m;
 }

@@ -1,31 +1,48 @@
-// pf_vdecim.h -- device side of the vector decimating recorders (include/pffdtd_hip.h: pf_vdecim): per cell of a region, up to four COMPONENTS of
-// the field -- the cell itself or a difference, sampled exactly as a vector band accumulator samples them (pf_vband.h: k_region_cut, k_region_diff,
-// k_region_lat into the component's ring slot) -- run through their own second-order sections (k_vband_pre, unchanged) and then, each on its own,
-// through pf_decim.h's FIR in ARRIVAL order, every D-th output kept: a B-format impulse response per cell.
-//    x_k = double(component k);  x_k -> pre sections of k;  per slot p:  acc[k][p] = acc[k][p] + h[tap] * x_k      product, then sum: NO fma
+// pf_vdecim.h -- device side of the decimating recorders, scalar and vector (include/pffdtd_hip.h: pf_decim, pf_vdecim): per cell of a region, up
+// to four COMPONENTS of the field -- the cell itself or a difference, sampled exactly as a vector band accumulator samples them (pf_vband.h:
+// k_region_cut, k_region_diff, k_region_lat into the component's ring slot) -- run through their own npre second-order sections (k_vband_pre,
+// unchanged) and then, each on its own, through a linear-phase FIR of ntap taps h, of which every D-th output is kept: an impulse response per
+// cell, in B-format with four components.  The scalar recorder (pf_decim) is the one component 0.
+//    frame m = sum_k h[k] x[m D - k]                     (the terms before sample 0 are not added)
+// The sum is formed in ARRIVAL order.  P = ceil(ntap / D) outputs are in flight at any time, one per slot of `acc`; the sample with index n meets
+// tap = m D - n of the output m that slot p carries (q = ceil(n / D), m = q + ((p - q) mod P)):
+//    x_k = double(component k);  x_k -> pre sections of k;  per slot p:  acc[k][p] = acc[k][p] + h[tap] * x_k      product rounded to double, then the sum: NO fma
 //    tap == 0:  frame m of component k = acc[k][p];  acc[k][p] = +0.0
-// The tap a pending sample meets in a slot and the frame row it completes (plan, orow: pf_decim.h) depend on neither the cell nor the component: the
-// host works them out once per sample.
-//   acc    double [ncomp][P][cstride]           cstride = the cell count rounded up to a multiple of 2
+// so a numpy loop over time gives the same bits at every ring depth.  m, the tap and the frame's device row depend on neither the cell nor the
+// component: the host works them out once per pending sample and slot and uploads them with every fold (plan, orow; as pf_band.h's bins):
+//   acc    double [ncomp][P][cstride]           cstride = the cell count rounded up to a multiple of 2: every row starts 16-byte aligned
 //   frames double [cap][ncomp][cstride]         frame m of component k in row (m mod cap) * ncomp + k: n frames are n * ncomp consecutive rows
-//   st     double [ncomp][npre * 2][cstride]    taps double [ntap]     coef double [ncomp][npre][5]
-//   ring   Real   [ncomp][depth][cells]         xpre double [ncomp][depth][cstride] (npre > 0 only)      plan, orow int32 [depth][P]
+//   st     double [ncomp][npre * 2][cstride]    taps double [ntap] (uploaded once, at creation)     coef double [ncomp][npre][5]
+//   ring   Real   [ncomp][depth][cells]         the region's components at the samples not folded in yet
+//   xpre   double [ncomp][depth][cstride]       npre > 0 only: the pending samples after the sections
+//   plan   int32  [depth][P]                    the tap a pending sample meets in a slot, or -1 (the slot idles: tap >= ntap)
+//   orow   int32  [depth][P]                    the frame (m mod cap) the sample completes in a slot, or -1
 // A fold of NT pending samples is k_vband_pre<Real, NT> (npre > 0; grid.y = the component) and ONE k_vdecim_fold<In, NT, S> on a grid of
-// (cdiv(cdiv(cells, 2), 256), cdiv(P, S), ncomp): blockIdx.z is the component, everything else is k_decim_fold -- a thread owns two adjacent cells
-// (16-byte loads and stores), holds its group's S slots in registers and walks the NT samples in order; plan, orow and taps are scalar loads.  No
-// atomics, no LDS, no scratch (tools/kernel_resources.py k_vdecim).  64-bit indices, every access guarded by the cell count.  Components and slots
-// are independent of each other, so neither the grid's z nor S changes a bit.
+// (cdiv(cdiv(cells, 2), 256), cdiv(P, S), ncomp): groups of S slots in parallel, blockIdx.z is the component.  A thread owns two adjacent cells
+// (16-byte loads and stores, lanes along cells: whole lines), loads and widens its NT inputs once, holds its group's S slots in registers -- acc
+// loaded once, stored once -- and walks the NT samples in order; a completing slot stores its pair into the frame's row and restarts from +0.0.
+// plan[...], orow[...] and taps[...] do not depend on the lane: scalar loads.  No atomics, no LDS, no scratch (tools/kernel_resources.py
+// k_vdecim).  64-bit indices, every access guarded by the cell count (c even and c < cells, so c + 1 < cstride).  The padding cell of an odd
+// count filters zeros.  Components and slots are independent of each other, so neither the grid's z nor S changes a bit.
 //
+// PF_DECIM_SLOTS (S) and PF_DECIM_DEFAULT_DEPTH: tools/field_recording_cost.py (profiles/field_recording.txt, measured with one component).
 // PF_VDECIM_DEFAULT_DEPTH: the fastest of the depths 1, 4, 8, 16 for four components on the plane cases of tools/field_recording_cost.py --axes
-// (profiles/field_vector_recording.txt); it equals the scalar recorder's.
+// (profiles/field_vector_recording.txt); the two agree.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-#include "pf_decim.h"
-
 namespace pf {
 
+constexpr int PF_DECIM_MAX_TAPS = 4096;
+constexpr int PF_DECIM_MAX_FACTOR = 64;
+constexpr int PF_DECIM_MAX_SLOTS = 128; // P
+constexpr int PF_DECIM_MAX_DEPTH = 16;
+constexpr int PF_DECIM_DEFAULT_DEPTH = 16;
+#ifndef PF_DECIM_SLOTS_N // (tools/field_recording_cost.py builds the library once per candidate)
+#define PF_DECIM_SLOTS_N 4
+#endif
+constexpr int PF_DECIM_SLOTS = PF_DECIM_SLOTS_N; // S
 constexpr int PF_VDECIM_DEFAULT_DEPTH = PF_DECIM_DEFAULT_DEPTH;
 
 // grid: (cdiv(cdiv(cells, 2), 256), cdiv(P, S), ncomp) blocks of 256 threads.  x: the ring (xstride = cells) or xpre (xstride = cstride) at the first of

@@ -265,12 +265,16 @@ def _check(rc):
         raise e
 
 
+def _region(what, lo, hi, stride):
+    try:
+        return PfRegion((ctypes.c_int64 * 3)(*[int(v) for v in lo]), (ctypes.c_int64 * 3)(*[int(v) for v in hi]), (ctypes.c_int64 * 3)(*[int(v) for v in stride]))
+    except TypeError as e:
+        raise PfError(f"{what}: lo, hi and stride are three integers each ({e})")
+
+
 def _get_region(call, handle, dtype, which, lo, hi, stride):
     """pf_engine_get_region / pf_multi_get_region -> ndarray of shape counts, the cells lo + k * stride < hi in FILE coordinates x, y, z"""
-    try:
-        r = PfRegion((ctypes.c_int64 * 3)(*[int(v) for v in lo]), (ctypes.c_int64 * 3)(*[int(v) for v in hi]), (ctypes.c_int64 * 3)(*[int(v) for v in stride]))
-    except TypeError as e:
-        raise PfError(f"get_region: lo, hi and stride are three integers each ({e})")
+    r = _region("get_region", lo, hi, stride)
     counts = (ctypes.c_int64 * 3)()
     if lib().pf_region_count(ctypes.byref(r), counts) < 0:
         _check(1)  # (PF_ERR_ARG: pf_last_error names the field)
@@ -279,18 +283,53 @@ def _get_region(call, handle, dtype, which, lo, hi, stride):
     return a
 
 
-class Accumulator:
+class _Observer:
+    """What the region observers share: the owner that made them, the C handle `_a`, the C functions `_f` of the owner's prefix, count and close.
+    An owner closed first took its observers with it: the handle is dead."""
+    _kind = ""  # pf_engine_<_kind>_* / pf_multi_<_kind>_*
+    _handle = ""  # pf_<_handle>_count
+    _noun = "accumulator"
+
+    def _bind(self, owner, prefix, names):
+        L = lib()
+        self._owner, self._f = owner, {k: getattr(L, f"{prefix}_{self._kind}_{k}") for k in names}
+        self._a = ctypes.c_void_p()
+        return L
+
+    def _number(self, name):
+        if not (self._a.value and self._alive()):
+            raise PfError(f"{type(self).__name__}.{name}: the {self._noun} or its owner is closed")
+        return int(getattr(lib(), f"pf_{self._handle}_{name}")(self._a))
+
+    @property
+    def count(self):
+        """samples added so far, or the count given to set / set_state"""
+        return self._number("count")
+
+    def _alive(self):
+        return bool(getattr(self._owner, "_h", None) and self._owner._h.value)
+
+    def close(self):
+        if getattr(self, "_a", None) and self._a.value:
+            if self._alive():
+                _check(self._f["destroy"](self._owner._h, self._a))
+            self._a = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Accumulator(_Observer):
     """Running sums of a region of the field on the device (pf_engine_accum_* / pf_multi_accum_*): acc[m] += w[m] * double(u^n) at every add.
     Made by HipEngine.accumulator / HipMulti.accumulator; it lives no longer than the object that made it."""
+    _kind, _handle = "accum", "accum"
 
     def __init__(self, owner, prefix, lo, hi, stride, nchan, depth):
-        try:
-            r = PfRegion((ctypes.c_int64 * 3)(*[int(v) for v in lo]), (ctypes.c_int64 * 3)(*[int(v) for v in hi]), (ctypes.c_int64 * 3)(*[int(v) for v in stride]))
-        except TypeError as e:
-            raise PfError(f"accumulator: lo, hi and stride are three integers each ({e})")
-        L = lib()
-        self._owner, self._f = owner, {k: getattr(L, f"{prefix}_accum_{k}") for k in ("create", "add", "get", "set", "destroy")}
-        self._a = ctypes.c_void_p()
+        r = _region("accumulator", lo, hi, stride)
+        L = self._bind(owner, prefix, ("create", "add", "get", "set", "destroy"))
         _check(self._f["create"](owner._h, ctypes.byref(r), int(nchan), int(depth), ctypes.byref(self._a)))
         counts = (ctypes.c_int64 * 3)()
         L.pf_region_count(ctypes.byref(r), counts)
@@ -318,28 +357,6 @@ class Accumulator:
                 raise PfError(f"Accumulator.set: {a.size} sums, the accumulator holds {int(np.prod(self.shape))}")
         _check(self._f["set"](self._owner._h, self._a, None if a is None else a.ctypes.data_as(ctypes.c_void_p), int(count)))
 
-    @property
-    def count(self):
-        """samples added so far, or the count given to set"""
-        if not (self._a.value and self._alive()):
-            raise PfError("Accumulator.count: the accumulator or its owner is closed")
-        return int(lib().pf_accum_count(self._a))
-
-    def _alive(self):  # (an owner closed first took its accumulators with it: the handle is dead)
-        return bool(getattr(self._owner, "_h", None) and self._owner._h.value)
-
-    def close(self):
-        if getattr(self, "_a", None) and self._a.value:
-            if self._alive():
-                _check(self._f["destroy"](self._owner._h, self._a))
-            self._a = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _sos5(name, sos, lead):
     """scipy-style rows [.., 6] (b0 b1 b2 a0 a1 a2, a0 = 1) -> float64 [.., 5] as the C ABI takes them; `lead` leading dimensions"""
@@ -353,16 +370,14 @@ def _sos5(name, sos, lead):
     return np.ascontiguousarray(a[..., [0, 1, 2, 4, 5]])
 
 
-class BandAccumulator:
+class BandAccumulator(_Observer):
     """Per cell of a region, on the device (pf_engine_bandacc_* / pf_multi_bandacc_*): u^n through the shared sections pre_sos [npre, 6], then per
     band through band_sos [nband, nsec, 6] (scipy's sos rows, a0 = 1), squared and summed into time bin `bin` at every add(bin).
     Made by HipEngine.band_accumulator / HipMulti.band_accumulator; it lives no longer than the object that made it."""
+    _kind, _handle = "bandacc", "bandacc"
 
     def __init__(self, owner, prefix, lo, hi, stride, pre_sos, band_sos, nbin, depth):
-        try:
-            r = PfRegion((ctypes.c_int64 * 3)(*[int(v) for v in lo]), (ctypes.c_int64 * 3)(*[int(v) for v in hi]), (ctypes.c_int64 * 3)(*[int(v) for v in stride]))
-        except TypeError as e:
-            raise PfError(f"band_accumulator: lo, hi and stride are three integers each ({e})")
+        r = _region("band_accumulator", lo, hi, stride)
         pre = _sos5("pre_sos", pre_sos, 1)
         b = np.asarray(band_sos, dtype=np.float64)
         if b.ndim == 3 and b.shape[1] == 0:  # nband bands without sections: plain squares of what the shared sections give
@@ -370,9 +385,7 @@ class BandAccumulator:
         else:
             band = _sos5("band_sos", band_sos, 2)
             nband = band.shape[0] if band.ndim == 3 else 0
-        L = lib()
-        self._owner, self._f = owner, {k: getattr(L, f"{prefix}_bandacc_{k}") for k in ("create", "add", "get", "set", "destroy")}
-        self._a = ctypes.c_void_p()
+        L = self._bind(owner, prefix, ("create", "add", "get", "set", "destroy"))
         self.npre, self.nband, self.nsec, self.nbin = int(pre.shape[0]), int(nband), int(band.shape[1]) if band.ndim == 3 else 0, int(nbin)
         vp = ctypes.c_void_p
         _check(self._f["create"](owner._h, ctypes.byref(r), self.npre, pre.ctypes.data_as(vp) if pre.size else None, self.nband, self.nsec,
@@ -405,42 +418,18 @@ class BandAccumulator:
             arrs.append(a)
         _check(self._f["set"](self._owner._h, self._a, *[None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p) for a in arrs], int(count)))
 
-    @property
-    def count(self):
-        """samples added so far, or the count given to set"""
-        if not (self._a.value and self._alive()):
-            raise PfError("BandAccumulator.count: the accumulator or its owner is closed")
-        return int(lib().pf_bandacc_count(self._a))
 
-    def _alive(self):
-        return bool(getattr(self._owner, "_h", None) and self._owner._h.value)
-
-    def close(self):
-        if getattr(self, "_a", None) and self._a.value:
-            if self._alive():
-                _check(self._f["destroy"](self._owner._h, self._a))
-            self._a = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class VectorBandAccumulator:
+class VectorBandAccumulator(_Observer):
     """Per cell of a region, on the device (pf_engine_vband_* / pf_multi_vband_*): the components `comp` (0: the cell of u^n, 1 / 2 / 3: its central
     difference along file x / y / z on a Cartesian grid, 4 / 5 / 6: the lattice difference along file x / y / z of an FCC grid -- the four pair
     differences over the eight FCC neighbours at +-1 along the axis, in stored coordinates, ~ 8 h du/da) through their own sections pre_sos [ncomp, npre, 6], then per band through band_sos [nband, nsec, 6] (scipy's
     sos rows, a0 = 1; state per component); the products prod [nprod, 3] -- rows (i, j, mode), mode 1: the absolute value -- of two filtered
     components are summed into time bin `bin` at every add(bin).
     Made by HipEngine.vector_band_accumulator / HipMulti.vector_band_accumulator; it lives no longer than the object that made it."""
+    _kind, _handle = "vband", "vbandacc"
 
     def __init__(self, owner, prefix, lo, hi, stride, comp, pre_sos, band_sos, prod, nbin, depth):
-        try:
-            r = PfRegion((ctypes.c_int64 * 3)(*[int(v) for v in lo]), (ctypes.c_int64 * 3)(*[int(v) for v in hi]), (ctypes.c_int64 * 3)(*[int(v) for v in stride]))
-        except TypeError as e:
-            raise PfError(f"vector_band_accumulator: lo, hi and stride are three integers each ({e})")
+        r = _region("vector_band_accumulator", lo, hi, stride)
         comp = np.ascontiguousarray(np.asarray(comp).reshape(-1), dtype=np.int32)
         prod = np.asarray([] if prod is None else prod)
         if prod.size and (prod.ndim != 2 or prod.shape[1] != 3):
@@ -459,9 +448,7 @@ class VectorBandAccumulator:
         else:
             band = _sos5("band_sos", band_sos, 2)
             nband = band.shape[0] if band.ndim == 3 else 0
-        L = lib()
-        self._owner, self._f = owner, {k: getattr(L, f"{prefix}_vband_{k}") for k in ("create", "add", "get", "set", "destroy")}
-        self._a = ctypes.c_void_p()
+        L = self._bind(owner, prefix, ("create", "add", "get", "set", "destroy"))
         self.ncomp, self.nprod, self.npre, self.nband, self.nbin = int(comp.size), int(prod.shape[0]), int(pre.shape[1]), int(nband), int(nbin)
         self.nsec = int(band.shape[1]) if band.ndim == 3 else 0
         vp = ctypes.c_void_p
@@ -496,46 +483,20 @@ class VectorBandAccumulator:
             arrs.append(a)
         _check(self._f["set"](self._owner._h, self._a, *[None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p) for a in arrs], int(count)))
 
-    @property
-    def count(self):
-        """samples added so far, or the count given to set"""
-        if not (self._a.value and self._alive()):
-            raise PfError("VectorBandAccumulator.count: the accumulator or its owner is closed")
-        return int(lib().pf_vbandacc_count(self._a))
 
-    def _alive(self):
-        return bool(getattr(self._owner, "_h", None) and self._owner._h.value)
-
-    def close(self):
-        if getattr(self, "_a", None) and self._a.value:
-            if self._alive():
-                _check(self._f["destroy"](self._owner._h, self._a))
-            self._a = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DecimatingRecorder:
+class DecimatingRecorder(_Observer):
     """Per cell of a region, on the device (pf_engine_decim_* / pf_multi_decim_*): every sample u^n through the shared sections pre_sos [npre, 6] and a
     FIR of taps `taps`, every `factor`-th output kept as a frame; up to `cap` frames wait on the device for read().
     Made by HipEngine.decimating_recorder / HipMulti.decimating_recorder; it lives no longer than the object that made it."""
+    _kind, _handle, _noun = "decim", "decim", "recorder"
 
     def __init__(self, owner, prefix, lo, hi, stride, pre_sos, taps, factor, cap, depth):
-        try:
-            r = PfRegion((ctypes.c_int64 * 3)(*[int(v) for v in lo]), (ctypes.c_int64 * 3)(*[int(v) for v in hi]), (ctypes.c_int64 * 3)(*[int(v) for v in stride]))
-        except TypeError as e:
-            raise PfError(f"decimating_recorder: lo, hi and stride are three integers each ({e})")
+        r = _region("decimating_recorder", lo, hi, stride)
         pre = _sos5("pre_sos", pre_sos, 1)
         h = np.ascontiguousarray([] if taps is None else taps, dtype=np.float64)
         if h.ndim != 1:
             raise PfError(f"decimating_recorder: taps has shape {h.shape}: a vector of ntap values is expected")
-        L = lib()
-        self._owner, self._f = owner, {k: getattr(L, f"{prefix}_decim_{k}") for k in ("create", "add", "read", "get_state", "set_state", "destroy")}
-        self._a = ctypes.c_void_p()
+        L = self._bind(owner, prefix, ("create", "add", "read", "get_state", "set_state", "destroy"))
         self.npre, self.ntap, self.factor = int(pre.shape[0]), int(h.size), int(factor)
         self.cap = int(cap) if cap else 64  # frames kept on the device between two reads
         vp = ctypes.c_void_p
@@ -577,35 +538,10 @@ class DecimatingRecorder:
             arrs.append(a)
         _check(self._f["set_state"](self._owner._h, self._a, *[None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p) for a in arrs], int(count)))
 
-    def _number(self, name):
-        if not (self._a.value and self._alive()):
-            raise PfError(f"DecimatingRecorder.{name}: the recorder or its owner is closed")
-        return int(getattr(lib(), f"pf_decim_{name}")(self._a))
-
-    @property
-    def count(self):
-        """samples added so far, or the count given to set_state"""
-        return self._number("count")
-
     @property
     def pending(self):
         """frames complete and not yet read"""
         return self._number("pending")
-
-    def _alive(self):
-        return bool(getattr(self._owner, "_h", None) and self._owner._h.value)
-
-    def close(self):
-        if getattr(self, "_a", None) and self._a.value:
-            if self._alive():
-                _check(self._f["destroy"](self._owner._h, self._a))
-            self._a = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class VectorDecimatingRecorder(DecimatingRecorder):
@@ -614,12 +550,10 @@ class VectorDecimatingRecorder(DecimatingRecorder):
     own sections pre_sos [ncomp, npre, 6], then each through the FIR `taps`, every `factor`-th output kept as a frame [ncomp, c0, c1, c2]; up to
     `cap` frames wait on the device for read().  add, set_state, count, pending and close are a DecimatingRecorder's.
     Made by HipEngine.vector_decimating_recorder / HipMulti.vector_decimating_recorder; it lives no longer than the object that made it."""
+    _kind, _handle = "vdecim", "vdecim"
 
     def __init__(self, owner, prefix, lo, hi, stride, comp, pre_sos, taps, factor, cap, depth):
-        try:
-            r = PfRegion((ctypes.c_int64 * 3)(*[int(v) for v in lo]), (ctypes.c_int64 * 3)(*[int(v) for v in hi]), (ctypes.c_int64 * 3)(*[int(v) for v in stride]))
-        except TypeError as e:
-            raise PfError(f"vector_decimating_recorder: lo, hi and stride are three integers each ({e})")
+        r = _region("vector_decimating_recorder", lo, hi, stride)
         comp = np.ascontiguousarray(np.asarray(comp).reshape(-1), dtype=np.int32)
         p = np.asarray([] if pre_sos is None else pre_sos, dtype=np.float64)
         if p.size == 0:
@@ -631,9 +565,7 @@ class VectorDecimatingRecorder(DecimatingRecorder):
         h = np.ascontiguousarray([] if taps is None else taps, dtype=np.float64)
         if h.ndim != 1:
             raise PfError(f"vector_decimating_recorder: taps has shape {h.shape}: a vector of ntap values is expected")
-        L = lib()
-        self._owner, self._f = owner, {k: getattr(L, f"{prefix}_vdecim_{k}") for k in ("create", "add", "read", "get_state", "set_state", "destroy")}
-        self._a = ctypes.c_void_p()
+        L = self._bind(owner, prefix, ("create", "add", "read", "get_state", "set_state", "destroy"))
         self.ncomp, self.comp = int(comp.size), tuple(int(c) for c in comp)
         self.npre, self.ntap, self.factor = int(pre.shape[1]), int(h.size), int(factor)
         self.cap = int(cap) if cap else 64  # frames kept on the device between two reads
@@ -654,11 +586,6 @@ class VectorDecimatingRecorder(DecimatingRecorder):
         first, nread = ctypes.c_int64(), ctypes.c_int64()
         _check(self._f["read"](self._owner._h, self._a, out.ctypes.data_as(ctypes.c_void_p) if out.size else None, n, ctypes.byref(first), ctypes.byref(nread)))
         return int(first.value), out[:nread.value]
-
-    def _number(self, name):
-        if not (self._a.value and self._alive()):
-            raise PfError(f"VectorDecimatingRecorder.{name}: the recorder or its owner is closed")
-        return int(getattr(lib(), f"pf_vdecim_{name}")(self._a))
 
 
 def device_count():

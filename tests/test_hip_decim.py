@@ -1,5 +1,5 @@
-"""GPU: decimating recorders (pf_engine_decim_* / pf_multi_decim_*, kernels k_band_pre / k_decim_fold): per cell of a region every sample u^n runs
-through shared second-order sections and a FIR whose every D-th output is kept as a frame, on the device.
+"""GPU: decimating recorders (pf_engine_decim_* / pf_multi_decim_*, the vector recorder's kernels k_vband_pre / k_vdecim_fold with one component):
+per cell of a region every sample u^n runs through shared second-order sections and a FIR whose every D-th output is kept as a frame, on the device.
 
 The bar: frames, the outputs in flight and the sections' state are bit for bit those of `Decim` (tests/test_recordings_host.py: a numpy loop over
 time, vectorised over cells, written with the contract's lines -- the FIR in arrival order, product and sum each rounded to double once) over the

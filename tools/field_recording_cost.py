@@ -6,7 +6,7 @@ against a band accumulator on the same region and against the engine's own steps
   tools/field_recording_cost.py [--size 512] [--reps 7] [--out profiles/field_recording.txt]
   tools/field_recording_cost.py --axes [--size 512] [--reps 7] [--out profiles/field_vector_recording.txt]
 
-S is a compile-time constant of csrc/pf_decim.h, so the library is built once per candidate S in {1, 4, 8} (tools/_decim_cost/, kept out of the
+S is a compile-time constant of csrc/pf_vdecim.h, so the library is built once per candidate S in {1, 4, 8} (tools/_decim_cost/, kept out of the
 history; S = 4 is the product library as built) and every S is measured in a process of its own, started under a time limit of its own; the first
 that fails ends the measurement.  In each process, on a shoebox size^3, fp32 (synth.shoebox), once stored in file order and once with the x and z
 axes exchanged:
@@ -16,11 +16,12 @@ axes exchanged:
     median of --reps repetitions in which the depths and a band accumulator of 6 octave bands (pf_bandacc, its default depth) ALTERNATE;
   * beside them the same engine's wall time per single step (run(n, 1)) without any recorder call in between.
 No threshold is fixed in advance.  Recorded at the end: the (S, depth) with the smallest sum of medians over the plane cases, which PF_DECIM_SLOTS
-and PF_DECIM_DEFAULT_DEPTH (csrc/pf_decim.h) are to equal.  Needs a GPU; there is no fallback.
+and PF_DECIM_DEFAULT_DEPTH (csrc/pf_vdecim.h) are to equal.  Needs a GPU; there is no fallback.
 
 --axes measures the VECTOR decimating recorders instead (pf_engine_vdecim_add, csrc/pf_vdecim.h), with the product library alone, in one process
 under one time limit: the same engine, filters and method; the regions keep one cell clear of the faces (the plane is the (size - 2)^2 interior of
-the z plane), as a difference needs; per region and filter the scalar recorder, the vector recorder with comp = [0] and the one with the 4
+the z plane), as a difference needs; per region and filter the scalar recorder (the vector recorder's code with the one component 0, entered through
+pf_engine_decim_*), the vector recorder with comp = [0] and the one with the 4
 components 0, 1, 2, 3 (the sections directional.gradient_sections gives: 3 per component), each at depths 1, 4, 8 and 16, all twelve ALTERNATING.
 Recorded at the end: the depth with the smallest sum of the 4-component medians over the plane cases, which PF_VDECIM_DEFAULT_DEPTH
 (csrc/pf_vdecim.h) is to equal.
