@@ -13,10 +13,10 @@ high-pass where diff is not set; nothing for lowcut_hz = 0 without diff -- as th
 exactly one half at both edges (the prewarped bilinear map); a band whose upper edge reaches 1 / (2 Ts) is refused by name.
 
 Every step from `first` on is a sample -- there is no `every`: a recursive filter over skipped samples is another filter.  The bin of step n is
-(n - first) // bin_steps with bin_steps = round(bin_ms * 1e-3 / Ts).  A chain answers only while no slab is inside a pair or triple, and a
-sample is never shifted: a chain that is sampled is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES.
+(n - first) // bin_steps with bin_steps = round(bin_ms * 1e-3 / Ts).  FieldDecay is a field_output.FieldOutput: a sample is never shifted, a chain
+that is sampled is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES, and take, write and the rules of a resume are described there.
 
-The file (write(): written to a temporary name and moved into place with os.replace) holds
+The file holds
     regions  int64 [R, 9]      bands  float64 [B]      Ts  float64      sampling  int64 [3] = first, bin_steps, count (samples so far)
     pre_sos  float64 [npre, 6]      band_sos  float64 [B, nsec, 6]      (scipy's rows)
     r{i:03d}_E      float64 [B, nbin, c0, c1, c2] of region i: sums * infac^2 (the square of the factor SimData.rescale_output applies to u_out)
@@ -25,13 +25,11 @@ With resume_at (the step a resumed run continues at) the file must match in regi
 count must be the number of sample steps below resume_at; otherwise it is refused with the field's name.
 The command line's --decay-bands is parsed here: host code, no device.
 """
-import os
-
 import numpy as np
 from scipy.signal import bilinear_zpk, butter, zpk2sos
 
 from . import h5io
-from .engine import PfError
+from .field_output import FieldOutput
 
 
 def parse_bands(spec):
@@ -70,124 +68,80 @@ def band_sections(Ts, bands_hz, order):
     return np.ascontiguousarray(np.stack(out), dtype=np.float64)
 
 
-class FieldDecay:
-    def __init__(self, path, sd, regions, bands_hz, bin_ms, first=0, order=3, lowcut_hz=10.0, lowcut_order=4, resume_at=None):
-        self.path, self.sd = os.fspath(path), sd
-        self.regions = [tuple(tuple(int(v) for v in t) for t in r) for r in regions]
+class BandOutput(FieldOutput):
+    """what the decay maps and the directional maps share: octave bands, time bins, a sum and a filter state per region.  A kind sets `sections`
+    and `holder` (the words of the pre_sos refusal, the observer's name) and writes its scaled sums (`_write_scaled`)."""
+    holds, observers_noun = "sums", "accumulators"
+    accs = property(lambda self: self.observers)
+
+    def _bands_and_bins(self, bands_hz, bin_ms, order):
+        """bands, bin_steps, nbin and their refusals"""
+        who = type(self).__name__
         self.bands = np.ascontiguousarray(bands_hz, dtype=np.float64).reshape(-1)
-        self.first, self.Ts = int(first), float(sd.Ts)
         self.bin_steps = int(round(float(bin_ms) * 1e-3 / self.Ts))
         if self.first < 0 or not self.regions or self.bands.size == 0 or int(order) < 1:
-            raise ValueError("FieldDecay: at least one region and one band, first >= 0, order >= 1")
+            raise ValueError(f"{who}: at least one region and one band, first >= 0, order >= 1")
         if self.bands.size > 16 or int(order) > 8:
-            raise ValueError(f"FieldDecay: bands: {self.bands.size} bands of order {order}, a band accumulator holds 16 of 8 sections")
+            raise ValueError(f"{who}: bands: {self.bands.size} bands of order {order}, a {self.holder} holds 16 of 8 sections")
         if self.bin_steps < 1:
-            raise ValueError(f"FieldDecay: bin_ms: {bin_ms} ms is less than half a step of {self.Ts * 1e3:g} ms")
-        self.pre_sos = pre_sections(self.Ts, bool(getattr(sd, "diff", False)), float(lowcut_hz), int(lowcut_order))
-        self.band_sos = band_sections(self.Ts, self.bands, int(order))
-        self.nbin = max(1, -(-(sd.Nt - self.first) // self.bin_steps))
-        self.table = np.array([lo + hi + st for lo, hi, st in self.regions], dtype=np.int64).reshape(-1, 9)
-        self.accs, self._restore = None, None
-        if resume_at is not None:
-            self._restore = self._read_matching(int(resume_at))
-
-    # ---- the sample steps ----
-    def next_step(self, n):
-        """the first step >= n at which a sample is due (it may lie at or past Nt: no sample then)"""
-        return max(n, self.first)
-
-    def due(self, n):
-        return self.first <= n < self.sd.Nt
-
-    def samples_below(self, n):
-        """how many sample steps lie below step n"""
-        return max(0, n - self.first)
+            raise ValueError(f"{who}: bin_ms: {bin_ms} ms is less than half a step of {self.Ts * 1e3:g} ms")
+        self.nbin = max(1, -(-(self.sd.Nt - self.first) // self.bin_steps))
 
     def bin_of(self, n):
         return (n - self.first) // self.bin_steps
 
-    # ---- the sums ----
-    def attach(self, obj):
-        """one band accumulator per region on obj (a HipEngine or a HipMulti); a resumed run's sums and filter state go into them"""
-        if self.accs is not None:
-            return
-        self.accs = [obj.band_accumulator(lo, hi, st, pre_sos=self.pre_sos, band_sos=self.band_sos, nbin=self.nbin) for lo, hi, st in self.regions]
-        if self._restore is not None:
-            count, sums, state = self._restore
-            for a, e, s in zip(self.accs, sums, state):
-                a.set(e, s, count)
-            self._restore = None
+    def _sample(self, n):
+        return (self.bin_of(n),)
 
-    @property
-    def count(self):
-        if self.accs is None:
-            return self._restore[0] if self._restore is not None else 0
-        return self.accs[0].count
+    def _restore_observer(self, a, i, count, sums, state):
+        a.set(sums[i], state[i], count)
 
-    def take(self, obj, n):
-        """the sample of step n (due(n)) -- never of another step"""
-        if not self.due(n):
-            raise ValueError(f"FieldDecay.take: no sample is due at step {n} (first {self.first}, Nt {self.sd.Nt})")
-        self.attach(obj)
-        try:
-            for a in self.accs:
-                a.add(self.bin_of(n))
-        except PfError as e:
-            if e.code != 4:  # (PF_ERR_STATE: a slab inside a pair or triple; no slab took the sample)
-                raise
-            err = PfError(f"field decay: step {n} cannot be sampled, a slab is inside a blocked pass there, and a sample is never shifted: "
-                          f"create the chain with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES ({e})")
-            err.code = 4
-            raise err
-        return n
+    def _write_region(self, path, i, a):
+        e, s = a.get()
+        h5io.write(path, f"r{i:03d}_sums", e)
+        h5io.write(path, f"r{i:03d}_state", s)
+        self._write_scaled(path, i, e * (self.sd.infac * self.sd.infac))
 
-    def write(self):
-        """the file as it stands: every region's sums and filter state so far"""
-        if self.accs is None:
-            raise ValueError("FieldDecay.write: no accumulators yet (attach or take first)")
-        tmp = self.path + ".tmp"
-        h5io.write(tmp, "regions", self.table, append=False)
-        h5io.write(tmp, "bands", self.bands)
-        h5io.write(tmp, "Ts", np.float64(self.Ts))
-        h5io.write(tmp, "sampling", np.array([self.first, self.bin_steps, self.count], dtype=np.int64))
-        h5io.write(tmp, "pre_sos", self.pre_sos if self.pre_sos.size else np.zeros((1, 6)))  # (no shared section: one row of zeros)
-        h5io.write(tmp, "npre", np.int64(self.pre_sos.shape[0]))
-        h5io.write(tmp, "band_sos", self.band_sos)
-        for i, a in enumerate(self.accs):
-            e, s = a.get()
-            h5io.write(tmp, f"r{i:03d}_sums", e)
-            h5io.write(tmp, f"r{i:03d}_state", s)
-            h5io.write(tmp, f"r{i:03d}_E", e * (self.sd.infac * self.sd.infac))
-        os.replace(tmp, self.path)
+    def _band_checks(self, f):
+        """the rows of `_checks` from Ts on"""
+        return [*self._same_clock(f), self._asked("bin_steps", f["sampling"][1], self.bin_steps),
+                ("pre_sos", np.array_equal(f["pre_sos"], self.pre_sos), f"the file's sums went through other {self.sections}"),
+                ("band_sos", np.array_equal(f["band_sos"], self.band_sos), "the file's sums went through other band filters (order)")]
 
-    def close(self):
-        for a in self.accs or []:
-            a.close()
-        self.accs = None
-
-    def _read_matching(self, resume_at):
-        """(count, [raw sums per region], [filter state per region]) of the file a resumed run continues, or ValueError naming the field that differs"""
-        if not os.path.exists(self.path):
-            raise ValueError(f"{self.path}: no decay file to resume from")
-        f = read(self.path, raw=True)
-        if not np.array_equal(f["regions"], self.table):
-            raise ValueError(f"{self.path}: regions: the file holds the sums of other regions")
-        if not np.array_equal(f["bands"], self.bands):
-            raise ValueError(f"{self.path}: bands: the file holds the sums of other bands")
-        if f["Ts"] != self.Ts:
-            raise ValueError(f"{self.path}: Ts: {f['Ts']!r} in the file, {self.Ts!r} in the scene")
-        first, bin_steps, count = (int(v) for v in f["sampling"])
-        if first != self.first:
-            raise ValueError(f"{self.path}: first: {first} in the file, {self.first} asked for")
-        if bin_steps != self.bin_steps:
-            raise ValueError(f"{self.path}: bin_steps: {bin_steps} in the file, {self.bin_steps} asked for")
-        if not np.array_equal(f["pre_sos"], self.pre_sos):
-            raise ValueError(f"{self.path}: pre_sos: the file's sums went through other shared sections (low-cut, integrator)")
-        if not np.array_equal(f["band_sos"], self.band_sos):
-            raise ValueError(f"{self.path}: band_sos: the file's sums went through other band filters (order)")
-        if count != self.samples_below(resume_at):
-            raise ValueError(f"{self.path}: count: the file holds {count} samples, {self.samples_below(resume_at)} sample steps lie below step {resume_at}")
+    def _saved(self, f, count):
         return count, f["sums"], f["state"]
+
+
+class FieldDecay(BandOutput):
+    label, noun, holder, sections = "field decay", "decay", "band accumulator", "shared sections (low-cut, integrator)"
+
+    def __init__(self, path, sd, regions, bands_hz, bin_ms, first=0, order=3, lowcut_hz=10.0, lowcut_order=4, resume_at=None):
+        super().__init__(path, sd, regions, first)
+        self._bands_and_bins(bands_hz, bin_ms, order)
+        self.pre_sos = pre_sections(self.Ts, bool(getattr(sd, "diff", False)), float(lowcut_hz), int(lowcut_order))
+        self.band_sos = band_sections(self.Ts, self.bands, int(order))
+        self._resume(resume_at)
+
+    def _observer(self, obj, lo, hi, st):
+        return obj.band_accumulator(lo, hi, st, pre_sos=self.pre_sos, band_sos=self.band_sos, nbin=self.nbin)
+
+    def _write_head(self, path, append):
+        h5io.write(path, "regions", self.table, append=append)
+        h5io.write(path, "bands", self.bands)
+        h5io.write(path, "Ts", np.float64(self.Ts))
+        h5io.write(path, "sampling", np.array([self.first, self.bin_steps, self.count], dtype=np.int64))
+        h5io.write(path, "pre_sos", self.pre_sos if self.pre_sos.size else np.zeros((1, 6)))  # (no shared section: one row of zeros)
+        h5io.write(path, "npre", np.int64(self.pre_sos.shape[0]))
+        h5io.write(path, "band_sos", self.band_sos)
+
+    def _write_scaled(self, path, i, E):
+        h5io.write(path, f"r{i:03d}_E", E)
+
+    def _read_file(self):
+        return read(self.path, raw=True)
+
+    def _checks(self, f):
+        return [self._other(f, "bands"), *self._band_checks(f)]
 
 
 def read(path, raw=False):
@@ -258,3 +212,22 @@ def parameters(E, bin_seconds):
             if name == "50":
                 out["D50"] = (early / (early + late)).reshape(lead + cells)
     return out
+
+
+def add_arguments(p):
+    """the --decay-* arguments of the command line"""
+    p.add_argument("--decay-planes", action="append", default=[], metavar="x=I,y=J,z=K", help="sum the band-filtered, squared field of these planes into time bins on the device (the syntax of --field-planes)")
+    p.add_argument("--decay-box", action="append", default=[], metavar="x0:x1:sx,y0:y1:sy,z0:z1:sz", help="... of this strided box")
+    p.add_argument("--decay-bands", default="", metavar="F1,F2,...", help="... in the octave bands around these centre frequencies in Hz")
+    p.add_argument("--decay-bin-ms", type=float, default=5.0, metavar="MS", help="... in time bins of MS milliseconds (default 5)")
+    p.add_argument("--decay-first", type=int, default=0, metavar="N", help="... at every step from N on (default 0)")
+    p.add_argument("--decay-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_decay.h5 in the data folder)")
+
+
+def check_arguments(p, a):
+    """a.decay: are decay maps asked for?  Regions without --decay-bands, and any --decay-* without a region, are refused"""
+    a.decay = bool(a.decay_planes or a.decay_box)
+    if a.decay != bool(a.decay_bands) or a.decay_bin_ms <= 0 or a.decay_first < 0:
+        p.error("--decay-planes / --decay-box need --decay-bands (and the other way round); --decay-bin-ms: positive, --decay-first: not negative")
+    if (a.decay_first or a.decay_file or a.decay_bin_ms != 5.0) and not a.decay:
+        p.error("--decay-bin-ms / --decay-first / --decay-file need --decay-planes or --decay-box")

@@ -19,8 +19,8 @@ against the zero of butter(1, 2 Ts lowcut_hz, 'high') = k (1 - z^-1) / (1 - a z^
 bilinear integrator, (omega Ts)^2 / 12, and the first-order high-pass, (lowcut_hz / f)^2 / 2 (tests/test_directional_host.py).
 The products, per chosen axis a (component k): (0, 0) -- once --, (k, k), (0, k) plain and (0, k) absolute.
 
-Every step from `first` on is a sample, and a sample is never shifted, exactly as decay.FieldDecay; a chain that is sampled is created with
-PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES.  These difference components exist on Cartesian grids only (fcc_flag 0), and a region keeps one cell clear
+Every step from `first` on is a sample, exactly as decay.FieldDecay (both are decay.BandOutput, a field_output.FieldOutput: the schedule, take, write
+and the rules of a resume are described there).  These difference components exist on Cartesian grids only (fcc_flag 0), and a region keeps one cell clear
 of both faces along every chosen axis: the engine refuses anything else by name.
 
 FCC grids (fcc_flag 1, the checkerboard, and 2, the checkerboard folded along y) take stencil="lattice": an axis neighbour at +-1 is no node of the
@@ -34,7 +34,7 @@ where it is odd (the upper half of the room, mirrored; row Ny - 1 is the fold's 
 carries each cell's physical row; the raw sums and the filter state stay in storage form, which is what a resumed run continues bit for bit.  The
 axes are the folder's file axes: a rotation sim_setup applied before it wrote the folder is not undone (the folder does not record it).
 
-The file (write(): written to a temporary name and moved into place with os.replace) holds
+The file holds
     regions  int64 [R, 9]    bands  float64 [B]    axes  int64 [A] (1 / 2 / 3 = x / y / z)    Ts  float64    sampling  int64 [3] = first, bin_steps, count
     pre_sos  float64 [1 + A, npre, 6]      band_sos  float64 [B, nsec, 6]      prod  int64 [1 + 3 A, 3]
     r{i:03d}_S      float64 [nprod, B, nbin, c0, c1, c2] of region i: sums * infac^2
@@ -44,14 +44,11 @@ The file (write(): written to a temporary name and moved into place with os.repl
 With resume_at the file must match in regions, bands, axes, stencil, Ts, first, bin_steps, pre_sos, band_sos and prod, and its count must be the number of
 sample steps below resume_at; otherwise it is refused with the field's name.
 """
-import os
-
 import numpy as np
 from scipy.signal import butter
 
 from . import h5io
-from .decay import band_sections, pre_sections
-from .engine import PfError
+from .decay import BandOutput, band_sections, pre_sections
 
 IDENTITY = np.array([1.0, 0.0, 0.0, 1.0, 0.0, 0.0])
 
@@ -97,6 +94,36 @@ def gradient_sections(Ts, h, c, diff, lowcut_hz, lowcut_order, span=2):
     return (np.ascontiguousarray(np.vstack([pre, IDENTITY[None]]), dtype=np.float64), np.ascontiguousarray(np.vstack([pre, last[None]]), dtype=np.float64))
 
 
+def vector_setup(who, holder, sd, axes, stencil, lowcut_hz, lowcut_order):
+    """-> (axes int64 [A], pre_sos [1 + A, npre, 6]: the omni sections, then the gradient's per axis, comp int64 [1 + A]: the cell and the difference
+    `stencil` names per axis) for the scene sd, or ValueError in the name of the class `who`, whose observer is "a `holder`" """
+    axes = np.ascontiguousarray(axes, dtype=np.int64).reshape(-1)
+    fcc_flag = int(getattr(sd, "fcc_flag", 0))
+    if axes.size < 1 or axes.size > 3 or np.any(axes < 1) or np.any(axes > 3) or len(set(axes.tolist())) != axes.size:
+        raise ValueError(f"{who}: axes: {axes.tolist()} is not one to three different axes out of 1, 2, 3 (x, y, z)")
+    if stencil not in STENCILS:
+        raise ValueError(f"{who}: stencil: {stencil!r} is neither \"axis\" nor \"lattice\"")
+    if stencil == "axis" and fcc_flag != 0:
+        raise ValueError(f"{who}: fcc_flag: the central difference along an axis exists on Cartesian grids only (fcc_flag 0); an FCC grid takes "
+                         "stencil=\"lattice\", the difference over the lattice's own neighbours")
+    if stencil == "lattice" and fcc_flag == 0:
+        raise ValueError(f"{who}: stencil=\"lattice\": the lattice difference exists on FCC grids only (fcc_flag 1 or 2); a Cartesian grid takes "
+                         "stencil=\"axis\"")
+    if getattr(sd, "h", None) is None or getattr(sd, "c", None) is None:
+        raise ValueError(f"{who}: h, c: the scene's constants hold no grid spacing or speed of sound (sim_consts.h5: h, c)")
+    omni, grad = gradient_sections(float(sd.Ts), float(sd.h), float(sd.c), bool(getattr(sd, "diff", False)), float(lowcut_hz), int(lowcut_order),
+                                   span=LATTICE_SPAN if stencil == "lattice" else 2)
+    if omni.shape[0] > 8:
+        raise ValueError(f"{who}: lowcut_order: {omni.shape[0]} sections per component, a {holder} holds 8")
+    return axes, np.ascontiguousarray(np.stack([omni] + [grad] * axes.size)), np.concatenate([[0], axes + (3 if stencil == "lattice" else 0)]).astype(np.int64)
+
+
+def y_components(comp):
+    """the positions in the component list `comp` of the differences along y (2: axis, 5: lattice).  On a folded grid (fcc_flag 2) the stored +y
+    of an odd cell (fold_coordinates: upper) is the room's -y: what is odd in these components is negated there -- exact"""
+    return [k for k, c in enumerate(np.asarray(comp).tolist()) if c in (2, 5)]
+
+
 def products(naxes):
     """int64 [1 + 3 naxes, 3]: (0, 0, 0), then per axis component k = 1 .. naxes: (k, k, 0), (0, k, 0), (0, k, 1)"""
     rows = [(0, 0, 0)]
@@ -105,160 +132,50 @@ def products(naxes):
     return np.array(rows, dtype=np.int64)
 
 
-class FieldDirectional:
+class FieldDirectional(BandOutput):
+    label, noun, holder, sections = "directional maps", "directional", "vector band accumulator", "sections per component (low-cut, integrator, grid spacing)"
+
     def __init__(self, path, sd, regions, bands_hz, axes, bin_ms, first=0, order=3, lowcut_hz=10.0, lowcut_order=4, resume_at=None, stencil="axis"):
-        self.path, self.sd = os.fspath(path), sd
+        super().__init__(path, sd, regions, first)
         self.stencil, self.fcc_flag = stencil, int(getattr(sd, "fcc_flag", 0))
-        self.regions = [tuple(tuple(int(v) for v in t) for t in r) for r in regions]
-        self.bands = np.ascontiguousarray(bands_hz, dtype=np.float64).reshape(-1)
-        self.axes = np.ascontiguousarray(axes, dtype=np.int64).reshape(-1)
-        self.first, self.Ts = int(first), float(sd.Ts)
-        self.bin_steps = int(round(float(bin_ms) * 1e-3 / self.Ts))
-        if self.first < 0 or not self.regions or self.bands.size == 0 or int(order) < 1:
-            raise ValueError("FieldDirectional: at least one region and one band, first >= 0, order >= 1")
-        if self.axes.size < 1 or self.axes.size > 3 or np.any(self.axes < 1) or np.any(self.axes > 3) or len(set(self.axes.tolist())) != self.axes.size:
-            raise ValueError(f"FieldDirectional: axes: {self.axes.tolist()} is not one to three different axes out of 1, 2, 3 (x, y, z)")
-        if self.bands.size > 16 or int(order) > 8:
-            raise ValueError(f"FieldDirectional: bands: {self.bands.size} bands of order {order}, a vector band accumulator holds 16 of 8 sections")
-        if self.bin_steps < 1:
-            raise ValueError(f"FieldDirectional: bin_ms: {bin_ms} ms is less than half a step of {self.Ts * 1e3:g} ms")
-        if stencil not in STENCILS:
-            raise ValueError(f"FieldDirectional: stencil: {stencil!r} is neither \"axis\" nor \"lattice\"")
-        if stencil == "axis" and self.fcc_flag != 0:
-            raise ValueError("FieldDirectional: fcc_flag: the central difference along an axis exists on Cartesian grids only (fcc_flag 0); an FCC grid takes "
-                             "stencil=\"lattice\", the difference over the lattice's own neighbours")
-        if stencil == "lattice" and self.fcc_flag == 0:
-            raise ValueError("FieldDirectional: stencil=\"lattice\": the lattice difference exists on FCC grids only (fcc_flag 1 or 2); a Cartesian grid takes "
-                             "stencil=\"axis\"")
-        if getattr(sd, "h", None) is None or getattr(sd, "c", None) is None:
-            raise ValueError("FieldDirectional: h, c: the scene's constants hold no grid spacing or speed of sound (sim_consts.h5: h, c)")
-        omni, grad = gradient_sections(self.Ts, float(sd.h), float(sd.c), bool(getattr(sd, "diff", False)), float(lowcut_hz), int(lowcut_order),
-                                       span=LATTICE_SPAN if stencil == "lattice" else 2)
-        if omni.shape[0] > 8:
-            raise ValueError(f"FieldDirectional: lowcut_order: {omni.shape[0]} sections per component, a vector band accumulator holds 8")
-        self.pre_sos = np.ascontiguousarray(np.stack([omni] + [grad] * self.axes.size))
+        self._bands_and_bins(bands_hz, bin_ms, order)
+        self.axes, self.pre_sos, self.comp = vector_setup("FieldDirectional", self.holder, sd, axes, stencil, lowcut_hz, lowcut_order)
         self.band_sos = band_sections(self.Ts, self.bands, int(order))
-        self.comp = np.concatenate([[0], self.axes + (3 if stencil == "lattice" else 0)]).astype(np.int64)
         self.prod = products(self.axes.size)
-        self.nbin = max(1, -(-(sd.Nt - self.first) // self.bin_steps))
-        self.table = np.array([lo + hi + st for lo, hi, st in self.regions], dtype=np.int64).reshape(-1, 9)
-        self.accs, self._restore = None, None
-        if resume_at is not None:
-            self._restore = self._read_matching(int(resume_at))
+        self._resume(resume_at)
 
-    # ---- the sample steps ----
-    def next_step(self, n):
-        """the first step >= n at which a sample is due (it may lie at or past Nt: no sample then)"""
-        return max(n, self.first)
+    def _observer(self, obj, lo, hi, st):
+        return obj.vector_band_accumulator(lo, hi, st, comp=self.comp, pre_sos=self.pre_sos, band_sos=self.band_sos, prod=self.prod, nbin=self.nbin)
 
-    def due(self, n):
-        return self.first <= n < self.sd.Nt
+    def _write_head(self, path, append):
+        h5io.write(path, "regions", self.table, append=append)
+        h5io.write(path, "bands", self.bands)
+        h5io.write(path, "axes", self.axes)
+        h5io.write(path, "Ts", np.float64(self.Ts))
+        h5io.write(path, "sampling", np.array([self.first, self.bin_steps, self.count], dtype=np.int64))
+        h5io.write(path, "pre_sos", self.pre_sos)
+        h5io.write(path, "band_sos", self.band_sos)
+        h5io.write(path, "prod", self.prod)
+        h5io.write(path, "stencil", np.int64(STENCILS.index(self.stencil)))
+        h5io.write(path, "fcc_flag", np.int64(self.fcc_flag))
 
-    def samples_below(self, n):
-        """how many sample steps lie below step n"""
-        return max(0, n - self.first)
-
-    def bin_of(self, n):
-        return (n - self.first) // self.bin_steps
-
-    # ---- the sums ----
-    def attach(self, obj):
-        """one vector band accumulator per region on obj (a HipEngine or a HipMulti); a resumed run's sums and filter state go into them"""
-        if self.accs is not None:
-            return
-        self.accs = [obj.vector_band_accumulator(lo, hi, st, comp=self.comp, pre_sos=self.pre_sos, band_sos=self.band_sos, prod=self.prod, nbin=self.nbin)
-                     for lo, hi, st in self.regions]
-        if self._restore is not None:
-            count, sums, state = self._restore
-            for a, e, s in zip(self.accs, sums, state):
-                a.set(e, s, count)
-            self._restore = None
-
-    @property
-    def count(self):
-        if self.accs is None:
-            return self._restore[0] if self._restore is not None else 0
-        return self.accs[0].count
-
-    def take(self, obj, n):
-        """the sample of step n (due(n)) -- never of another step"""
-        if not self.due(n):
-            raise ValueError(f"FieldDirectional.take: no sample is due at step {n} (first {self.first}, Nt {self.sd.Nt})")
-        self.attach(obj)
-        try:
-            for a in self.accs:
-                a.add(self.bin_of(n))
-        except PfError as e:
-            if e.code != 4:  # (PF_ERR_STATE: a slab inside a pair or triple; no slab took the sample)
-                raise
-            err = PfError(f"directional maps: step {n} cannot be sampled, a slab is inside a blocked pass there, and a sample is never shifted: "
-                          f"create the chain with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES ({e})")
-            err.code = 4
-            raise err
-        return n
-
-    def write(self):
-        """the file as it stands: every region's sums and filter state so far"""
-        if self.accs is None:
-            raise ValueError("FieldDirectional.write: no accumulators yet (attach or take first)")
-        tmp = self.path + ".tmp"
-        h5io.write(tmp, "regions", self.table, append=False)
-        h5io.write(tmp, "bands", self.bands)
-        h5io.write(tmp, "axes", self.axes)
-        h5io.write(tmp, "Ts", np.float64(self.Ts))
-        h5io.write(tmp, "sampling", np.array([self.first, self.bin_steps, self.count], dtype=np.int64))
-        h5io.write(tmp, "pre_sos", self.pre_sos)
-        h5io.write(tmp, "band_sos", self.band_sos)
-        h5io.write(tmp, "prod", self.prod)
-        h5io.write(tmp, "stencil", np.int64(STENCILS.index(self.stencil)))
-        h5io.write(tmp, "fcc_flag", np.int64(self.fcc_flag))
-        # the products whose sign follows the room's y: an odd number of y factors, mode 0 (folded grids: the stored +y of an odd cell is the room's -y)
-        ycomp = [k for k, c in enumerate(self.comp.tolist()) if c in (2, 5)]
-        flip = [p for p, (i, j, mode) in enumerate(self.prod.tolist()) if mode == 0 and ((i in ycomp) != (j in ycomp))]
-        for i, a in enumerate(self.accs):
-            e, s = a.get()
-            h5io.write(tmp, f"r{i:03d}_sums", e)
-            h5io.write(tmp, f"r{i:03d}_state", s)
-            S = e * (self.sd.infac * self.sd.infac)
-            if self.fcc_flag == 2:
-                _, iy, _, upper = fold_coordinates(self.regions[i], self.sd.Ny)
-                h5io.write(tmp, f"r{i:03d}_iy", np.ascontiguousarray(iy, dtype=np.int64))
-                for p in flip:
+    def _write_scaled(self, path, i, S):
+        if self.fcc_flag == 2:
+            _, iy, _, upper = fold_coordinates(self.regions[i], self.sd.Ny)
+            h5io.write(path, f"r{i:03d}_iy", np.ascontiguousarray(iy, dtype=np.int64))
+            ycomp = y_components(self.comp)
+            for p, (i0, i1, mode) in enumerate(self.prod.tolist()):  # the products whose sign follows the room's y: an odd number of y factors, mode 0
+                if mode == 0 and ((i0 in ycomp) != (i1 in ycomp)):
                     S[p][..., upper] = -S[p][..., upper]
-            h5io.write(tmp, f"r{i:03d}_S", S)
-        os.replace(tmp, self.path)
+        h5io.write(path, f"r{i:03d}_S", S)
 
-    def close(self):
-        for a in self.accs or []:
-            a.close()
-        self.accs = None
+    def _read_file(self):
+        return read(self.path, raw=True)
 
-    def _read_matching(self, resume_at):
-        """(count, [raw sums per region], [filter state per region]) of the file a resumed run continues, or ValueError naming the field that differs"""
-        if not os.path.exists(self.path):
-            raise ValueError(f"{self.path}: no directional file to resume from")
-        f = read(self.path, raw=True)
-        for name, mine in (("regions", self.table), ("bands", self.bands), ("axes", self.axes)):
-            if not np.array_equal(f[name], mine):
-                raise ValueError(f"{self.path}: {name}: the file holds the sums of other {name}")
-        if f["stencil"] != self.stencil:
-            raise ValueError(f"{self.path}: stencil: the file holds the sums of stencil=\"{f['stencil']}\", \"{self.stencil}\" is asked for")
-        if f["Ts"] != self.Ts:
-            raise ValueError(f"{self.path}: Ts: {f['Ts']!r} in the file, {self.Ts!r} in the scene")
-        first, bin_steps, count = (int(v) for v in f["sampling"])
-        if first != self.first:
-            raise ValueError(f"{self.path}: first: {first} in the file, {self.first} asked for")
-        if bin_steps != self.bin_steps:
-            raise ValueError(f"{self.path}: bin_steps: {bin_steps} in the file, {self.bin_steps} asked for")
-        if not np.array_equal(f["pre_sos"], self.pre_sos):
-            raise ValueError(f"{self.path}: pre_sos: the file's sums went through other sections per component (low-cut, integrator, grid spacing)")
-        if not np.array_equal(f["band_sos"], self.band_sos):
-            raise ValueError(f"{self.path}: band_sos: the file's sums went through other band filters (order)")
-        if not np.array_equal(f["prod"], self.prod):
-            raise ValueError(f"{self.path}: prod: the file holds the sums of other products")
-        if count != self.samples_below(resume_at):
-            raise ValueError(f"{self.path}: count: the file holds {count} samples, {self.samples_below(resume_at)} sample steps lie below step {resume_at}")
-        return count, f["sums"], f["state"]
+    def _checks(self, f):
+        return [self._other(f, "bands"), self._other(f, "axes"),
+                ("stencil", f["stencil"] == self.stencil, f"the file holds the sums of stencil=\"{f['stencil']}\", \"{self.stencil}\" is asked for"),
+                *self._band_checks(f), self._other(f, "prod", "products")]
 
 
 def read(path, raw=False):
@@ -338,3 +255,28 @@ def parameters(S, prod, bin_seconds):
     for name in ("LF", "LFC", "intensity", "intensity_total"):
         out[name] = np.stack(out[name]) if comps else np.zeros((0,))
     return out
+
+
+def add_arguments(p):
+    """the --dir-* arguments of the command line"""
+    p.add_argument("--dir-planes", action="append", default=[], metavar="x=I,y=J,z=K", help="sum band-filtered products of the pressure and its gradient on these planes into time bins on the device (the syntax of --field-planes)")
+    p.add_argument("--dir-box", action="append", default=[], metavar="x0:x1:sx,y0:y1:sy,z0:z1:sz", help="... of this strided box")
+    p.add_argument("--dir-bands", default="", metavar="F1,F2,...", help="... in the octave bands around these centre frequencies in Hz")
+    p.add_argument("--dir-axes", default="", metavar="y[,x,z]", help="... with the gradient along these file axes (default y)")
+    p.add_argument("--dir-stencil", default="", choices=["", "axis", "lattice"], metavar="axis|lattice", help="... as the central difference along the axis (axis, the default: Cartesian grids) or the FCC lattice's difference (lattice: FCC folders)")
+    p.add_argument("--dir-bin-ms", type=float, default=5.0, metavar="MS", help="... in time bins of MS milliseconds (default 5)")
+    p.add_argument("--dir-first", type=int, default=0, metavar="N", help="... at every step from N on (default 0)")
+    p.add_argument("--dir-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_directional.h5 in the data folder)")
+
+
+def check_arguments(p, a):
+    """a.directional: are directional maps asked for?  Regions without --dir-bands, and any --dir-* without a region, are refused; the defaults of
+    --dir-stencil (axis) and --dir-axes (y) are filled in"""
+    a.directional = bool(a.dir_planes or a.dir_box)
+    if a.directional != bool(a.dir_bands) or a.dir_bin_ms <= 0 or a.dir_first < 0:
+        p.error("--dir-planes / --dir-box need --dir-bands (and the other way round); --dir-bin-ms: positive, --dir-first: not negative")
+    if (a.dir_first or a.dir_file or a.dir_axes or a.dir_stencil or a.dir_bin_ms != 5.0) and not a.directional:
+        p.error("--dir-axes / --dir-stencil / --dir-bin-ms / --dir-first / --dir-file need --dir-planes or --dir-box")
+    a.dir_stencil = a.dir_stencil or "axis"
+    if a.directional and not a.dir_axes:
+        a.dir_axes = "y"

@@ -74,6 +74,8 @@ import argparse
 import os
 import time
 from pathlib import Path
+from types import ModuleType
+from typing import Callable, NamedTuple
 
 from . import checkpoint, engine, fields, sim_data, spectra
 from . import decay as decay_mod
@@ -132,7 +134,7 @@ def _run_chain(a, sd, m):
     """all Nt steps of a chain object, in one go or in chunks with progress reports; returns (seconds, timing of the busiest slab).
     With --resume / --checkpoint / --stop-after: from the resumed step, to the step the run stops after (a.stopped_at: less than Nt then)."""
     live = range(m.nslabs)
-    if a.resume or a.checkpoint or a.field_every or a.spectrum or a.decay or a.directional or a.rec:
+    if a.resume or a.checkpoint or a.field_every or any(getattr(a, kind.flag) for kind in KINDS):
         return _run_chain_checkpointed(a, sd, m)
     t0 = time.perf_counter()
     if not a.progress:
@@ -172,95 +174,81 @@ def _field_writer(a, sd, resume_at):
         raise SystemExit(str(e))
 
 
-def _field_spectrum(a, sd, m, resume_at):
-    """the FieldSpectrum of --spectrum-planes / --spectrum-box on chain m (None without them); a resumed run's sums are restored"""
-    if not a.spectrum:
-        return None
+class _Kind(NamedTuple):
+    """one kind of field output that is summed or filtered on the device, as the command line sees it"""
+    name: str  # in the lines of standard output: "--field <name> ..."
+    prefix: str  # of its arguments: --<prefix>-planes, --<prefix>-box, --<prefix>-file
+    flag: str  # a.<flag>, set by its module's check_arguments: is it asked for?
+    module: ModuleType  # add_arguments, check_arguments
+    file: str  # the default file name, beside sim_outs.h5
+    build: Callable  # (a, sd, regions, path, resume_at) -> the output
+    reword: tuple  # (old, new) applied to a ValueError's text after "--field-" has become "--<prefix>-"
+    attach_names_regions: bool  # a PfError of attach is a refusal of the regions: it exits as "--<prefix>-planes / --<prefix>-box: ..."
+    sampled: str  # why its chain takes single steps (_chain_flags)
+    done: Callable  # the output -> the end-of-run line between "--field " and ": <path>"
+
+
+def _stencil_words(prefix):
+    return (('stencil="lattice"', f"--{prefix}-stencil lattice"), ('stencil="axis"', f"--{prefix}-stencil axis"))
+
+
+KINDS = (  # in the order they are built, sampled within a step, written and reported
+    _Kind("spectrum", "spectrum", "spectrum", spectra, "sim_spectra.h5",
+          lambda a, sd, regions, path, resume_at: spectra.FieldSpectrum(path, sd, regions, spectra.parse_freqs(a.spectrum_freqs), a.spectrum_every, a.spectrum_first,
+                                                                        a.spectrum_window, resume_at=resume_at),
+          (), False, "every sample step can be sampled", lambda o: f"spectrum of {o.count} samples at {o.freqs.size} frequencies"),
+    _Kind("decay", "decay", "decay", decay_mod, "sim_decay.h5",
+          lambda a, sd, regions, path, resume_at: decay_mod.FieldDecay(path, sd, regions, decay_mod.parse_bands(a.decay_bands), a.decay_bin_ms, a.decay_first, resume_at=resume_at),
+          (), False, "every step is sampled", lambda o: f"decay of {o.count} samples in {o.bands.size} bands, bins of {o.bin_steps} steps"),
+    _Kind("directional", "dir", "directional", dir_mod, "sim_directional.h5",
+          lambda a, sd, regions, path, resume_at: dir_mod.FieldDirectional(path, sd, regions, decay_mod.parse_bands(a.dir_bands), dir_mod.parse_axes(a.dir_axes), a.dir_bin_ms,
+                                                                           a.dir_first, resume_at=resume_at, stencil=a.dir_stencil),
+          (("--decay-", "--dir-"),) + _stencil_words("dir"), True, "every step is sampled",  # (attach: a region on a face along a chosen axis, an FCC grid: the engine names it)
+          lambda o: f"directional maps of {o.count} samples in {o.bands.size} bands along {','.join('xyz'[k - 1] for k in o.axes)}"
+                    f"{' (lattice differences)' if o.stencil == 'lattice' else ''}, bins of {o.bin_steps} steps"),
+    _Kind("recording", "rec", "rec", rec_mod, "sim_recordings.h5",
+          lambda a, sd, regions, path, resume_at: rec_mod.FieldRecording(path, sd, regions, a.rec_factor, a.rec_fpass, a.rec_atten, a.rec_first, dtype=a.rec_dtype, resume_at=resume_at,
+                                                                         axes=dir_mod.parse_axes(a.rec_axes) if a.rec_axes else None, stencil=a.rec_stencil),
+          (("--dir-", "--rec-"),) + _stencil_words("rec"), True, "every step is sampled",  # (attach: a factor or a tap count the engine refuses, a region on a face along a recorded axis)
+          lambda o: f"recording of {o.count} samples, {o.frames} frames at every {o.factor}th step through {o.taps.size} taps"
+                    + ("" if o.axes is None else f", channels W {' '.join('XYZ'[k - 1] for k in o.axes.tolist())} ({o.stencil} differences)")),
+)
+
+
+def _field_output(kind, a, sd, m, resume_at):
+    """the output of `kind` on chain m, attached; a resumed run's state is restored from its file"""
     N = (sd.Nx, sd.Ny, sd.Nz)
     try:
-        regions = [r for spec in a.spectrum_planes for r in fields.parse_planes(spec, N)] + [fields.parse_box(spec, N) for spec in a.spectrum_box]
-        path = a.spectrum_file if a.spectrum_file else Path(a.data_dir) / "sim_spectra.h5"
-        fs = spectra.FieldSpectrum(path, sd, regions, spectra.parse_freqs(a.spectrum_freqs), a.spectrum_every, a.spectrum_first, a.spectrum_window, resume_at=resume_at)
+        regions = [r for spec in getattr(a, kind.prefix + "_planes") for r in fields.parse_planes(spec, N)] + [fields.parse_box(spec, N) for spec in getattr(a, kind.prefix + "_box")]
+        path = getattr(a, kind.prefix + "_file") or Path(a.data_dir) / kind.file
+        out = kind.build(a, sd, regions, path, resume_at)
     except ValueError as e:
-        raise SystemExit(str(e).replace("--field-", "--spectrum-"))
-    fs.attach(m)
-    return fs
-
-
-def _field_decay(a, sd, m, resume_at):
-    """the FieldDecay of --decay-planes / --decay-box on chain m (None without them); a resumed run's sums and filter state are restored"""
-    if not a.decay:
-        return None
-    N = (sd.Nx, sd.Ny, sd.Nz)
+        text = str(e).replace("--field-", f"--{kind.prefix}-")
+        for old, new in kind.reword:
+            text = text.replace(old, new)
+        raise SystemExit(text)
     try:
-        regions = [r for spec in a.decay_planes for r in fields.parse_planes(spec, N)] + [fields.parse_box(spec, N) for spec in a.decay_box]
-        path = a.decay_file if a.decay_file else Path(a.data_dir) / "sim_decay.h5"
-        fd = decay_mod.FieldDecay(path, sd, regions, decay_mod.parse_bands(a.decay_bands), a.decay_bin_ms, a.decay_first, resume_at=resume_at)
-    except ValueError as e:
-        raise SystemExit(str(e).replace("--field-", "--decay-"))
-    fd.attach(m)
-    return fd
-
-
-def _field_directional(a, sd, m, resume_at):
-    """the FieldDirectional of --dir-planes / --dir-box on chain m (None without them); a resumed run's sums and filter state are restored"""
-    if not a.directional:
-        return None
-    N = (sd.Nx, sd.Ny, sd.Nz)
-    try:
-        regions = [r for spec in a.dir_planes for r in fields.parse_planes(spec, N)] + [fields.parse_box(spec, N) for spec in a.dir_box]
-        path = a.dir_file if a.dir_file else Path(a.data_dir) / "sim_directional.h5"
-        fv = dir_mod.FieldDirectional(path, sd, regions, decay_mod.parse_bands(a.dir_bands), dir_mod.parse_axes(a.dir_axes), a.dir_bin_ms, a.dir_first, resume_at=resume_at,
-                                      stencil=a.dir_stencil)
-    except ValueError as e:
-        raise SystemExit(str(e).replace("--field-", "--dir-").replace("--decay-", "--dir-").replace('stencil="lattice"', "--dir-stencil lattice")
-                         .replace('stencil="axis"', "--dir-stencil axis"))
-    try:
-        fv.attach(m)
-    except engine.PfError as e:  # (a region on a face along a chosen axis, an FCC grid: the engine names it)
-        raise SystemExit(f"--dir-planes / --dir-box: {e}")
-    return fv
-
-
-def _field_recording(a, sd, m, resume_at):
-    """the FieldRecording of --rec-planes / --rec-box on chain m (None without them); a resumed run's outputs in flight and filter state are restored"""
-    if not a.rec:
-        return None
-    N = (sd.Nx, sd.Ny, sd.Nz)
-    try:
-        regions = [r for spec in a.rec_planes for r in fields.parse_planes(spec, N)] + [fields.parse_box(spec, N) for spec in a.rec_box]
-        path = a.rec_file if a.rec_file else Path(a.data_dir) / "sim_recordings.h5"
-        fr = rec_mod.FieldRecording(path, sd, regions, a.rec_factor, a.rec_fpass, a.rec_atten, a.rec_first, dtype=a.rec_dtype, resume_at=resume_at,
-                                    axes=dir_mod.parse_axes(a.rec_axes) if a.rec_axes else None, stencil=a.rec_stencil)
-    except ValueError as e:
-        raise SystemExit(str(e).replace("--field-", "--rec-").replace("--dir-", "--rec-").replace('stencil="lattice"', "--rec-stencil lattice")
-                         .replace('stencil="axis"', "--rec-stencil axis"))
-    try:
-        fr.attach(m)
-    except engine.PfError as e:  # (a factor or a tap count the engine refuses, a region on a face along a recorded axis: it names the field)
-        raise SystemExit(f"--rec-planes / --rec-box: {e}")
-    return fr
+        out.attach(m)
+    except engine.PfError as e:
+        if not kind.attach_names_regions:
+            raise
+        raise SystemExit(f"--{kind.prefix}-planes / --{kind.prefix}-box: {e}")
+    return out
 
 
 def _chain_flags(a, nslabs):
-    """multi_flags of the chain: sampled for a spectrum or a decay map, its slabs take single steps (a sample is never shifted, and no slab answers
-    inside a pass)"""
-    if not (a.spectrum or a.decay or a.directional or a.rec) or nslabs < 2:
+    """multi_flags of the chain: sampled by a field output of KINDS, no slab steps in pairs or triples (a sample is never shifted, and no slab
+    answers inside a pass)"""
+    asked = [kind for kind in KINDS if getattr(a, kind.flag)]
+    if not asked or nslabs < 2:
         return 0
-    if a.rec:
-        print("--field recording: the chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (its slabs take single steps: every step is sampled)")
-    if a.directional:
-        print("--field directional: the chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (its slabs take single steps: every step is sampled)")
-    if a.decay:
-        print("--field decay: the chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (its slabs take single steps: every step is sampled)")
-    if not a.spectrum:
-        return engine.PF_MULTI_NO_PAIRS | engine.PF_MULTI_NO_TRIPLES
-    print("--field spectrum: the chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (its slabs take single steps: every sample step can be sampled)")
+    for kind in reversed(asked):
+        print(f"--field {kind.name}: the chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (its slabs take single steps: {kind.sampled})")
     return engine.PF_MULTI_NO_PAIRS | engine.PF_MULTI_NO_TRIPLES
 
 
 def _run_chain_checkpointed(a, sd, m):
-    """the run cut at checkpoint steps, at frame steps (--field-every) and at the sample steps of a spectrum (--spectrum-every)"""
+    """the run cut at checkpoint steps, at frame steps (--field-every) and at the sample steps of every field output of KINDS"""
     live = range(m.nslabs)
     n = 0
     if a.resume:
@@ -272,10 +260,8 @@ def _run_chain_checkpointed(a, sd, m):
         m.load_state(state)
         print(f"--resumed at step {n} of {sd.Nt}: {a.resume}", flush=True)
     fw = _field_writer(a, sd, n if a.resume else None)
-    fs = _field_spectrum(a, sd, m, n if a.resume else None)
-    fd = _field_decay(a, sd, m, n if a.resume else None)
-    fv = _field_directional(a, sd, m, n if a.resume else None)
-    fr = _field_recording(a, sd, m, n if a.resume else None)
+    outs = [(kind, _field_output(kind, a, sd, m, n if a.resume else None)) for kind in KINDS if getattr(a, kind.flag)]
+    cuts = ([fw] if fw else []) + [out for _, out in outs]  # the run is cut at the next step of each of these
     end = sd.Nt if a.stop_after is None else min(max(a.stop_after, n), sd.Nt)
     every = a.checkpoint_every if a.checkpoint else 0
     t0 = time.perf_counter()
@@ -283,30 +269,17 @@ def _run_chain_checkpointed(a, sd, m):
     if fw and fw.due(n) and n < end:  # (the frame of the first step: before any step of this run)
         n = fw.take(m, n)
         print(f"--field frame at step {n} of {sd.Nt}: {fw.path}", flush=True)
-    if fs and fs.due(n) and n < end:  # (a step's sample belongs to the run that takes the step: a stopped run leaves the sample of its last step to the resumed one)
-        fs.take(m, n)
-    if fd and fd.due(n) and n < end:
-        fd.take(m, n)
-    if fv and fv.due(n) and n < end:
-        fv.take(m, n)
-    if fr and fr.due(n) and n < end:
-        fr.take(m, n)
+    for _, out in outs:  # (a step's sample belongs to the run that takes the step: a stopped run leaves the sample of its last step to the resumed one)
+        if out.due(n) and n < end:
+            out.take(m, n)
     while n < end:
         k = end - n
         if a.progress:
             k = min(k, a.progress)
         if every:
             k = min(k, every - n % every)
-        if fw and fw.next_step(n + 1) < n + k:
-            k = fw.next_step(n + 1) - n
-        if fs and fs.next_step(n + 1) < n + k:
-            k = fs.next_step(n + 1) - n
-        if fd and fd.next_step(n + 1) < n + k:
-            k = fd.next_step(n + 1) - n
-        if fv and fv.next_step(n + 1) < n + k:
-            k = fv.next_step(n + 1) - n
-        if fr and fr.next_step(n + 1) < n + k:
-            k = fr.next_step(n + 1) - n
+        for out in cuts:
+            k = min(k, out.next_step(n + 1) - n)
         tc = time.perf_counter()
         m.run(n, k)
         n += k
@@ -318,22 +291,11 @@ def _run_chain_checkpointed(a, sd, m):
         if save:
             n = _save_checkpoint(a, sd, m, n)
             end = max(end, n)
-            if fs:
-                fs.write()  # (the sums of the sample steps below n: what --resume of this checkpoint continues)
-            if fd:
-                fd.write()
-            if fv:
-                fv.write()
-            if fr:
-                fr.write()
-        if fs and fs.due(n) and n < end:
-            fs.take(m, n)
-        if fd and fd.due(n) and n < end:
-            fd.take(m, n)
-        if fv and fv.due(n) and n < end:
-            fv.take(m, n)
-        if fr and fr.due(n) and n < end:
-            fr.take(m, n)
+            for _, out in outs:
+                out.write()  # (the output of the sample steps below n: what --resume of this checkpoint continues)
+        for _, out in outs:
+            if out.due(n) and n < end:
+                out.take(m, n)
         now = time.perf_counter()
         tms = [m.slab(g)["engine"].timing(reset=True) for g in live]
         air = max(t["air_ms_total"] for t in tms) * 1e-3
@@ -345,23 +307,10 @@ def _run_chain_checkpointed(a, sd, m):
         if a.progress:
             _progress(sd, n, sd.Nt, now - t0, now - tc, k, air_all, air, max(step_all - air_all, 1e-12), max(step - air, 1e-12), m.nslabs)
     a.stopped_at = n
-    if fs:
-        fs.write()
-        print(f"--field spectrum of {fs.count} samples at {fs.freqs.size} frequencies: {fs.path}", flush=True)
-        fs.close()
-    if fd:
-        fd.write()
-        print(f"--field decay of {fd.count} samples in {fd.bands.size} bands, bins of {fd.bin_steps} steps: {fd.path}", flush=True)
-        fd.close()
-    if fv:
-        fv.write()
-        print(f"--field directional maps of {fv.count} samples in {fv.bands.size} bands along {','.join('xyz'[k - 1] for k in fv.axes)}{' (lattice differences)' if fv.stencil == 'lattice' else ''}, bins of {fv.bin_steps} steps: {fv.path}", flush=True)
-        fv.close()
-    if fr:
-        fr.write()
-        chan = "" if fr.axes is None else f", channels W {' '.join('XYZ'[k - 1] for k in fr.axes.tolist())} ({fr.stencil} differences)"
-        print(f"--field recording of {fr.count} samples, {fr.frames} frames at every {fr.factor}th step through {fr.taps.size} taps{chan}: {fr.path}", flush=True)
-        fr.close()
+    for kind, out in outs:
+        out.write()
+        print(f"--field {kind.done(out)}: {out.path}", flush=True)
+        out.close()
     return time.perf_counter() - t0, {"air_ms_total": air_all * 1e3, "step_ms_total": step_all * 1e3}
 
 
@@ -491,48 +440,11 @@ def main():
     p.add_argument("--field-every", type=int, default=0, metavar="K", help="record the field regions every K steps")
     p.add_argument("--field-first", type=int, default=0, metavar="N", help="... from step N on (default 0)")
     p.add_argument("--field-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_fields.h5 in the data folder)")
-    p.add_argument("--spectrum-planes", action="append", default=[], metavar="x=I,y=J,z=K", help="sum the DFT of these planes of the field on the device (the syntax of --field-planes)")
-    p.add_argument("--spectrum-box", action="append", default=[], metavar="x0:x1:sx,y0:y1:sy,z0:z1:sz", help="... of this strided box")
-    p.add_argument("--spectrum-freqs", default="", metavar="F1,F2,... | LO:HI:N", help="... at these frequencies in Hz (LO:HI:N: N of them, linearly spaced)")
-    p.add_argument("--spectrum-every", type=int, default=1, metavar="K", help="... sampling every K steps (default 1; content above 1 / (2 K Ts) aliases)")
-    p.add_argument("--spectrum-first", type=int, default=0, metavar="N", help="... from step N on (default 0)")
-    p.add_argument("--spectrum-window", default=None, choices=["hann"], help="... under a window over the sample steps (default: none)")
-    p.add_argument("--spectrum-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_spectra.h5 in the data folder)")
-    p.add_argument("--decay-planes", action="append", default=[], metavar="x=I,y=J,z=K", help="sum the band-filtered, squared field of these planes into time bins on the device (the syntax of --field-planes)")
-    p.add_argument("--decay-box", action="append", default=[], metavar="x0:x1:sx,y0:y1:sy,z0:z1:sz", help="... of this strided box")
-    p.add_argument("--decay-bands", default="", metavar="F1,F2,...", help="... in the octave bands around these centre frequencies in Hz")
-    p.add_argument("--decay-bin-ms", type=float, default=5.0, metavar="MS", help="... in time bins of MS milliseconds (default 5)")
-    p.add_argument("--decay-first", type=int, default=0, metavar="N", help="... at every step from N on (default 0)")
-    p.add_argument("--decay-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_decay.h5 in the data folder)")
-    p.add_argument("--dir-planes", action="append", default=[], metavar="x=I,y=J,z=K", help="sum band-filtered products of the pressure and its gradient on these planes into time bins on the device (the syntax of --field-planes)")
-    p.add_argument("--dir-box", action="append", default=[], metavar="x0:x1:sx,y0:y1:sy,z0:z1:sz", help="... of this strided box")
-    p.add_argument("--dir-bands", default="", metavar="F1,F2,...", help="... in the octave bands around these centre frequencies in Hz")
-    p.add_argument("--dir-axes", default="", metavar="y[,x,z]", help="... with the gradient along these file axes (default y)")
-    p.add_argument("--dir-stencil", default="", choices=["", "axis", "lattice"], metavar="axis|lattice", help="... as the central difference along the axis (axis, the default: Cartesian grids) or the FCC lattice's difference (lattice: FCC folders)")
-    p.add_argument("--dir-bin-ms", type=float, default=5.0, metavar="MS", help="... in time bins of MS milliseconds (default 5)")
-    p.add_argument("--dir-first", type=int, default=0, metavar="N", help="... at every step from N on (default 0)")
-    p.add_argument("--dir-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_directional.h5 in the data folder)")
-    rec_mod.add_arguments(p)
+    for kind in KINDS:
+        kind.module.add_arguments(p)
     a = p.parse_args()
-    rec_mod.check_arguments(p, a)
-    a.directional = bool(a.dir_planes or a.dir_box)
-    if a.directional != bool(a.dir_bands) or a.dir_bin_ms <= 0 or a.dir_first < 0:
-        p.error("--dir-planes / --dir-box need --dir-bands (and the other way round); --dir-bin-ms: positive, --dir-first: not negative")
-    if (a.dir_first or a.dir_file or a.dir_axes or a.dir_stencil or a.dir_bin_ms != 5.0) and not a.directional:
-        p.error("--dir-axes / --dir-stencil / --dir-bin-ms / --dir-first / --dir-file need --dir-planes or --dir-box")
-    a.dir_stencil = a.dir_stencil or "axis"
-    if a.directional and not a.dir_axes:
-        a.dir_axes = "y"
-    a.decay = bool(a.decay_planes or a.decay_box)
-    if a.decay != bool(a.decay_bands) or a.decay_bin_ms <= 0 or a.decay_first < 0:
-        p.error("--decay-planes / --decay-box need --decay-bands (and the other way round); --decay-bin-ms: positive, --decay-first: not negative")
-    if (a.decay_first or a.decay_file or a.decay_bin_ms != 5.0) and not a.decay:
-        p.error("--decay-bin-ms / --decay-first / --decay-file need --decay-planes or --decay-box")
-    a.spectrum = bool(a.spectrum_planes or a.spectrum_box)
-    if a.spectrum != bool(a.spectrum_freqs) or a.spectrum_every < 1 or a.spectrum_first < 0:
-        p.error("--spectrum-planes / --spectrum-box need --spectrum-freqs (and the other way round); --spectrum-every >= 1, --spectrum-first: not negative")
-    if (a.spectrum_first or a.spectrum_file or a.spectrum_window or a.spectrum_every != 1) and not a.spectrum:
-        p.error("--spectrum-every / --spectrum-first / --spectrum-window / --spectrum-file need --spectrum-planes or --spectrum-box")
+    for kind in reversed(KINDS):  # (p.error exits at the first refusal: recordings first, as ever)
+        kind.module.check_arguments(p, a)
     if bool(a.field_planes or a.field_box) != bool(a.field_every) or a.field_every < 0 or a.field_first < 0:
         p.error("--field-planes / --field-box need --field-every K >= 1 (and the other way round); --field-first: not negative")
     if (a.field_first or a.field_file) and not a.field_every:
@@ -542,18 +454,10 @@ def main():
     if a.checkpoint_every < 0 or (a.stop_after is not None and a.stop_after < 0):
         p.error("--checkpoint-every / --stop-after: not negative")
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world > 1 and (a.checkpoint or a.resume) and not a.devices:
-        raise SystemExit("--checkpoint / --resume: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
-    if world > 1 and a.field_every and not a.devices:
-        raise SystemExit("--field-planes / --field-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
-    if world > 1 and a.spectrum and not a.devices:
-        raise SystemExit("--spectrum-planes / --spectrum-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
-    if world > 1 and a.decay and not a.devices:
-        raise SystemExit("--decay-planes / --decay-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
-    if world > 1 and a.directional and not a.devices:
-        raise SystemExit("--dir-planes / --dir-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
-    if world > 1 and a.rec and not a.devices:
-        raise SystemExit("--rec-planes / --rec-box: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
+    fixed = [("--checkpoint / --resume", a.checkpoint or a.resume), ("--field-planes / --field-box", a.field_every)]
+    for names, asked in fixed + [(f"--{kind.prefix}-planes / --{kind.prefix}-box", getattr(a, kind.flag)) for kind in KINDS]:
+        if world > 1 and asked and not a.devices:
+            raise SystemExit(f"{names}: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
     if a.devices:
         return run_devices(a, [int(v) for v in a.devices.split(",")])
     if world > 1:

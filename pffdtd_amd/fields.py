@@ -3,7 +3,7 @@
     fw = FieldWriter(path, sd, regions, every, first=0)      regions: [(lo, hi, stride)] in FILE coordinates x, y, z
     n = fw.take(obj, n)                                      obj: a HipEngine or HipMulti that has taken the steps 0 .. n-1
 
-Frames are due at the steps first, first + every, ... below Nt.  The frame of step n is u^n -- get_region(1, ...) after run(0, n) --, the
+Frames are due at the steps first, first + every, ... below Nt (field_output.Schedule).  The frame of step n is u^n -- get_region(1, ...) after run(0, n) --, the
 field the receivers of step n sample: at a receiver's cell it equals that receiver's sample n.  The file holds
     regions           int64 [R, 9]   lo, hi, stride of every region
     steps             int64 [F]      the steps of the frames so far, rewritten after each frame
@@ -19,6 +19,7 @@ import numpy as np
 
 from . import h5io
 from .engine import PfError
+from .field_output import Schedule, normalise_regions
 
 MAX_SHIFT = 5  # steps a frame may be taken late (a triple ends within two steps, a pair within one; slabs need not agree)
 
@@ -60,15 +61,14 @@ def parse_box(spec, N):
     return tuple(lo), tuple(hi), tuple(st)
 
 
-class FieldWriter:
+class FieldWriter(Schedule):
     def __init__(self, path, sd, regions, every, first=0, resume_at=None):
         """resume_at: the step a resumed run continues at -- an existing file is appended to and keeps its frames of the steps before it"""
         self.path, self.sd = os.fspath(path), sd
-        self.regions = [tuple(tuple(int(v) for v in t) for t in r) for r in regions]
+        self.regions, table = normalise_regions(regions)
         self.every, self.first = int(every), int(first)
         if self.every < 1 or self.first < 0 or not self.regions:
             raise ValueError("FieldWriter: at least one region, every >= 1, first >= 0")
-        table = np.array([lo + hi + st for lo, hi, st in self.regions], dtype=np.int64).reshape(-1, 9)
         self.steps = []
         if resume_at is not None and os.path.exists(self.path):
             if not np.array_equal(np.asarray(h5io.read(self.path, "regions", h5io.I64)).reshape(-1, 9), table):
@@ -77,13 +77,6 @@ class FieldWriter:
         else:
             h5io.write(self.path, "regions", table, append=False)
         h5io.write(self.path, "steps", np.array(self.steps, dtype=np.int64))
-
-    def next_step(self, n):
-        """the first step >= n at which a frame is due (it may lie at or past Nt: no frame then)"""
-        return self.first if n <= self.first else self.first + -(-(n - self.first) // self.every) * self.every
-
-    def due(self, n):
-        return n < self.sd.Nt and self.next_step(n) == n
 
     def take(self, obj, n):
         """the frame of step n -- or, where a slab is inside a blocked pass there, of the first step after it at which none is; -> that step"""

@@ -15,8 +15,8 @@ to the receivers (decay.pre_sections: the integrator + low-cut as shared section
 (engine.DecimatingRecorder, pf_engine_decim_*).  After the host-side low-pass and resampling that remain, a cell's frames are what ProcessOutputs
 gives for a receiver in that cell, delayed by the FIR's (ntap - 1) / 2 samples: t0 = (first - delay) Ts.
 
-Every step from `first` on is a sample, never shifted: a chain that is recorded is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES.  Up to
-`cap` frames wait on the device; take() drains them into the file when they are `cap`.
+Every step from `first` on is a sample (FieldRecording is a field_output.FieldOutput: the schedule, take and the rules of a resume are described
+there).  Up to `cap` frames wait on the device; take() drains them into the file when they are `cap`.
 
 The file holds
     regions  int64 [R, 9]      Ts  float64      sampling  int64 [4] = first, factor, count (samples so far), frames (complete so far)
@@ -46,8 +46,8 @@ from scipy.signal import firwin, freqz, kaiserord
 
 from . import h5io
 from .decay import pre_sections
-from .directional import LATTICE_SPAN, STENCILS, fold_coordinates, gradient_sections, parse_axes
-from .engine import PfError
+from .directional import STENCILS, fold_coordinates, parse_axes, vector_setup, y_components
+from .field_output import FieldOutput
 
 MAX_SLOTS = 128  # P = ceil(ntap / factor): the outputs a recorder holds in flight (include/pffdtd_hip.h)
 DTYPES = {"f4": np.float32, "f8": np.float64}
@@ -85,12 +85,14 @@ def decimation_filter(Ts, factor, fpass_hz, atten_db=80.0):
     return np.ascontiguousarray(h, dtype=np.float64), info
 
 
-class FieldRecording:
+class FieldRecording(FieldOutput):
+    label, noun, holds, observers_noun = "field recording", "recording", "frames", "recorders"
+    recs = property(lambda self: self.observers)
+
     def __init__(self, path, sd, regions, factor, fpass_hz, atten_db=80.0, first=0, lowcut_hz=10.0, lowcut_order=4, dtype="f4", resume_at=None, cap=32, axes=None,
                  stencil="axis"):
-        self.path, self.sd = os.fspath(path), sd
-        self.regions = [tuple(tuple(int(v) for v in t) for t in r) for r in regions]
-        self.first, self.Ts, self.cap = int(first), float(sd.Ts), int(cap)
+        super().__init__(path, sd, regions, first)
+        self.cap = int(cap)
         if self.first < 0 or not self.regions or self.cap < 1:
             raise ValueError("FieldRecording: at least one region, first >= 0, cap >= 1")
         if dtype not in DTYPES:
@@ -105,45 +107,10 @@ class FieldRecording:
             if stencil != "axis":
                 raise ValueError("FieldRecording: stencil: stencil=\"lattice\" chooses the difference of the channels `axes` asks for; without axes the pressure alone is recorded")
             self.pre_sos = pre_sections(self.Ts, bool(getattr(sd, "diff", False)), float(lowcut_hz), int(lowcut_order))
-        else:
-            self._vector_setup(axes, float(lowcut_hz), int(lowcut_order))
-        self.table = np.array([lo + hi + st for lo, hi, st in self.regions], dtype=np.int64).reshape(-1, 9)
-        self.recs, self._restore, self.blocks, self._part, self._part0 = None, None, [], [], 0
-        if resume_at is not None:
-            self._restore = self._read_matching(int(resume_at))
-
-    def _vector_setup(self, axes, lowcut_hz, lowcut_order):
-        """axes: W and one figure-of-eight channel per file axis -- the components, and the sections per component as FieldDirectional stacks them"""
-        sd, stencil = self.sd, self.stencil
-        self.axes = np.ascontiguousarray(axes, dtype=np.int64).reshape(-1)
-        if self.axes.size < 1 or self.axes.size > 3 or np.any(self.axes < 1) or np.any(self.axes > 3) or len(set(self.axes.tolist())) != self.axes.size:
-            raise ValueError(f"FieldRecording: axes: {self.axes.tolist()} is not one to three different axes out of 1, 2, 3 (x, y, z)")
-        if stencil == "axis" and self.fcc_flag != 0:
-            raise ValueError("FieldRecording: fcc_flag: the central difference along an axis exists on Cartesian grids only (fcc_flag 0); an FCC grid takes "
-                             "stencil=\"lattice\", the difference over the lattice's own neighbours")
-        if stencil == "lattice" and self.fcc_flag == 0:
-            raise ValueError("FieldRecording: stencil=\"lattice\": the lattice difference exists on FCC grids only (fcc_flag 1 or 2); a Cartesian grid takes "
-                             "stencil=\"axis\"")
-        if getattr(sd, "h", None) is None or getattr(sd, "c", None) is None:
-            raise ValueError("FieldRecording: h, c: the scene's constants hold no grid spacing or speed of sound (sim_consts.h5: h, c)")
-        omni, grad = gradient_sections(self.Ts, float(sd.h), float(sd.c), bool(getattr(sd, "diff", False)), lowcut_hz, lowcut_order,
-                                       span=LATTICE_SPAN if stencil == "lattice" else 2)
-        if omni.shape[0] > 8:
-            raise ValueError(f"FieldRecording: lowcut_order: {omni.shape[0]} sections per component, a vector decimating recorder holds 8")
-        self.pre_sos = np.ascontiguousarray(np.stack([omni] + [grad] * self.axes.size))
-        self.comp = np.concatenate([[0], self.axes + (3 if stencil == "lattice" else 0)]).astype(np.int64)
-
-    # ---- the sample steps ----
-    def next_step(self, n):
-        """the first step >= n at which a sample is due (it may lie at or past Nt: no sample then)"""
-        return max(n, self.first)
-
-    def due(self, n):
-        return self.first <= n < self.sd.Nt
-
-    def samples_below(self, n):
-        """how many sample steps lie below step n"""
-        return max(0, n - self.first)
+        else:  # W and one figure-of-eight channel per file axis: the components, and the sections per component as FieldDirectional stacks them
+            self.axes, self.pre_sos, self.comp = vector_setup("FieldRecording", "vector decimating recorder", sd, axes, stencil, lowcut_hz, lowcut_order)
+        self.blocks, self._part, self._part0 = [], [], 0
+        self._resume(resume_at)
 
     # ---- the recorders ----
     def _frame_cells(self, r):
@@ -156,64 +123,48 @@ class FieldRecording:
         fr = fr * self.sd.infac
         if self.axes is not None and self.fcc_flag == 2:
             upper = fold_coordinates(self.regions[i], self.sd.Ny)[3]
-            for k, c in enumerate(self.comp.tolist()):
-                if c in (2, 5):
-                    fr[:, k][..., upper] = -fr[:, k][..., upper]
+            for k in y_components(self.comp):
+                fr[:, k][..., upper] = -fr[:, k][..., upper]
         return fr.astype(self.dtype)
+
+    def _observer(self, obj, lo, hi, st):
+        if self.axes is None:
+            return obj.decimating_recorder(lo, hi, st, pre_sos=self.pre_sos, taps=self.taps, factor=self.factor, cap=self.cap)
+        return obj.vector_decimating_recorder(lo, hi, st, comp=self.comp, pre_sos=self.pre_sos, taps=self.taps, factor=self.factor, cap=self.cap)
+
+    def _restore_observer(self, r, i, count, acc, state, nfull, part):
+        r.set_state(acc[i], state[i], count)
 
     def attach(self, obj):
         """one decimating recorder per region on obj (a HipEngine or a HipMulti); a resumed run's outputs in flight and filter state go into them.
         A new run starts the file; a resumed one keeps the blocks below its first frame."""
         if self.recs is not None:
             return
-        if self.axes is None:
-            self.recs = [obj.decimating_recorder(lo, hi, st, pre_sos=self.pre_sos, taps=self.taps, factor=self.factor, cap=self.cap) for lo, hi, st in self.regions]
-        else:
-            self.recs = [obj.vector_decimating_recorder(lo, hi, st, comp=self.comp, pre_sos=self.pre_sos, taps=self.taps, factor=self.factor, cap=self.cap)
-                         for lo, hi, st in self.regions]
+        resumed = self._restore
+        super().attach(obj)
         self._part = [np.zeros((0,) + self._frame_cells(r), dtype=self.dtype) for r in self.recs]  # the frames of the block that is not full yet, as the file stores them
         self._part0 = 0  # ... and its first frame
-        if self._restore is not None:
-            count, acc, state, nfull, part = self._restore
-            for r, a, s in zip(self.recs, acc, state):
-                r.set_state(a, s, count)
-            self.blocks, self._part0 = [k * self.cap for k in range(nfull)], nfull * self.cap
-            if part is not None:
-                self._part = [p.astype(self.dtype) for p in part]
-            self._restore = None
-            self._write_blocks(self.path, last=True)
-        else:
+        if resumed is None:
             self._write_head(self.path, append=False)
-
-    @property
-    def count(self):
-        if self.recs is None:
-            return self._restore[0] if self._restore is not None else 0
-        return self.recs[0].count
+            return
+        nfull, part = resumed[3:]
+        self.blocks, self._part0 = [k * self.cap for k in range(nfull)], nfull * self.cap
+        if part is not None:
+            self._part = [p.astype(self.dtype) for p in part]
+        self._write_blocks(self.path, last=True)
 
     @property
     def frames(self):
         """frames complete so far"""
         return -(-self.count // self.factor)
 
-    def take(self, obj, n):
-        """the sample of step n (due(n)) -- never of another step; the frames on the device go to the file first when they are `cap`"""
-        if not self.due(n):
-            raise ValueError(f"FieldRecording.take: no sample is due at step {n} (first {self.first}, Nt {self.sd.Nt})")
-        self.attach(obj)
+    def _before_sample(self):
+        """the frames on the device go to the file first when they are `cap`"""
         if self.recs[0].pending == self.cap:
             self.drain()
-        try:
-            for r in self.recs:
-                r.add()
-        except PfError as e:
-            if e.code != 4:  # (PF_ERR_STATE: a slab inside a pair or triple; no slab took the sample)
-                raise
-            err = PfError(f"field recording: step {n} cannot be sampled, a slab is inside a blocked pass there, and a sample is never shifted: "
-                          f"create the chain with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES ({e})")
-            err.code = 4
-            raise err
-        return n
+
+    def _sample(self, n):
+        return ()
 
     def drain(self):
         """the complete frames of every region from the device; whole blocks of `cap` frames go to the file.  Blocks start at multiples of `cap`
@@ -257,57 +208,44 @@ class FieldRecording:
         h5io.write(path, "design", np.array([self.info[k] for k in ("fpass", "atten", "stop_db", "ripple_db", "delay")], dtype=np.float64))
         self._write_blocks(path)
 
+    def _write_region(self, path, i, r):
+        if self._part[i].shape[0]:
+            h5io.write(path, f"r{i:03d}_f{self._part0:07d}", self._part[i])
+        acc, state = r.get_state()
+        h5io.write(path, f"r{i:03d}_acc", acc)
+        if state.size:
+            h5io.write(path, f"r{i:03d}_state", state)
+
     def write(self):
-        """the file as it stands: every complete frame, and the outputs in flight and filter state a resumed run continues from"""
-        if self.recs is None:
-            raise ValueError("FieldRecording.write: no recorders yet (attach or take first)")
+        """the file as it stands: every complete frame, and the outputs in flight and filter state a resumed run continues from.  The blocks are in
+        the file already: it is copied, not written anew"""
+        self._attached("write")
         self.drain()
         tmp = self.path + ".tmp"
         shutil.copyfile(self.path, tmp)
         self._write_head(tmp)
         self._write_blocks(tmp, last=True)
         for i, r in enumerate(self.recs):
-            if self._part[i].shape[0]:
-                h5io.write(tmp, f"r{i:03d}_f{self._part0:07d}", self._part[i])
-            acc, state = r.get_state()
-            h5io.write(tmp, f"r{i:03d}_acc", acc)
-            if state.size:
-                h5io.write(tmp, f"r{i:03d}_state", state)
+            self._write_region(tmp, i, r)
         os.replace(tmp, self.path)
 
-    def close(self):
-        for r in self.recs or []:
-            r.close()
-        self.recs = None
+    # ---- the file of a resumed run ----
+    def _read_file(self):
+        return read_file(self.path, raw=True)
 
-    def _read_matching(self, resume_at):
-        """(count, [acc per region], [state per region], the number of full blocks, [the frames of the block not full yet per region] or None) of the file a resumed run continues, or ValueError naming the field that differs"""
-        if not os.path.exists(self.path):
-            raise ValueError(f"{self.path}: no recording file to resume from")
-        f = read_file(self.path, raw=True)
-        if not np.array_equal(f["regions"], self.table):
-            raise ValueError(f"{self.path}: regions: the file holds the frames of other regions")
-        if (f["axes"] is None) != (self.axes is None) or (self.axes is not None and not np.array_equal(f["axes"], self.axes)):
-            raise ValueError(f"{self.path}: axes: the file holds the channels of axes {None if f['axes'] is None else f['axes'].tolist()}, "
-                             f"{None if self.axes is None else self.axes.tolist()} asked for")
-        if f["stencil"] != self.stencil:
-            raise ValueError(f"{self.path}: stencil: the file holds the frames of stencil=\"{f['stencil']}\", \"{self.stencil}\" is asked for")
-        if f["Ts"] != self.Ts:
-            raise ValueError(f"{self.path}: Ts: {f['Ts']!r} in the file, {self.Ts!r} in the scene")
-        first, factor, count, _ = (int(v) for v in f["sampling"])
-        if first != self.first:
-            raise ValueError(f"{self.path}: first: {first} in the file, {self.first} asked for")
-        if factor != self.factor:
-            raise ValueError(f"{self.path}: factor: {factor} in the file, {self.factor} asked for")
-        if not np.array_equal(f["taps"], self.taps):
-            raise ValueError(f"{self.path}: taps: the file's frames went through another low-pass (fpass, atten)")
-        if h5io._CODE_TO_NP[f["frame_code"]] != self.dtype:
-            raise ValueError(f"{self.path}: dtype: the file's frames are {np.dtype(h5io._CODE_TO_NP[f['frame_code']]).name}, {np.dtype(self.dtype).name} asked for")
-        if not np.array_equal(f["pre_sos"], self.pre_sos):
-            raise ValueError(f"{self.path}: pre_sos: the file's frames went through other sections (low-cut, integrator, grid spacing)")
-        if count != self.samples_below(resume_at):
-            raise ValueError(f"{self.path}: count: the file holds {count} samples, {self.samples_below(resume_at)} sample steps lie below step {resume_at}")
-        done = -(-count // factor)  # frames complete at the resumed step; blocks at or beyond it are a later run's
+    def _checks(self, f):
+        theirs, mine = h5io._CODE_TO_NP[f["frame_code"]], self.dtype
+        return [("axes", (f["axes"] is None) == (self.axes is None) and (self.axes is None or np.array_equal(f["axes"], self.axes)),
+                 f"the file holds the channels of axes {None if f['axes'] is None else f['axes'].tolist()}, {None if self.axes is None else self.axes.tolist()} asked for"),
+                ("stencil", f["stencil"] == self.stencil, f"the file holds the frames of stencil=\"{f['stencil']}\", \"{self.stencil}\" is asked for"),
+                *self._same_clock(f), self._asked("factor", f["sampling"][1], self.factor),
+                ("taps", np.array_equal(f["taps"], self.taps), "the file's frames went through another low-pass (fpass, atten)"),
+                ("dtype", theirs == mine, f"the file's frames are {np.dtype(theirs).name}, {np.dtype(mine).name} asked for"),
+                ("pre_sos", np.array_equal(f["pre_sos"], self.pre_sos), "the file's frames went through other sections (low-cut, integrator, grid spacing)")]
+
+    def _saved(self, f, count):
+        """(count, [acc per region], [state per region], the number of full blocks, [the frames of the block not full yet per region] or None)"""
+        done = -(-count // self.factor)  # frames complete at the resumed step; blocks at or beyond it are a later run's
         nfull, have = done // self.cap, [int(b) for b in f["blocks"] if b < done]
         if have != [k * self.cap for k in range(-(-done // self.cap))]:
             raise ValueError(f"{self.path}: blocks: the file's blocks {have} are not those of {done} frames in blocks of cap = {self.cap}")

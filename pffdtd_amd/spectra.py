@@ -19,7 +19,8 @@ every = 3 and runs of three steps between the samples (an accumulator answers be
 while no slab is inside a pair or triple and `take` NEVER shifts the step -- a DFT over unevenly spaced samples is not the DFT the file
 promises --: a chain that is sampled is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES.
 
-The file (write(): written to a temporary name and moved into place with os.replace, so a reader never sees half of it) holds
+FieldSpectrum is a field_output.FieldOutput: the schedule, the accumulators of the regions, take, write and the rules of a resume are described there.
+The file holds
     regions   int64 [R, 9]     lo, hi, stride of every region
     freqs     float64 [K]      Ts   float64      sampling  int64 [3] = first, every, count (samples summed so far)      window  int64 (0 none, 1 hann)
     r{i:03d}_re, r{i:03d}_im   float64 [K, c0, c1, c2] of region i: acc * sd.infac, a single multiplication (the factor SimData.rescale_output
@@ -30,12 +31,10 @@ beside the scaled ones (r{i:03d}_acc float64 [2K, c0, c1, c2]: a division by inf
 the new accumulators and the run goes on to the sums of a run in one piece.
 The command line's --spectrum-freqs is parsed here: host code, no device.
 """
-import os
-
 import numpy as np
 
 from . import h5io
-from .engine import PfError
+from .field_output import FieldOutput
 
 WINDOWS = {None: 0, "none": 0, "hann": 1}
 
@@ -58,12 +57,14 @@ def parse_freqs(spec):
     return f
 
 
-class FieldSpectrum:
+class FieldSpectrum(FieldOutput):
+    label, noun, holds, observers_noun = "field spectrum", "spectra", "sums", "accumulators"
+    accs = property(lambda self: self.observers)
+
     def __init__(self, path, sd, regions, freqs, every=1, first=0, window=None, resume_at=None):
-        self.path, self.sd = os.fspath(path), sd
-        self.regions = [tuple(tuple(int(v) for v in t) for t in r) for r in regions]
+        super().__init__(path, sd, regions, first)
         self.freqs = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
-        self.every, self.first = int(every), int(first)
+        self.every = int(every)
         if window not in WINDOWS:
             raise ValueError(f"FieldSpectrum: window = {window!r} is neither None nor 'hann'")
         self.window = WINDOWS[window]
@@ -71,28 +72,12 @@ class FieldSpectrum:
             raise ValueError("FieldSpectrum: at least one region and one frequency, every >= 1, first >= 0")
         if 2 * self.freqs.size > 256:
             raise ValueError(f"FieldSpectrum: freqs: {self.freqs.size} frequencies, an accumulator holds 128 (256 channels)")
-        self.Ts = float(sd.Ts)
         nyq = 1.0 / (2.0 * self.every * self.Ts)
         if np.any(self.freqs < 0) or np.any(self.freqs >= nyq):
             raise ValueError(f"FieldSpectrum: freqs: every frequency must lie in [0, 1 / (2 * every * Ts)) = [0, {nyq:g}) Hz: samples every {self.every} "
                              f"step(s) cannot tell {float(self.freqs.max()):g} Hz from its alias")
         self.nsamples = self.samples_below(sd.Nt)  # of the whole run: the Hann window's length
-        self.table = np.array([lo + hi + st for lo, hi, st in self.regions], dtype=np.int64).reshape(-1, 9)
-        self.accs, self._restore = None, None
-        if resume_at is not None:
-            self._restore = self._read_matching(int(resume_at))
-
-    # ---- the sample steps ----
-    def next_step(self, n):
-        """the first step >= n at which a sample is due (it may lie at or past Nt: no sample then)"""
-        return self.first if n <= self.first else self.first + -(-(n - self.first) // self.every) * self.every
-
-    def due(self, n):
-        return n < self.sd.Nt and self.next_step(n) == n
-
-    def samples_below(self, n):
-        """how many sample steps lie below step n"""
-        return 0 if n <= self.first else -(-(n - self.first) // self.every)
+        self._resume(resume_at)
 
     def weights(self, n):
         """float64 [2K]: g(n) cos(phi_k), -g(n) sin(phi_k) of step n, phi_k = 2 pi ((freqs[k] * Ts * n) mod 1.0)"""
@@ -106,84 +91,40 @@ class FieldSpectrum:
         w[1::2] = -(g * np.sin(phi))
         return w
 
-    # ---- the sums ----
-    def attach(self, obj):
-        """one accumulator per region on obj (a HipEngine or a HipMulti); a resumed run's sums go into them"""
-        if self.accs is not None:
-            return
-        self.accs = [obj.accumulator(lo, hi, st, nchan=2 * self.freqs.size) for lo, hi, st in self.regions]
-        if self._restore is not None:
-            count, sums = self._restore
-            for a, s in zip(self.accs, sums):
-                a.set(s, count)
-            self._restore = None
+    # ---- what FieldOutput asks of a kind ----
+    def _observer(self, obj, lo, hi, st):
+        return obj.accumulator(lo, hi, st, nchan=2 * self.freqs.size)
 
-    @property
-    def count(self):
-        if self.accs is None:
-            return self._restore[0] if self._restore is not None else 0
-        return self.accs[0].count
+    def _restore_observer(self, a, i, count, sums):
+        a.set(sums[i], count)
 
-    def take(self, obj, n):
-        """the sample of step n (due(n)) -- never of another step"""
-        if not self.due(n):
-            raise ValueError(f"FieldSpectrum.take: no sample is due at step {n} (first {self.first}, every {self.every}, Nt {self.sd.Nt})")
-        self.attach(obj)
-        w = self.weights(n)
-        try:
-            for a in self.accs:
-                a.add(w)
-        except PfError as e:
-            if e.code != 4:  # (PF_ERR_STATE: a slab inside a pair or triple; no slab took the sample)
-                raise
-            err = PfError(f"field spectrum: step {n} cannot be sampled, a slab is inside a blocked pass there, and a sample is never shifted: "
-                          f"create the chain with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES ({e})")
-            err.code = 4
-            raise err
-        return n
+    def _due_rule(self):
+        return f"first {self.first}, every {self.every}"
 
-    def write(self):
-        """the file as it stands: every region's sums so far"""
-        if self.accs is None:
-            raise ValueError("FieldSpectrum.write: no accumulators yet (attach or take first)")
-        tmp = self.path + ".tmp"
-        h5io.write(tmp, "regions", self.table, append=False)
-        h5io.write(tmp, "freqs", self.freqs)
-        h5io.write(tmp, "Ts", np.float64(self.Ts))
-        h5io.write(tmp, "sampling", np.array([self.first, self.every, self.count], dtype=np.int64))
-        h5io.write(tmp, "window", np.int64(self.window))
-        for i, a in enumerate(self.accs):
-            acc = a.get()
-            h5io.write(tmp, f"r{i:03d}_acc", acc)
-            h5io.write(tmp, f"r{i:03d}_re", acc[0::2] * self.sd.infac)
-            h5io.write(tmp, f"r{i:03d}_im", acc[1::2] * self.sd.infac)
-        os.replace(tmp, self.path)
+    def _sample(self, n):
+        return (self.weights(n),)
 
-    def close(self):
-        for a in self.accs or []:
-            a.close()
-        self.accs = None
+    def _write_head(self, path, append):
+        h5io.write(path, "regions", self.table, append=append)
+        h5io.write(path, "freqs", self.freqs)
+        h5io.write(path, "Ts", np.float64(self.Ts))
+        h5io.write(path, "sampling", np.array([self.first, self.every, self.count], dtype=np.int64))
+        h5io.write(path, "window", np.int64(self.window))
 
-    def _read_matching(self, resume_at):
-        """(count, [raw sums per region]) of the file a resumed run continues, or ValueError naming the field that differs"""
-        if not os.path.exists(self.path):
-            raise ValueError(f"{self.path}: no spectra file to resume from")
-        f = read(self.path, raw=True)
-        if not np.array_equal(f["regions"], self.table):
-            raise ValueError(f"{self.path}: regions: the file holds the sums of other regions")
-        if not np.array_equal(f["freqs"], self.freqs):
-            raise ValueError(f"{self.path}: freqs: the file holds the sums of other frequencies")
-        if f["Ts"] != self.Ts:
-            raise ValueError(f"{self.path}: Ts: {f['Ts']!r} in the file, {self.Ts!r} in the scene")
-        first, every, count = (int(v) for v in f["sampling"])
-        if first != self.first:
-            raise ValueError(f"{self.path}: first: {first} in the file, {self.first} asked for")
-        if every != self.every:
-            raise ValueError(f"{self.path}: every: {every} in the file, {self.every} asked for")
-        if f["window"] != self.window:
-            raise ValueError(f"{self.path}: window: {f['window']} in the file, {self.window} asked for (0 none, 1 hann)")
-        if count != self.samples_below(resume_at):
-            raise ValueError(f"{self.path}: count: the file holds {count} samples, {self.samples_below(resume_at)} sample steps lie below step {resume_at}")
+    def _write_region(self, path, i, a):
+        acc = a.get()
+        h5io.write(path, f"r{i:03d}_acc", acc)
+        h5io.write(path, f"r{i:03d}_re", acc[0::2] * self.sd.infac)
+        h5io.write(path, f"r{i:03d}_im", acc[1::2] * self.sd.infac)
+
+    def _read_file(self):
+        return read(self.path, raw=True)
+
+    def _checks(self, f):
+        return [self._other(f, "freqs", "frequencies"), *self._same_clock(f), self._asked("every", f["sampling"][1], self.every),
+                self._asked("window", f["window"], self.window, " (0 none, 1 hann)")]
+
+    def _saved(self, f, count):
         return count, f["acc"]
 
 
@@ -196,3 +137,23 @@ def read(path, raw=False):
     for key in ("re", "im") + (("acc",) if raw else ()):
         out[key] = [np.asarray(h5io.read(path, f"r{i:03d}_{key}", h5io.F64)) for i in range(len(regions))]
     return out
+
+
+def add_arguments(p):
+    """the --spectrum-* arguments of the command line"""
+    p.add_argument("--spectrum-planes", action="append", default=[], metavar="x=I,y=J,z=K", help="sum the DFT of these planes of the field on the device (the syntax of --field-planes)")
+    p.add_argument("--spectrum-box", action="append", default=[], metavar="x0:x1:sx,y0:y1:sy,z0:z1:sz", help="... of this strided box")
+    p.add_argument("--spectrum-freqs", default="", metavar="F1,F2,... | LO:HI:N", help="... at these frequencies in Hz (LO:HI:N: N of them, linearly spaced)")
+    p.add_argument("--spectrum-every", type=int, default=1, metavar="K", help="... sampling every K steps (default 1; content above 1 / (2 K Ts) aliases)")
+    p.add_argument("--spectrum-first", type=int, default=0, metavar="N", help="... from step N on (default 0)")
+    p.add_argument("--spectrum-window", default=None, choices=["hann"], help="... under a window over the sample steps (default: none)")
+    p.add_argument("--spectrum-file", default="", metavar="FILE", help="... into this HDF5 file (default: sim_spectra.h5 in the data folder)")
+
+
+def check_arguments(p, a):
+    """a.spectrum: is a spectrum asked for?  Regions without --spectrum-freqs, and any --spectrum-* without a region, are refused"""
+    a.spectrum = bool(a.spectrum_planes or a.spectrum_box)
+    if a.spectrum != bool(a.spectrum_freqs) or a.spectrum_every < 1 or a.spectrum_first < 0:
+        p.error("--spectrum-planes / --spectrum-box need --spectrum-freqs (and the other way round); --spectrum-every >= 1, --spectrum-first: not negative")
+    if (a.spectrum_first or a.spectrum_file or a.spectrum_window or a.spectrum_every != 1) and not a.spectrum:
+        p.error("--spectrum-every / --spectrum-first / --spectrum-window / --spectrum-file need --spectrum-planes or --spectrum-box")
