@@ -22,6 +22,9 @@
 // coef[...] and bins[...] do not depend on the lane: scalar loads.  No atomics, no LDS, no scratch (tools/kernel_resources.py k_band).  64-bit
 // indices, every access guarded by the cell count (c even and c < cells, so c + 1 < cstride).
 //
+// The host side is the vector band accumulators' (pf_engine_vband.inc: VBand with one component and one product, whose S, st, coef and ring are
+// the arrays above); band_section is also pf_vband.h's and pf_vdecim.h's.
+//
 // PF_BAND_DEFAULT_DEPTH: the fastest of the measured depths 1, 4, 8, 16 on the plane cases of tools/field_decay_cost.py (profiles/field_decay.txt).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -69,13 +69,12 @@ struct pf_vdecim : pf_observer { // frames are [ncomp][cells], acc [ncomp][P][ce
    int64_t factor = 1, cap = 0, rd = 0;
 };
 // pf_engine_*_get / _set / _read / _get_state / _set_state with the caller's region rows `pitch` and channel / sum / state / frame / acc rows `rowstride`
-// doubles apart (0: dense) -- a slab's cells of a chain's arrays; count: as given.  The recorders': `a` is a pf_decim (scalar) or a pf_vdecim.
+// doubles apart (0: dense) -- a slab's cells of a chain's arrays; count: as given.  The band accumulators': `a` is a pf_bandacc (scalar) or a pf_vbandacc; the
+// recorders': a pf_decim (scalar) or a pf_vdecim.
 int pf__engine_accum_get_x(pf_engine *e, pf_accum *a, double *host, int64_t pitch, int64_t chstride);
 int pf__engine_accum_set_x(pf_engine *e, pf_accum *a, const double *host, int64_t pitch, int64_t chstride, int64_t count);
-int pf__engine_bandacc_get_x(pf_engine *e, pf_bandacc *a, double *sums, double *state, int64_t pitch, int64_t rowstride);
-int pf__engine_bandacc_set_x(pf_engine *e, pf_bandacc *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride, int64_t count);
-int pf__engine_vband_get_x(pf_engine *e, pf_vbandacc *a, double *sums, double *state, int64_t pitch, int64_t rowstride);
-int pf__engine_vband_set_x(pf_engine *e, pf_vbandacc *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride, int64_t count);
+int pf__engine_bands_get_x(pf_engine *e, pf_observer *a, bool scalar, double *sums, double *state, int64_t pitch, int64_t rowstride);
+int pf__engine_bands_set_x(pf_engine *e, pf_observer *a, bool scalar, const double *sums, const double *state, int64_t pitch, int64_t rowstride, int64_t count);
 int pf__engine_rec_read_x(pf_engine *e, pf_observer *a, bool scalar, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride);
 int pf__engine_rec_get_state_x(pf_engine *e, pf_observer *a, bool scalar, double *acc, double *state, int64_t pitch, int64_t rowstride);
 int pf__engine_rec_set_state_x(pf_engine *e, pf_observer *a, bool scalar, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count);

@@ -190,7 +190,10 @@ template <typename T> static void rec_numbers(const T *a, int64_t *count, int64_
    if (a->chain) { *count = a->count; *pending = (a->count + a->factor - 1) / a->factor - a->rd; }
    else if (a->eng && a->eng->impl) a->eng->impl->vdecim_info(T::kind == pfeng::OBS_DECIM, a->impl, count, pending);
 }
-#define PF_REC(scalar, fn) const char *what = (scalar) ? "pf_engine_decim_" fn : "pf_engine_vdecim_" fn; const int kind = (scalar) ? pfeng::OBS_DECIM : pfeng::OBS_VDECIM
+// a kind with a scalar and a vector form: the public function's name and the handle's kind
+#define PF_TWO(scalar, s, v, S, V, fn) const char *what = (scalar) ? "pf_engine_" s "_" fn : "pf_engine_" v "_" fn; const int kind = (scalar) ? pfeng::S : pfeng::V
+#define PF_BANDS(scalar, fn) PF_TWO(scalar, "bandacc", "vband", OBS_BAND, OBS_VBAND, fn)
+#define PF_REC(scalar, fn) PF_TWO(scalar, "decim", "vdecim", OBS_DECIM, OBS_VDECIM, fn)
 
 // internal (pf_multi.hip): a slab's cells of a chain's arrays
 int pf__engine_accum_get_x(pf_engine *e, pf_accum *a, double *host, int64_t pitch, int64_t chstride) {
@@ -200,19 +203,18 @@ int pf__engine_accum_get_x(pf_engine *e, pf_accum *a, double *host, int64_t pitc
 int pf__engine_accum_set_x(pf_engine *e, pf_accum *a, const double *host, int64_t pitch, int64_t chstride, int64_t count) {
    return set_counted(e, a, pfeng::OBS_ACCUM, "pf_engine_accum_set", count, [&] { return e->impl->accum_set(a->impl, host, pitch, chstride); });
 }
-int pf__engine_bandacc_get_x(pf_engine *e, pf_bandacc *a, double *sums, double *state, int64_t pitch, int64_t rowstride) {
-   const int rc = mine(e, a, pfeng::OBS_BAND, "pf_engine_bandacc_get");
-   return rc ? rc : e->impl->band_get(a->impl, sums, state, pitch, rowstride);
+int pf__engine_bands_get_x(pf_engine *e, pf_observer *a, bool scalar, double *sums, double *state, int64_t pitch, int64_t rowstride) {
+   PF_BANDS(scalar, "get");
+   const int rc = mine(e, a, kind, what);
+   return rc ? rc : e->impl->vband_get(what, scalar, a->impl, sums, state, pitch, rowstride);
 }
-int pf__engine_bandacc_set_x(pf_engine *e, pf_bandacc *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride, int64_t count) {
-   return set_counted(e, a, pfeng::OBS_BAND, "pf_engine_bandacc_set", count, [&] { return e->impl->band_set(a->impl, sums, state, pitch, rowstride); });
+int pf__engine_bands_set_x(pf_engine *e, pf_observer *a, bool scalar, const double *sums, const double *state, int64_t pitch, int64_t rowstride, int64_t count) {
+   PF_BANDS(scalar, "set");
+   return set_counted(e, a, kind, what, count, [&] { return e->impl->vband_set(what, scalar, a->impl, sums, state, pitch, rowstride); });
 }
-int pf__engine_vband_get_x(pf_engine *e, pf_vbandacc *a, double *sums, double *state, int64_t pitch, int64_t rowstride) {
-   const int rc = mine(e, a, pfeng::OBS_VBAND, "pf_engine_vband_get");
-   return rc ? rc : e->impl->vband_get(a->impl, sums, state, pitch, rowstride);
-}
-int pf__engine_vband_set_x(pf_engine *e, pf_vbandacc *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride, int64_t count) {
-   return set_counted(e, a, pfeng::OBS_VBAND, "pf_engine_vband_set", count, [&] { return e->impl->vband_set(a->impl, sums, state, pitch, rowstride); });
+static int bands_add(pf_engine *e, pf_observer *a, bool scalar, int64_t bin) {
+   PF_BANDS(scalar, "add");
+   return add_counted(e, a, kind, what, [&] { return e->impl->vband_add(what, scalar, a->impl, bin); });
 }
 int pf__engine_rec_read_x(pf_engine *e, pf_observer *a, bool scalar, double *frames, int64_t max_frames, int64_t *first, int64_t *nread, int64_t pitch, int64_t rowstride) {
    PF_REC(scalar, "read");
@@ -235,6 +237,8 @@ static int rec_add(pf_engine *e, pf_observer *a, bool scalar) {
    return rc ? rc : e->impl->vdecim_add(what, scalar, a->impl);
 }
 #undef PF_REC
+#undef PF_BANDS
+#undef PF_TWO
 int pf__engine_between_runs(pf_engine *e) { return e && e->impl && e->impl->between_runs() ? 1 : 0; }
 
 extern "C" {
@@ -259,32 +263,32 @@ int pf_engine_accum_set(pf_engine *e, pf_accum *a, const double *host, int64_t c
 int64_t pf_accum_count(const pf_accum *a) { return a ? a->count : -1; }
 int pf_engine_accum_destroy(pf_engine *e, pf_accum *a) { return destroy(e, a, pfeng::OBS_ACCUM, "pf_engine_accum_destroy"); }
 
+// the scalar band accumulator is the vector one with the one component 0, the one product (0, 0, 0) and a handle type of its own
 int pf_engine_bandacc_create(pf_engine *e, const pf_region *r, int32_t npre, const double *pre_sos, int32_t nband, int32_t nsec, const double *band_sos, int64_t nbin,
                              int32_t depth, pf_bandacc **out) {
-   const int rc = create(e, "pf_engine_bandacc_create", r, out, [&](void **impl) { return e->impl->band_create(r, npre, pre_sos, nband, nsec, band_sos, nbin, depth, impl); });
+   static const int32_t cell[1] = {0}, square[3] = {0, 0, 0};
+   const char *what = "pf_engine_bandacc_create";
+   const int rc = create(e, what, r, out, [&](void **impl) { return e->impl->vband_create(what, true, r, 1, cell, npre, pre_sos, nband, nsec, band_sos, 1, square, nbin, depth, impl); });
    if (rc == PF_OK) (*out)->nbin = nbin;
    return rc;
 }
-int pf_engine_bandacc_add(pf_engine *e, pf_bandacc *a, int64_t bin) {
-   return add_counted(e, a, pfeng::OBS_BAND, "pf_engine_bandacc_add", [&] { return e->impl->band_add(a->impl, bin); });
-}
-int pf_engine_bandacc_get(pf_engine *e, pf_bandacc *a, double *sums, double *state) { return pf__engine_bandacc_get_x(e, a, sums, state, 0, 0); }
-int pf_engine_bandacc_set(pf_engine *e, pf_bandacc *a, const double *sums, const double *state, int64_t count) { return pf__engine_bandacc_set_x(e, a, sums, state, 0, 0, count); }
+int pf_engine_bandacc_add(pf_engine *e, pf_bandacc *a, int64_t bin) { return bands_add(e, a, true, bin); }
+int pf_engine_bandacc_get(pf_engine *e, pf_bandacc *a, double *sums, double *state) { return pf__engine_bands_get_x(e, a, true, sums, state, 0, 0); }
+int pf_engine_bandacc_set(pf_engine *e, pf_bandacc *a, const double *sums, const double *state, int64_t count) { return pf__engine_bands_set_x(e, a, true, sums, state, 0, 0, count); }
 int64_t pf_bandacc_count(const pf_bandacc *a) { return a ? a->count : -1; }
 int pf_engine_bandacc_destroy(pf_engine *e, pf_bandacc *a) { return destroy(e, a, pfeng::OBS_BAND, "pf_engine_bandacc_destroy"); }
 
 int pf_engine_vband_create(pf_engine *e, const pf_region *r, int32_t ncomp, const int32_t *comp, int32_t npre, const double *pre_sos, int32_t nband, int32_t nsec,
                            const double *band_sos, int32_t nprod, const int32_t *prod, int64_t nbin, int32_t depth, pf_vbandacc **out) {
-   const int rc = create(e, "pf_engine_vband_create", r, out,
-                         [&](void **impl) { return e->impl->vband_create(r, ncomp, comp, npre, pre_sos, nband, nsec, band_sos, nprod, prod, nbin, depth, impl); });
+   const char *what = "pf_engine_vband_create";
+   const int rc = create(e, what, r, out,
+                         [&](void **impl) { return e->impl->vband_create(what, false, r, ncomp, comp, npre, pre_sos, nband, nsec, band_sos, nprod, prod, nbin, depth, impl); });
    if (rc == PF_OK) (*out)->nbin = nbin;
    return rc;
 }
-int pf_engine_vband_add(pf_engine *e, pf_vbandacc *a, int64_t bin) {
-   return add_counted(e, a, pfeng::OBS_VBAND, "pf_engine_vband_add", [&] { return e->impl->vband_add(a->impl, bin); });
-}
-int pf_engine_vband_get(pf_engine *e, pf_vbandacc *a, double *sums, double *state) { return pf__engine_vband_get_x(e, a, sums, state, 0, 0); }
-int pf_engine_vband_set(pf_engine *e, pf_vbandacc *a, const double *sums, const double *state, int64_t count) { return pf__engine_vband_set_x(e, a, sums, state, 0, 0, count); }
+int pf_engine_vband_add(pf_engine *e, pf_vbandacc *a, int64_t bin) { return bands_add(e, a, false, bin); }
+int pf_engine_vband_get(pf_engine *e, pf_vbandacc *a, double *sums, double *state) { return pf__engine_bands_get_x(e, a, false, sums, state, 0, 0); }
+int pf_engine_vband_set(pf_engine *e, pf_vbandacc *a, const double *sums, const double *state, int64_t count) { return pf__engine_bands_set_x(e, a, false, sums, state, 0, 0, count); }
 int64_t pf_vbandacc_count(const pf_vbandacc *a) { return a ? a->count : -1; }
 int pf_engine_vband_destroy(pf_engine *e, pf_vbandacc *a) { return destroy(e, a, pfeng::OBS_VBAND, "pf_engine_vband_destroy"); }
 

@@ -62,15 +62,12 @@ struct EngineBase {
    virtual int accum_add(void *a, const double *w) = 0;
    virtual int accum_get(void *a, double *host, int64_t pitch, int64_t chstride) = 0;
    virtual int accum_set(void *a, const double *host, int64_t pitch, int64_t chstride) = 0;
-   virtual int band_create(const pf_region *r, int npre, const double *pre_sos, int nband, int nsec, const double *band_sos, int64_t nbin, int depth, void **out) = 0; // band accumulators (pf_engine_band.inc)
-   virtual int band_add(void *a, int64_t bin) = 0;
-   virtual int band_get(void *a, double *sums, double *state, int64_t pitch, int64_t rowstride) = 0;
-   virtual int band_set(void *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride) = 0;
-   virtual int vband_create(const pf_region *r, int ncomp, const int32_t *comp, int npre, const double *pre_sos, int nband, int nsec, const double *band_sos, int nprod,
-                            const int32_t *prod, int64_t nbin, int depth, void **out) = 0; // vector band accumulators (pf_engine_vband.inc)
-   virtual int vband_add(void *a, int64_t bin) = 0;
-   virtual int vband_get(void *a, double *sums, double *state, int64_t pitch, int64_t rowstride) = 0;
-   virtual int vband_set(void *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride) = 0;
+   // the band accumulators, scalar (`scalar`: the handle is a pf_bandacc, ncomp = 1, comp = {0}, nprod = 1, prod = {0, 0, 0}) and vector (pf_engine_vband.inc); what: the public function's name
+   virtual int vband_create(const char *what, bool scalar, const pf_region *r, int ncomp, const int32_t *comp, int npre, const double *pre_sos, int nband, int nsec,
+                            const double *band_sos, int nprod, const int32_t *prod, int64_t nbin, int depth, void **out) = 0;
+   virtual int vband_add(const char *what, bool scalar, void *a, int64_t bin) = 0;
+   virtual int vband_get(const char *what, bool scalar, void *a, double *sums, double *state, int64_t pitch, int64_t rowstride) = 0;
+   virtual int vband_set(const char *what, bool scalar, void *a, const double *sums, const double *state, int64_t pitch, int64_t rowstride) = 0;
    // the decimating recorders, scalar (`scalar`: the handle is a pf_decim, ncomp = 1, comp = {0}) and vector (pf_engine_vdecim.inc); what: the public function's name
    virtual int vdecim_create(const char *what, bool scalar, const pf_region *r, int ncomp, const int32_t *comp, int npre, const double *pre_sos, int ntap, const double *taps,
                              int factor, int64_t cap, int depth, void **out) = 0;
@@ -1102,7 +1099,6 @@ template <typename Real> struct Engine : EngineBase {
 #include "pf_engine_region.inc"
 #include "pf_engine_observe.inc"
 #include "pf_engine_accum.inc"
-#include "pf_engine_band.inc"
 #include "pf_engine_vband.inc"
 #include "pf_engine_vdecim.inc"
    void *stream(int which) override { return which == 1 ? (void *)s_edge : (void *)s_main; }

@@ -1,6 +1,6 @@
 // pf_engine_observe.inc -- part of `template <typename Real> struct Engine` (pf_engine_class.inc includes it INSIDE the class body, before the kinds;
-// not a translation unit): what the region observers share -- the field accumulators (pf_engine_accum.inc), the band accumulators
-// (pf_engine_band.inc), the vector band accumulators (pf_engine_vband.inc) and the decimating recorders, scalar and vector (pf_engine_vdecim.inc).
+// not a translation unit): what the region observers share -- the field accumulators (pf_engine_accum.inc), the band accumulators,
+// scalar and vector (pf_engine_vband.inc) and the decimating recorders, scalar and vector (pf_engine_vdecim.inc).
 // An observer samples up to four components of u^n over a pf_region -- the cell itself, or a difference -- into the next slot of its ring, folds a
 // full ring on the device with its kind's kernels, and moves rows of doubles to and from the caller's arrays.  Here: the one list that owns them,
 // the lookup by handle and kind, what every call checks first, the component rules, the sample, and the row copies.

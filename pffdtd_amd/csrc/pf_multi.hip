@@ -1206,20 +1206,20 @@ template <typename H> int chain_destroy(pf_multi *m, H *a, const char *what, int
    return rc;
 }
 
-// the two kinds of band accumulator (H: pf_bandacc, pf_vbandacc) and of recorder (H: pf_decim -- scalar --, pf_vdecim): all but create
+// the two kinds of band accumulator (H: pf_bandacc -- scalar --, pf_vbandacc) and of recorder (H: pf_decim -- scalar --, pf_vdecim): all but create
 template <typename H> int bands_add(pf_multi *m, H *a, const char *what, int64_t bin, int (*add)(pf_engine *, H *, int64_t)) {
    return chain_add(m, a, what, [&] { return bin < -1 || bin >= a->nbin ? failv(PF_ERR_ARG, "%s: bin = %ld outside -1 .. %ld", what, (long)bin, (long)a->nbin - 1) : (int)PF_OK; },
                     none, [=](pf_engine *e, H *part) { return add(e, part, bin); });
 }
-template <typename H> int bands_get(pf_multi *m, H *a, const char *what, double *sums, double *state, int (*get)(pf_engine *, H *, double *, double *, int64_t, int64_t)) {
-   return chain_rows(m, a, what, false, [&] { return sums ? (int)PF_OK : fail("%s: null sums array", what); },
-                     [&](pf_engine *e, H *part, int64_t off, int64_t pitch) { return get(e, part, at(sums, off), at(state, off), pitch, a->cells); });
+template <typename H> int bands_get(pf_multi *m, H *a, const char *what, double *sums, double *state) {
+   return chain_rows(m, a, what, false, [&] { return sums ? (int)PF_OK : fail("%s: null sums array", what); }, [&](pf_engine *e, H *part, int64_t off, int64_t pitch) {
+      return pf__engine_bands_get_x(e, part, H::kind == pfeng::OBS_BAND, at(sums, off), at(state, off), pitch, a->cells);
+   });
 }
-template <typename H>
-int bands_set(pf_multi *m, H *a, const char *what, const double *sums, const double *state, int64_t count,
-              int (*set)(pf_engine *, H *, const double *, const double *, int64_t, int64_t, int64_t)) {
-   const int rc = chain_rows(m, a, what, true, [&] { return count < 0 ? fail("%s: count < 0", what) : (int)PF_OK; },
-                             [&](pf_engine *e, H *part, int64_t off, int64_t pitch) { return set(e, part, at(sums, off), at(state, off), pitch, a->cells, count); });
+template <typename H> int bands_set(pf_multi *m, H *a, const char *what, const double *sums, const double *state, int64_t count) {
+   const int rc = chain_rows(m, a, what, true, [&] { return count < 0 ? fail("%s: count < 0", what) : (int)PF_OK; }, [&](pf_engine *e, H *part, int64_t off, int64_t pitch) {
+      return pf__engine_bands_set_x(e, part, H::kind == pfeng::OBS_BAND, at(sums, off), at(state, off), pitch, a->cells, count);
+   });
    if (rc == PF_OK) a->count = count;
    return rc;
 }
@@ -1328,12 +1328,12 @@ int pf_multi_bandacc_add(pf_multi *m, pf_bandacc *a, int64_t bin) {
 int pf_multi_bandacc_get(pf_multi *m, pf_bandacc *a, double *sums, double *state) {
    const char *what = "pf_multi_bandacc_get";
    PF_ACCUM_ENTER(what)
-   return S.G == 1 ? pf_engine_bandacc_get(S.eng[0], a, sums, state) : bands_get(m, a, what, sums, state, pf__engine_bandacc_get_x);
+   return S.G == 1 ? pf_engine_bandacc_get(S.eng[0], a, sums, state) : bands_get(m, a, what, sums, state);
 }
 int pf_multi_bandacc_set(pf_multi *m, pf_bandacc *a, const double *sums, const double *state, int64_t count) {
    const char *what = "pf_multi_bandacc_set";
    PF_ACCUM_ENTER(what)
-   return S.G == 1 ? pf_engine_bandacc_set(S.eng[0], a, sums, state, count) : bands_set(m, a, what, sums, state, count, pf__engine_bandacc_set_x);
+   return S.G == 1 ? pf_engine_bandacc_set(S.eng[0], a, sums, state, count) : bands_set(m, a, what, sums, state, count);
 }
 int pf_multi_bandacc_destroy(pf_multi *m, pf_bandacc *a) {
    const char *what = "pf_multi_bandacc_destroy";
@@ -1362,12 +1362,12 @@ int pf_multi_vband_add(pf_multi *m, pf_vbandacc *a, int64_t bin) {
 int pf_multi_vband_get(pf_multi *m, pf_vbandacc *a, double *sums, double *state) {
    const char *what = "pf_multi_vband_get";
    PF_ACCUM_ENTER(what)
-   return S.G == 1 ? pf_engine_vband_get(S.eng[0], a, sums, state) : bands_get(m, a, what, sums, state, pf__engine_vband_get_x);
+   return S.G == 1 ? pf_engine_vband_get(S.eng[0], a, sums, state) : bands_get(m, a, what, sums, state);
 }
 int pf_multi_vband_set(pf_multi *m, pf_vbandacc *a, const double *sums, const double *state, int64_t count) {
    const char *what = "pf_multi_vband_set";
    PF_ACCUM_ENTER(what)
-   return S.G == 1 ? pf_engine_vband_set(S.eng[0], a, sums, state, count) : bands_set(m, a, what, sums, state, count, pf__engine_vband_set_x);
+   return S.G == 1 ? pf_engine_vband_set(S.eng[0], a, sums, state, count) : bands_set(m, a, what, sums, state, count);
 }
 int pf_multi_vband_destroy(pf_multi *m, pf_vbandacc *a) {
    const char *what = "pf_multi_vband_destroy";

@@ -1,19 +1,23 @@
-// pf_vband.h -- device side of the vector band accumulators (include/pffdtd_hip.h: pf_vbandacc): per cell of a region, up to four COMPONENTS of
-// the field -- the cell itself (0) or the central difference along file x / y / z (1 / 2 / 3), d_a = u^n[c + e_a] - u^n[c - e_a] in the field's own
-// precision -- run through a cascade of second-order sections each, and PRODUCTS of two filtered components are summed into time bins,
+// pf_vband.h -- device side of the band accumulators, vector (include/pffdtd_hip.h: pf_vbandacc) and scalar (pf_bandacc): per cell of a region, up to
+// four COMPONENTS of the field -- the cell itself (0) or the central difference along file x / y / z (1 / 2 / 3), d_a = u^n[c + e_a] - u^n[c - e_a] in
+// the field's own precision -- run through a cascade of second-order sections each, and PRODUCTS of two filtered components are summed into time bins,
 //    x_k = double(component k);  x_k -> pre sections of k;  per band b: y_k = x_k -> the band's sections (state per component);
 //    S[p][b][bin] = S[p][b][bin] + y_i * y_j          (mode 1: + fabs(y_i * y_j))         for every product p = (i, j, mode)
-// which is what a lateral energy fraction or an intensity map needs of every cell (pffdtd_amd/directional.py).  The section is pf_band.h's
-// band_section, unchanged: the same three lines, every operation rounded to double once, NO fma (the build has -ffp-contract=off, the pragmas
-// below say so again).
-//   S     double [nprod * nband * nbin][cstride]            cstride = the cell count rounded up to a multiple of 2
-//   st    double [ncomp][(npre + nband*nsec) * 2][cstride]   component k's s1, s2 of section q in rows 2q, 2q + 1 of its block
-//   coef  double [(ncomp*npre + nband*nsec) * 5]            the components' pre sections, then the bands' (shared by the components)
+// which is what a lateral energy fraction or an intensity map needs of every cell (pffdtd_amd/directional.py).  The SCALAR band accumulator is the
+// one component 0 with the one product (0, 0, 0): E[b][bin] = E[b][bin] + y * y, what an energy decay per octave band needs (pffdtd_amd/decay.py).
+// The section is pf_band.h's band_section: three lines, every operation rounded to double once, NO fma (the build has -ffp-contract=off, the
+// pragmas below say so again).
+//   S     double [nprod * nband * nbin][cstride]            cstride = the cell count rounded up to a multiple of 2: every row starts 16-byte aligned
+//   st    double [ncomp][(npre + nband*nsec) * 2][cstride]   component k's s1, s2 of section q in rows 2q, 2q + 1 of its block; pre sections first,
+//                                                           then band 0's, band 1's, ...
+//   coef  double [(ncomp*npre + nband*nsec) * 5]            the components' pre sections, then the bands' (shared by the components); uploaded once
 //   ring  Real   [ncomp][depth][cells]                      the components at the samples not folded in yet: component 0 by k_region_cut
 //                                                           (pf_region.h), a difference by k_region_diff below -- a fold reads Real whatever
 //                                                           the component
 //   xpre  double [ncomp][depth][cstride]                    npre > 0 only: the pending samples after the components' pre sections
-//   bins  int32  [depth];  prod  int32 [nprod][3]
+//   bins  int32  [depth]                                    the pending samples' bins (-1: filter, sum nothing), uploaded with every fold
+//   prod  int32  [nprod][3]
+// (the scalar kind: ncomp = nprod = 1, so S is its E [nband * nbin][cstride] and st its [(npre + nband*nsec) * 2][cstride].)
 // k_region_diff<Real, EXCH> is k_region_cut with the two neighbour loads and ONE subtraction, rounded once in Real.  The subtraction is done in
 // registers before anything goes to LDS, so the tiled form keeps ONE 32 x 33 tile of Real and the bank picture of pf_region.h as it is (two
 // operand tiles would double the LDS for nothing: the operands are never needed apart).  On exchanged storage a difference along file x has its
@@ -23,18 +27,23 @@
 // each of the at most twelve distinct neighbours loaded once, the sums formed in registers, one 32 x 33 tile of Real PER REQUESTED component in the
 // tiled form (dynamic LDS; the bank picture of pf_region.h per tile), each component stored into its own ring slot.  Stored coordinates, no parity
 // logic: a folded grid's fold row is a row like any other, a checkerboard's hole is computed from holes.
-// A fold of NT pending samples is k_vband_pre<Real, NT> (npre > 0; grid.y = the component) and ONE k_vband_fold<In, NC, NT> on a grid of
-// (cdiv(cdiv(cells, 2), 256), nband): a thread owns two adjacent cells (16-byte loads and stores, lanes along cells), runs all NC components'
-// sections of its band over the NT samples in registers -- y[NC][NT] of two cells, 2 * NC * NT doubles, never go to memory -- and then walks the
-// products and, per product, the bins exactly as k_band_fold walks its one square: consecutive samples of one bin are summed in a register from
-// the loaded S in call order, a bin change stores and loads.  The components of a product are picked with selects on (i == k), uniform over the
-// wave: no indexed register file, hence no scratch.  prod, coef and bins do not depend on the lane: scalar loads.  No atomics, no LDS in the
-// folds, no scratch (tools/kernel_resources.py k_vband).  64-bit indices, every access guarded by the cell count.
+// A fold of NT pending samples is k_vband_pre<Real, NT> (npre > 0; grid.y = the component: one thread per two cells runs the pre sections once and
+// writes xpre -- the other choice, every band recomputing them, has band b read the shared state while band 0 stores it) and ONE
+// k_vband_fold<In, NC, NT> on a grid of (cdiv(cdiv(cells, 2), 256), nband): bands in parallel, so a 64^2 plane still fills the chip.  A thread owns
+// two adjacent cells (16-byte loads and stores, lanes along cells: whole lines), reads and widens its inputs once and runs all NC components'
+// sections of its band over the NT samples in registers -- two state words per cell loaded, NT samples through the section, stored once: state
+// traffic is 1 / NT of the depth-1 form; y[NC][NT] of two cells, 2 * NC * NT doubles, never go to memory -- and then walks the products and, per
+// product, the bins: consecutive samples of one bin are summed in a register from the loaded S in call order, a bin change stores and loads.  The
+// padding cell of an odd count filters zeros.  The components of a product are picked with selects on (i == k), uniform over the wave: no indexed
+// register file, hence no scratch.  prod, coef and bins do not depend on the lane: scalar loads.  No atomics, no LDS in the folds, no scratch
+// (tools/kernel_resources.py k_vband).  64-bit indices, every access guarded by the cell count (c even and c < cells, so c + 1 < cstride).
 // Instantiated for NC = 1 .. 4 and NT in {1, 2, 4, 8}: a partly filled ring is folded greedily (7 = 4 + 2 + 1), the samples still in call order,
-// so the pieces never change a bit.
+// so the pieces never change a bit.  The SCALAR kind's objects are this kind's with one component and one product, but its folds are launched on
+// pf_band.h's k_band_pre / k_band_fold, which compute the same bits: on these kernels it measured 0.3 .. 1 % slower per sample
+// (profiles/field_decay_refactor.txt), and a refactor is to cost nothing.
 //
 // PF_VBAND_DEFAULT_DEPTH: the fastest of the depths 1, 2, 4, 8 on the plane case of tools/field_directional_cost.py (profiles/field_directional.txt),
-// and of its --fcc case with the lattice differences (profiles/field_directional_fcc.txt).
+// and of its --fcc case with the lattice differences (profiles/field_directional_fcc.txt).  The scalar kind's ring: pf_band.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

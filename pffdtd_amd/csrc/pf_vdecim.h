@@ -9,7 +9,7 @@
 //    x_k = double(component k);  x_k -> pre sections of k;  per slot p:  acc[k][p] = acc[k][p] + h[tap] * x_k      product rounded to double, then the sum: NO fma
 //    tap == 0:  frame m of component k = acc[k][p];  acc[k][p] = +0.0
 // so a numpy loop over time gives the same bits at every ring depth.  m, the tap and the frame's device row depend on neither the cell nor the
-// component: the host works them out once per pending sample and slot and uploads them with every fold (plan, orow; as pf_band.h's bins):
+// component: the host works them out once per pending sample and slot and uploads them with every fold (plan, orow; as pf_vband.h's bins):
 //   acc    double [ncomp][P][cstride]           cstride = the cell count rounded up to a multiple of 2: every row starts 16-byte aligned
 //   frames double [cap][ncomp][cstride]         frame m of component k in row (m mod cap) * ncomp + k: n frames are n * ncomp consecutive rows
 //   st     double [ncomp][npre * 2][cstride]    taps double [ntap] (uploaded once, at creation)     coef double [ncomp][npre][5]

@@ -272,13 +272,18 @@ def _region(what, lo, hi, stride):
         raise PfError(f"{what}: lo, hi and stride are three integers each ({e})")
 
 
-def _get_region(call, handle, dtype, which, lo, hi, stride):
-    """pf_engine_get_region / pf_multi_get_region -> ndarray of shape counts, the cells lo + k * stride < hi in FILE coordinates x, y, z"""
-    r = _region("get_region", lo, hi, stride)
+def _cells(r):
+    """the counts (c0, c1, c2) of a region: the cells lo + k * stride < hi"""
     counts = (ctypes.c_int64 * 3)()
     if lib().pf_region_count(ctypes.byref(r), counts) < 0:
         _check(1)  # (PF_ERR_ARG: pf_last_error names the field)
-    a = np.empty(tuple(int(c) for c in counts), dtype=dtype)
+    return tuple(int(c) for c in counts)
+
+
+def _get_region(call, handle, dtype, which, lo, hi, stride):
+    """pf_engine_get_region / pf_multi_get_region -> ndarray of shape counts, the cells lo + k * stride < hi in FILE coordinates x, y, z"""
+    r = _region("get_region", lo, hi, stride)
+    a = np.empty(_cells(r), dtype=dtype)
     _check(call(handle, int(which), ctypes.byref(r), a.ctypes.data_as(ctypes.c_void_p)))
     return a
 
@@ -329,12 +334,10 @@ class Accumulator(_Observer):
 
     def __init__(self, owner, prefix, lo, hi, stride, nchan, depth):
         r = _region("accumulator", lo, hi, stride)
-        L = self._bind(owner, prefix, ("create", "add", "get", "set", "destroy"))
+        self._bind(owner, prefix, ("create", "add", "get", "set", "destroy"))
         _check(self._f["create"](owner._h, ctypes.byref(r), int(nchan), int(depth), ctypes.byref(self._a)))
-        counts = (ctypes.c_int64 * 3)()
-        L.pf_region_count(ctypes.byref(r), counts)
         self.nchan = int(nchan)
-        self.shape = (self.nchan,) + tuple(int(c) for c in counts)  # of get()
+        self.shape = (self.nchan,) + _cells(r)  # of get()
 
     def add(self, w):
         """the sample of the step the owner stands at: acc[m] += w[m] * double(u^n), w: nchan doubles"""
@@ -370,61 +373,86 @@ def _sos5(name, sos, lead):
     return np.ascontiguousarray(a[..., [0, 1, 2, 4, 5]])
 
 
-class BandAccumulator(_Observer):
+def _pre3(what, pre_sos, ncomp):
+    """a vector kind's pre_sos [ncomp, npre, 6] -> float64 [ncomp, npre, 5]"""
+    p = np.asarray([] if pre_sos is None else pre_sos, dtype=np.float64)
+    if p.size == 0:
+        return np.zeros((ncomp, 0, 5))
+    if p.ndim != 3 or p.shape[0] != ncomp:
+        raise PfError(f"{what}: pre_sos has shape {p.shape}: [ncomp = {ncomp}, npre, 6] is expected (pad a shorter cascade with 1 0 0 1 0 0)")
+    return _sos5("pre_sos", p, 2)
+
+
+def _ptr(a):
+    """an array for the C ABI; None, or an array without elements: null"""
+    return None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _float64_or_none(what, noun, arrays):
+    """a set's optional arrays (name, array or None, the shape it stands for) -> float64, contiguous, of that size -- or None: zeros"""
+    out = []
+    for name, a, shape in arrays:
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != int(np.prod(shape)):
+                raise PfError(f"{what}: {name} has {a.size} elements, the {noun} holds {int(np.prod(shape))}")
+        out.append(a)
+    return out
+
+
+class _Bands(_Observer):
+    """What the two band accumulators share: all but the components and products of the vector kind, which `_make` takes as the arguments that stand
+    around the filters' in its create call and as the leading axes of its arrays."""
+
+    def _make(self, owner, prefix, r, pre, band_sos, nbin, depth, comp=(), prod=(), lead=((), ())):
+        b = np.asarray([] if band_sos is None else band_sos, dtype=np.float64)
+        if b.ndim == 3 and b.shape[1] == 0:  # nband bands without sections: plain squares (products) of what the pre sections give
+            band = np.zeros((b.shape[0], 0, 5))
+        else:
+            band = _sos5("band_sos", band_sos, 2)
+        self._bind(owner, prefix, ("create", "add", "get", "set", "destroy"))
+        self.npre, self.nband, self.nsec, self.nbin = int(pre.shape[-2]), int(band.shape[0]), int(band.shape[1]), int(nbin)
+        _check(self._f["create"](owner._h, ctypes.byref(r), *comp, self.npre, _ptr(pre), self.nband, self.nsec, _ptr(band), *prod, self.nbin, int(depth), ctypes.byref(self._a)))
+        cells = _cells(r)
+        self.shape = lead[0] + (self.nband, self.nbin) + cells  # of get()'s sums
+        self.state_shape = lead[1] + (self.npre + self.nband * self.nsec, 2) + cells  # ... and state
+
+    def add(self, bin):
+        """the sample of the step the owner stands at, its squares (products) summed into time bin `bin` (-1: the filters run, nothing is summed)"""
+        _check(self._f["add"](self._owner._h, self._a, int(bin)))
+
+    def get(self, state=True):
+        """-> (sums float64 of `shape`, state float64 of `state_shape` or None): pending samples folded in, nothing reset"""
+        e = np.empty(self.shape, dtype=np.float64)
+        s = np.empty(self.state_shape, dtype=np.float64) if state else None
+        _check(self._f["get"](self._owner._h, self._a, e.ctypes.data_as(ctypes.c_void_p), _ptr(s)))
+        return e, s
+
+    def set(self, sums, state, count):
+        """replace sums, filter state and count (None: zeros); pending samples are dropped -- how a resumed run continues"""
+        arrs = _float64_or_none(f"{type(self).__name__}.set", "accumulator", (("sums", sums, self.shape), ("state", state, self.state_shape)))
+        _check(self._f["set"](self._owner._h, self._a, *map(_ptr, arrs), int(count)))
+
+
+class BandAccumulator(_Bands):
     """Per cell of a region, on the device (pf_engine_bandacc_* / pf_multi_bandacc_*): u^n through the shared sections pre_sos [npre, 6], then per
     band through band_sos [nband, nsec, 6] (scipy's sos rows, a0 = 1), squared and summed into time bin `bin` at every add(bin).
+    sums are [nband, nbin, c0, c1, c2], state [npre + nband * nsec, 2, c0, c1, c2].
     Made by HipEngine.band_accumulator / HipMulti.band_accumulator; it lives no longer than the object that made it."""
     _kind, _handle = "bandacc", "bandacc"
 
     def __init__(self, owner, prefix, lo, hi, stride, pre_sos, band_sos, nbin, depth):
         r = _region("band_accumulator", lo, hi, stride)
-        pre = _sos5("pre_sos", pre_sos, 1)
-        b = np.asarray(band_sos, dtype=np.float64)
-        if b.ndim == 3 and b.shape[1] == 0:  # nband bands without sections: plain squares of what the shared sections give
-            band, nband = np.zeros((b.shape[0], 0, 5)), b.shape[0]
-        else:
-            band = _sos5("band_sos", band_sos, 2)
-            nband = band.shape[0] if band.ndim == 3 else 0
-        L = self._bind(owner, prefix, ("create", "add", "get", "set", "destroy"))
-        self.npre, self.nband, self.nsec, self.nbin = int(pre.shape[0]), int(nband), int(band.shape[1]) if band.ndim == 3 else 0, int(nbin)
-        vp = ctypes.c_void_p
-        _check(self._f["create"](owner._h, ctypes.byref(r), self.npre, pre.ctypes.data_as(vp) if pre.size else None, self.nband, self.nsec,
-                                 band.ctypes.data_as(vp) if band.size else None, self.nbin, int(depth), ctypes.byref(self._a)))
-        counts = (ctypes.c_int64 * 3)()
-        L.pf_region_count(ctypes.byref(r), counts)
-        cells = tuple(int(c) for c in counts)
-        self.shape = (self.nband, self.nbin) + cells  # of get()'s sums
-        self.state_shape = (self.npre + self.nband * self.nsec, 2) + cells  # ... and state
-
-    def add(self, bin):
-        """the sample of the step the owner stands at, summed into time bin `bin` (-1: the filters run, nothing is summed)"""
-        _check(self._f["add"](self._owner._h, self._a, int(bin)))
-
-    def get(self, state=True):
-        """-> (sums float64 [nband, nbin, c0, c1, c2], state float64 [npre + nband * nsec, 2, c0, c1, c2] or None): pending samples folded in, nothing reset"""
-        e = np.empty(self.shape, dtype=np.float64)
-        s = np.empty(self.state_shape, dtype=np.float64) if state else None
-        _check(self._f["get"](self._owner._h, self._a, e.ctypes.data_as(ctypes.c_void_p), s.ctypes.data_as(ctypes.c_void_p) if state and s.size else None))
-        return e, s
-
-    def set(self, sums, state, count):
-        """replace sums, filter state and count (None: zeros); pending samples are dropped -- how a resumed run continues"""
-        arrs = []
-        for name, a, shape in (("sums", sums, self.shape), ("state", state, self.state_shape)):
-            if a is not None:
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.size != int(np.prod(shape)):
-                    raise PfError(f"BandAccumulator.set: {name} has {a.size} elements, the accumulator holds {int(np.prod(shape))}")
-            arrs.append(a)
-        _check(self._f["set"](self._owner._h, self._a, *[None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p) for a in arrs], int(count)))
+        self._make(owner, prefix, r, _sos5("pre_sos", pre_sos, 1), band_sos, nbin, depth)
 
 
-class VectorBandAccumulator(_Observer):
+class VectorBandAccumulator(_Bands):
     """Per cell of a region, on the device (pf_engine_vband_* / pf_multi_vband_*): the components `comp` (0: the cell of u^n, 1 / 2 / 3: its central
     difference along file x / y / z on a Cartesian grid, 4 / 5 / 6: the lattice difference along file x / y / z of an FCC grid -- the four pair
     differences over the eight FCC neighbours at +-1 along the axis, in stored coordinates, ~ 8 h du/da) through their own sections pre_sos [ncomp, npre, 6], then per band through band_sos [nband, nsec, 6] (scipy's
     sos rows, a0 = 1; state per component); the products prod [nprod, 3] -- rows (i, j, mode), mode 1: the absolute value -- of two filtered
     components are summed into time bin `bin` at every add(bin).
+    sums are [nprod, nband, nbin, c0, c1, c2], state [ncomp, npre + nband * nsec, 2, c0, c1, c2].
     Made by HipEngine.vector_band_accumulator / HipMulti.vector_band_accumulator; it lives no longer than the object that made it."""
     _kind, _handle = "vband", "vbandacc"
 
@@ -435,53 +463,9 @@ class VectorBandAccumulator(_Observer):
         if prod.size and (prod.ndim != 2 or prod.shape[1] != 3):
             raise PfError(f"vector_band_accumulator: prod has shape {prod.shape}: [nprod, 3] rows (i, j, mode) are expected")
         prod = np.ascontiguousarray(prod.reshape(-1, 3), dtype=np.int32)
-        p = np.asarray([] if pre_sos is None else pre_sos, dtype=np.float64)
-        if p.size == 0:
-            pre = np.zeros((comp.size, 0, 5))
-        else:
-            if p.ndim != 3 or p.shape[0] != comp.size:
-                raise PfError(f"vector_band_accumulator: pre_sos has shape {p.shape}: [ncomp = {comp.size}, npre, 6] is expected (pad a shorter cascade with 1 0 0 1 0 0)")
-            pre = _sos5("pre_sos", p, 2)
-        b = np.asarray([] if band_sos is None else band_sos, dtype=np.float64)
-        if b.ndim == 3 and b.shape[1] == 0:  # nband bands without sections
-            band, nband = np.zeros((b.shape[0], 0, 5)), b.shape[0]
-        else:
-            band = _sos5("band_sos", band_sos, 2)
-            nband = band.shape[0] if band.ndim == 3 else 0
-        L = self._bind(owner, prefix, ("create", "add", "get", "set", "destroy"))
-        self.ncomp, self.nprod, self.npre, self.nband, self.nbin = int(comp.size), int(prod.shape[0]), int(pre.shape[1]), int(nband), int(nbin)
-        self.nsec = int(band.shape[1]) if band.ndim == 3 else 0
-        vp = ctypes.c_void_p
-        _check(self._f["create"](owner._h, ctypes.byref(r), self.ncomp, comp.ctypes.data_as(vp) if comp.size else None, self.npre, pre.ctypes.data_as(vp) if pre.size else None,
-                                 self.nband, self.nsec, band.ctypes.data_as(vp) if band.size else None, self.nprod, prod.ctypes.data_as(vp) if prod.size else None,
-                                 self.nbin, int(depth), ctypes.byref(self._a)))
-        counts = (ctypes.c_int64 * 3)()
-        L.pf_region_count(ctypes.byref(r), counts)
-        cells = tuple(int(c) for c in counts)
-        self.shape = (self.nprod, self.nband, self.nbin) + cells  # of get()'s sums
-        self.state_shape = (self.ncomp, self.npre + self.nband * self.nsec, 2) + cells  # ... and state
-
-    def add(self, bin):
-        """the sample of the step the owner stands at, its products summed into time bin `bin` (-1: the filters run, nothing is summed)"""
-        _check(self._f["add"](self._owner._h, self._a, int(bin)))
-
-    def get(self, state=True):
-        """-> (sums float64 [nprod, nband, nbin, c0, c1, c2], state float64 [ncomp, npre + nband * nsec, 2, c0, c1, c2] or None): pending samples folded in"""
-        e = np.empty(self.shape, dtype=np.float64)
-        s = np.empty(self.state_shape, dtype=np.float64) if state else None
-        _check(self._f["get"](self._owner._h, self._a, e.ctypes.data_as(ctypes.c_void_p), s.ctypes.data_as(ctypes.c_void_p) if state and s.size else None))
-        return e, s
-
-    def set(self, sums, state, count):
-        """replace sums, filter state and count (None: zeros); pending samples are dropped -- how a resumed run continues"""
-        arrs = []
-        for name, a, shape in (("sums", sums, self.shape), ("state", state, self.state_shape)):
-            if a is not None:
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.size != int(np.prod(shape)):
-                    raise PfError(f"VectorBandAccumulator.set: {name} has {a.size} elements, the accumulator holds {int(np.prod(shape))}")
-            arrs.append(a)
-        _check(self._f["set"](self._owner._h, self._a, *[None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p) for a in arrs], int(count)))
+        self.ncomp, self.nprod = int(comp.size), int(prod.shape[0])
+        self._make(owner, prefix, r, _pre3("vector_band_accumulator", pre_sos, self.ncomp), band_sos, nbin, depth, comp=(self.ncomp, _ptr(comp)),
+                   prod=(self.nprod, _ptr(prod)), lead=((self.nprod,), (self.ncomp,)))
 
 
 class DecimatingRecorder(_Observer):
@@ -492,51 +476,47 @@ class DecimatingRecorder(_Observer):
 
     def __init__(self, owner, prefix, lo, hi, stride, pre_sos, taps, factor, cap, depth):
         r = _region("decimating_recorder", lo, hi, stride)
-        pre = _sos5("pre_sos", pre_sos, 1)
+        self._make("decimating_recorder", owner, prefix, r, _sos5("pre_sos", pre_sos, 1), taps, factor, cap, depth)
+
+    def _make(self, what, owner, prefix, r, pre, taps, factor, cap, depth, comp=(), lead=()):
+        """what the two recorders share; comp, lead: the vector kind's arguments of create and the leading axis of its arrays"""
         h = np.ascontiguousarray([] if taps is None else taps, dtype=np.float64)
         if h.ndim != 1:
-            raise PfError(f"decimating_recorder: taps has shape {h.shape}: a vector of ntap values is expected")
-        L = self._bind(owner, prefix, ("create", "add", "read", "get_state", "set_state", "destroy"))
-        self.npre, self.ntap, self.factor = int(pre.shape[0]), int(h.size), int(factor)
+            raise PfError(f"{what}: taps has shape {h.shape}: a vector of ntap values is expected")
+        self._bind(owner, prefix, ("create", "add", "read", "get_state", "set_state", "destroy"))
+        self.npre, self.ntap, self.factor = int(pre.shape[-2]), int(h.size), int(factor)
         self.cap = int(cap) if cap else 64  # frames kept on the device between two reads
-        vp = ctypes.c_void_p
-        _check(self._f["create"](owner._h, ctypes.byref(r), self.npre, pre.ctypes.data_as(vp) if pre.size else None, self.ntap, h.ctypes.data_as(vp) if h.size else None,
-                                 self.factor, self.cap, int(depth), ctypes.byref(self._a)))
-        counts = (ctypes.c_int64 * 3)()
-        L.pf_region_count(ctypes.byref(r), counts)
-        self.cells = tuple(int(c) for c in counts)
+        _check(self._f["create"](owner._h, ctypes.byref(r), *comp, self.npre, _ptr(pre), self.ntap, _ptr(h), self.factor, self.cap, int(depth), ctypes.byref(self._a)))
+        self.cells = _cells(r)
         self.slots = -(-self.ntap // self.factor)  # P
-        self.acc_shape = (self.slots,) + self.cells  # of get_state()'s acc
-        self.state_shape = (self.npre, 2) + self.cells  # ... and state
+        self._frame = lead + self.cells  # a frame of read()
+        self.acc_shape = lead + (self.slots,) + self.cells  # of get_state()'s acc
+        self.state_shape = lead + (self.npre, 2) + self.cells  # ... and state
 
     def add(self):
         """the sample of the step the owner stands at; PfError (code 4) and nothing changed where it would complete a frame while `cap` frames wait"""
         _check(self._f["add"](self._owner._h, self._a))
 
     def read(self, max_frames=None):
-        """-> (first, frames float64 [nread, c0, c1, c2]): the oldest complete frames in order (all of them, or max_frames), marked read"""
+        """-> (first, frames float64 [nread, c0, c1, c2] -- a vector recorder's: [nread, ncomp, c0, c1, c2]): the oldest complete frames in order (all of
+        them, or max_frames), marked read"""
         n = self.pending if max_frames is None else int(max_frames)
-        out = np.empty((max(n, 0),) + self.cells, dtype=np.float64)
+        out = np.empty((max(n, 0),) + self._frame, dtype=np.float64)
         first, nread = ctypes.c_int64(), ctypes.c_int64()
-        _check(self._f["read"](self._owner._h, self._a, out.ctypes.data_as(ctypes.c_void_p) if out.size else None, n, ctypes.byref(first), ctypes.byref(nread)))
+        _check(self._f["read"](self._owner._h, self._a, _ptr(out), n, ctypes.byref(first), ctypes.byref(nread)))
         return int(first.value), out[:nread.value]
 
     def get_state(self):
-        """-> (acc float64 [P, c0, c1, c2] in slot order, state float64 [npre, 2, c0, c1, c2]): pending samples folded in, nothing reset"""
+        """-> (acc float64 [P, c0, c1, c2] in slot order, state float64 [npre, 2, c0, c1, c2]; a vector recorder's: with a leading ncomp): pending samples
+        folded in, nothing reset"""
         a, s = np.empty(self.acc_shape, dtype=np.float64), np.empty(self.state_shape, dtype=np.float64)
-        _check(self._f["get_state"](self._owner._h, self._a, a.ctypes.data_as(ctypes.c_void_p), s.ctypes.data_as(ctypes.c_void_p) if s.size else None))
+        _check(self._f["get_state"](self._owner._h, self._a, a.ctypes.data_as(ctypes.c_void_p), _ptr(s)))
         return a, s
 
     def set_state(self, acc, state, count):
         """replace the outputs in flight, the filter state and the count (None: zeros); pending samples and unread frames are dropped"""
-        arrs = []
-        for name, a, shape in (("acc", acc, self.acc_shape), ("state", state, self.state_shape)):
-            if a is not None:
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.size != int(np.prod(shape)):
-                    raise PfError(f"DecimatingRecorder.set_state: {name} has {a.size} elements, the recorder holds {int(np.prod(shape))}")
-            arrs.append(a)
-        _check(self._f["set_state"](self._owner._h, self._a, *[None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p) for a in arrs], int(count)))
+        arrs = _float64_or_none("DecimatingRecorder.set_state", "recorder", (("acc", acc, self.acc_shape), ("state", state, self.state_shape)))
+        _check(self._f["set_state"](self._owner._h, self._a, *map(_ptr, arrs), int(count)))
 
     @property
     def pending(self):
@@ -548,44 +528,16 @@ class VectorDecimatingRecorder(DecimatingRecorder):
     """Per cell of a region, on the device (pf_engine_vdecim_* / pf_multi_vdecim_*): the components `comp` of a VectorBandAccumulator (0: the cell of
     u^n, 1 / 2 / 3: its central difference along file x / y / z on a Cartesian grid, 4 / 5 / 6: the lattice difference of an FCC grid) through their
     own sections pre_sos [ncomp, npre, 6], then each through the FIR `taps`, every `factor`-th output kept as a frame [ncomp, c0, c1, c2]; up to
-    `cap` frames wait on the device for read().  add, set_state, count, pending and close are a DecimatingRecorder's.
+    `cap` frames wait on the device for read().  All but the creation is a DecimatingRecorder's.
     Made by HipEngine.vector_decimating_recorder / HipMulti.vector_decimating_recorder; it lives no longer than the object that made it."""
     _kind, _handle = "vdecim", "vdecim"
 
     def __init__(self, owner, prefix, lo, hi, stride, comp, pre_sos, taps, factor, cap, depth):
-        r = _region("vector_decimating_recorder", lo, hi, stride)
+        what = "vector_decimating_recorder"
+        r = _region(what, lo, hi, stride)
         comp = np.ascontiguousarray(np.asarray(comp).reshape(-1), dtype=np.int32)
-        p = np.asarray([] if pre_sos is None else pre_sos, dtype=np.float64)
-        if p.size == 0:
-            pre = np.zeros((comp.size, 0, 5))
-        else:
-            if p.ndim != 3 or p.shape[0] != comp.size:
-                raise PfError(f"vector_decimating_recorder: pre_sos has shape {p.shape}: [ncomp = {comp.size}, npre, 6] is expected (pad a shorter cascade with 1 0 0 1 0 0)")
-            pre = _sos5("pre_sos", p, 2)
-        h = np.ascontiguousarray([] if taps is None else taps, dtype=np.float64)
-        if h.ndim != 1:
-            raise PfError(f"vector_decimating_recorder: taps has shape {h.shape}: a vector of ntap values is expected")
-        L = self._bind(owner, prefix, ("create", "add", "read", "get_state", "set_state", "destroy"))
         self.ncomp, self.comp = int(comp.size), tuple(int(c) for c in comp)
-        self.npre, self.ntap, self.factor = int(pre.shape[1]), int(h.size), int(factor)
-        self.cap = int(cap) if cap else 64  # frames kept on the device between two reads
-        vp = ctypes.c_void_p
-        _check(self._f["create"](owner._h, ctypes.byref(r), self.ncomp, comp.ctypes.data_as(vp) if comp.size else None, self.npre, pre.ctypes.data_as(vp) if pre.size else None,
-                                 self.ntap, h.ctypes.data_as(vp) if h.size else None, self.factor, self.cap, int(depth), ctypes.byref(self._a)))
-        counts = (ctypes.c_int64 * 3)()
-        L.pf_region_count(ctypes.byref(r), counts)
-        self.cells = tuple(int(c) for c in counts)
-        self.slots = -(-self.ntap // self.factor)  # P
-        self.acc_shape = (self.ncomp, self.slots) + self.cells  # of get_state()'s acc
-        self.state_shape = (self.ncomp, self.npre, 2) + self.cells  # ... and state
-
-    def read(self, max_frames=None):
-        """-> (first, frames float64 [nread, ncomp, c0, c1, c2]): the oldest complete frames in order (all of them, or max_frames), marked read"""
-        n = self.pending if max_frames is None else int(max_frames)
-        out = np.empty((max(n, 0), self.ncomp) + self.cells, dtype=np.float64)
-        first, nread = ctypes.c_int64(), ctypes.c_int64()
-        _check(self._f["read"](self._owner._h, self._a, out.ctypes.data_as(ctypes.c_void_p) if out.size else None, n, ctypes.byref(first), ctypes.byref(nread)))
-        return int(first.value), out[:nread.value]
+        self._make(what, owner, prefix, r, _pre3(what, pre_sos, self.ncomp), taps, factor, cap, depth, comp=(self.ncomp, _ptr(comp)), lead=(self.ncomp,))
 
 
 def device_count():

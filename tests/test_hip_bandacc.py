@@ -407,3 +407,51 @@ def test_refusals_name_the_field_and_leave_the_engine_running():
     assert np.array_equal(sd.u_out, ref.u_out) and np.abs(ref.u_out).max() > 0
     eng.close()
     other.close()
+
+
+# ---- 9. the scalar kind is the vector kind with one component ---------------------------------------------------------------------------------------------
+PRE2 = np.concatenate([PRE, butter(2, 0.03, "high", output="sos")])  # npre = 2
+assert PRE2.shape == (2, 6)
+
+
+@pytest.mark.parametrize("owner", ["engine", "chain2"])
+@pytest.mark.parametrize("name,prec", [("cart_mb11", "single"), ("fcc2_outside", "double")])
+def test_the_scalar_kind_is_the_vector_kind_with_one_component(name, prec, owner):
+    """A band_accumulator and a vector_band_accumulator(comp=(0,), prod=((0, 0, 0),)) of the same owner, sections and depth 8 return the same bits
+    after 20 samples (the bin changes every 3 samples, one sample goes to bin -1), for npre 0 and 2, over 5 x 3 x 7 = 105 cells (an odd count: the
+    padding cell of the last double2) and over more than one block of 512 cells: 24 x 18 x 20 = 8640 cells on cart_mb11; fcc2_outside is folded to
+    30 x 17 x 26, where 18 cells along y do not exist, so its large region is 28 x 15 x 24 = 10080 cells."""
+    sd = cases.make_sd(name, prec)
+    N = (sd.Nx, sd.Ny, sd.Nz)
+    if owner == "engine":
+        obj = engine.HipEngine(sd)
+    else:
+        obj = engine.HipMulti(sd, [0, 0], multi_flags=engine.PF_MULTI_NO_PAIRS | engine.PF_MULTI_NO_TRIPLES)
+        assert obj.info()["nslabs"] == 2
+    x0 = N[0] // 2 - 2  # (around the middle plane: both slabs of the chain hold cells of it)
+    small = ([x0, 2, 3], [x0 + 5, 5, 10])
+    large, large_cells = (([1, 1, 1], [25, 19, 21]), 8640) if name == "cart_mb11" else (([1, 1, 1], [29, 16, 25]), 10080)
+    pairs = []
+    for npre in (0, 2):
+        for r, cells in ((small, 105), (large, large_cells)):
+            kw = dict(band_sos=BANDS, nbin=7, depth=8)
+            s = obj.band_accumulator(*r, pre_sos=PRE2[:npre] if npre else None, **kw)
+            v = obj.vector_band_accumulator(*r, comp=(0,), pre_sos=PRE2[None, :npre] if npre else None, prod=((0, 0, 0),), **kw)
+            assert (s.npre, v.npre) == (npre, npre) and (v.ncomp, v.nprod) == (1, 1)
+            assert int(np.prod(s.shape[2:])) == cells
+            assert v.shape == (1,) + s.shape and v.state_shape == (1,) + s.state_shape
+            pairs.append((npre, r, s, v))
+    obj.run(0, 12)  # (the wave has reached both regions)
+    for k in range(20):
+        bin = -1 if k == 10 else k // 3
+        for _, _, s, v in pairs:
+            s.add(bin)
+            v.add(bin)
+        obj.run(12 + k, 1)
+    for npre, r, s, v in pairs:
+        (es, ss), (ev, sv) = s.get(), v.get()
+        assert s.count == 20 and v.count == 20
+        assert np.array_equal(ev.reshape(es.shape), es), (npre, r, "sums", int(np.count_nonzero(ev.reshape(es.shape) != es)))
+        assert np.array_equal(sv.reshape(ss.shape), ss), (npre, r, "state", int(np.count_nonzero(sv.reshape(ss.shape) != ss)))
+        assert es[:, 6].max() > 0 and np.abs(ss).max() > 0 and np.isfinite(es).all()
+    obj.close()
