@@ -234,6 +234,8 @@ template <typename Real> struct Engine : EngineBase {
    Cut bn_cut[4], bnl_cut[4], in_cut[4], bna_cut; // [w]; the ABC list: single steps only
    hipStream_t s_main = nullptr, s_edge = nullptr, s_wall = nullptr, s_wall2 = nullptr; // s_wall, s_wall2: a slab's wall regions, alike / generic blocks (created on first use)
    hipEvent_t ev_pre = nullptr, ev_edge = nullptr, ev_main = nullptr, ev_wall0 = nullptr, ev_wall = nullptr, ev_wall2 = nullptr;
+   hipEvent_t ev_obs = nullptr; // the main stream up to a region observer's sample: the edge stream of the next split-phase step waits for it
+   bool obs_pending = false;    // a sample was enqueued on s_main and no synchronisation has followed (observer_sample, step_begin, sync)
    hipEvent_t ev_src0 = nullptr, ev_src1 = nullptr; // fork / join of k_tb3_src beside the box kernel (single domains: fork_tb3_src)
    bool wall_pending = false;
    bool in_step = false;
@@ -414,9 +416,10 @@ template <typename Real> struct Engine : EngineBase {
       if (ev_pre) hipEventDestroy(ev_pre);
       if (ev_edge) hipEventDestroy(ev_edge);
       if (ev_main) hipEventDestroy(ev_main);
+      if (ev_obs) hipEventDestroy(ev_obs);
       if (ev_src0) hipEventDestroy(ev_src0);
       if (ev_src1) hipEventDestroy(ev_src1);
-      ev_src0 = ev_src1 = nullptr;
+      ev_src0 = ev_src1 = ev_obs = nullptr;
       if (gexec) hipGraphExecDestroy(gexec);
       if (s_wall) hipStreamDestroy(s_wall);
       if (s_wall2) hipStreamDestroy(s_wall2);
@@ -582,6 +585,7 @@ template <typename Real> struct Engine : EngineBase {
       HIPCHK(hipEventCreateWithFlags(&ev_pre, hipEventDisableTiming));
       HIPCHK(hipEventCreateWithFlags(&ev_edge, hipEventDisableTiming));
       HIPCHK(hipEventCreateWithFlags(&ev_main, hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&ev_obs, hipEventDisableTiming));
       HIPCHK(hipEventCreateWithFlags(&ev_src0, hipEventDisableTiming));
       HIPCHK(hipEventCreateWithFlags(&ev_src1, hipEventDisableTiming));
       use_dpp = check_dpp(s_main) == 1;
@@ -965,6 +969,7 @@ template <typename Real> struct Engine : EngineBase {
       HIPCHK(hipSetDevice(op.device));
       HIPCHK(hipStreamSynchronize(s_edge));
       HIPCHK(hipStreamSynchronize(s_main));
+      obs_pending = false;
       return PF_OK;
    }
 

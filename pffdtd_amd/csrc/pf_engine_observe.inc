@@ -11,7 +11,13 @@
 // by ONE k_region_lat launch per sample; they read along all three axes, so the region keeps one cell clear of all six faces.  The virtual ghost
 // shell is materialised when the region WIDENED by one cell along the axes its components read holds a face cell -- the get_region rule applied to
 // the cells actually read; a scalar kind (the one component 0) widens nothing.  Nothing a later step reads changes: the device writes are the
-// observer's own arrays, that ghost shell and a folded grid's fold row (observer_sample).  All device memory is `mem`'s.
+// observer's own arrays, that ghost shell and a folded grid's fold row (observer_sample).  The sample is enqueued on the main stream and not waited
+// for.  A slab's next step begins on the EDGE stream, and where the ghost shell lives in memory its first kernels (launch_flips) rewrite the shell of
+// u^n, which the cuts may still be reading; that stream last waited for the main stream at the end of the step before.  So a sample leaves
+// obs_pending set, and step_begin then has the edge stream wait for an event recorded on the main stream (ev_obs): add followed at once by the next
+// step reads what add, a read, then the step reads.  No host synchronisation (the ring exists to avoid one), and nothing at all per sample: an event
+// wait enqueued here, on the idle edge stream, made the next add's synchronisation of that stream cost 9 us (profiles/observer_ordering.txt).
+// All device memory is `mem`'s.
    struct Observer {
       const int kind; // pfeng::OBS_*: a handle is its kind's alone
       pf_region r{};
@@ -162,6 +168,7 @@
 
    // the sample of this moment: every component of u^n over the region -> position `fill` of its part of the ring
    int observer_sample(Observer *a) {
+      obs_pending = true; // whatever is enqueued below, on an error's way out too: the next split-phase step orders its edge stream behind it (step_begin)
       if ((lean || vg) && a->shell) { // the virtual ghost shell, exactly as get_region(1) writes it out, once for all components
          launch_flips(s_main, grids());
          HIPCHK(hipGetLastError());
@@ -179,7 +186,8 @@
          if (a->comp[k] >= 4) { lslot[a->comp[k] - 4] = slot; continue; }
          if ((rc = a->comp[k] == 0 ? region_to_slot(a->r, a->c, slot) : diff_to_slot(a->r, a->c, a->comp[k] - 1, slot))) return rc;
       }
-      return a->lat ? lat_to_slots(a->r, a->c, a->lat, lslot) : PF_OK; // all of them in one launch
+      if (a->lat && (rc = lat_to_slots(a->r, a->c, a->lat, lslot))) return rc; // all of them in one launch
+      return PF_OK;
    }
 
    // `nrows` device rows, cstride doubles apart, <-> the caller's: dense (pitch, rowstride = 0) or -- a slab's part of a chain's array -- the region's

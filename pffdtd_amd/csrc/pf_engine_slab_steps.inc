@@ -28,6 +28,12 @@
       if (in_step) return set_err(PF_ERR_STATE, "step_begin called twice");
       if (n < 0 || n >= Nt) return set_err(PF_ERR_ARG, "step %ld outside [0,Nt=%ld)", (long)n, (long)Nt);
       HIPCHK(hipSetDevice(op.device));
+      if (obs_pending) { // a region observer's sample may still be reading u^n, ghost shell included, on the main stream: every form of the step begins
+         // on the edge stream, which has not waited for the main stream since the step before (pf_engine_observe.inc, "The sample")
+         HIPCHK(hipEventRecord(ev_obs, s_main));
+         HIPCHK(hipStreamWaitEvent(s_edge, ev_obs, 0));
+         obs_pending = false;
+      }
       const int xl = 1, xh = (int)Nx - 2;
       // Slab engines with all four grids at hand step in temporally blocked pairs that span two split-phase steps:
       // phase 0 (step n): edge planes n -> n+1 on the edge stream; box n -> n+1, n+2 plus the shell n -> n+1 on the
