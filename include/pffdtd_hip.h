@@ -589,6 +589,48 @@ int     pf_multi_vdecim_read      (pf_multi *m, pf_vdecim *a, double *frames, in
 int     pf_multi_vdecim_get_state (pf_multi *m, pf_vdecim *a, double *acc, double *state);
 int     pf_multi_vdecim_set_state (pf_multi *m, pf_vdecim *a, const double *acc, const double *state, int64_t count);
 int     pf_multi_vdecim_destroy   (pf_multi *m, pf_vdecim *a);
+/* ---- wall absorption maps: the energy every step takes out of the room, per wall node, per material and per time bin -- on the device ----
+ * Which surface absorbs the energy: the one output that reads the WALLS, not the air.  A pf_absorb belongs to one engine (or chain) and observes no
+ * region: its nodes are the scene's frequency-dependent boundary nodes, its ABC nodes and its sources.  Per step n the reference Python engine's
+ * terms (python/fdtd/sim_fdtd.py:615-620), with vh the branch currents before and after the step:
+ *        wall node i:    wall_scale * ssaf_i * sum_m (vh_old + vh_new)^2_{i,m} * E[mat_i][m]      wall_scale = V_fac * 0.25 * h / l
+ *        ABC node j:     abc_scale * 2^-Q_j * Q_j * (u^{n+1}_j - u^{n-1}_j)^2                     abc_scale  = 0.5 * V_fac * h / l
+ *        source s:       in_scale * (u^{n+1}_s - u^{n-1}_s) * in_sig_s[n]                         in_scale   = 0.5 * V_fac * h / l2
+ * (V_fac: 2 on FCC grids, else 1; E: the second column of the materials' DEF triplets; in_sig: the sample the engine adds, in the field's precision).
+ * The wall terms are summed per node over the run and per material into a time bin, the ABC terms ("open boundary") and the source terms ("input")
+ * into the same bin.  The sums of a run equal the diagnostic's E_lost and E_in -- on every engine path, every fcc_flag, exchanged-axes storage, slab
+ * chains and across a checkpoint.  BROADBAND: the loss is quadratic in the branch currents, so a band's share needs a band-limited source.
+ *   - add(n, bin) is called between two steps: n is the index of the engine's NEXT step, the state is (u^{n-1}, u^n).  The first add after create or
+ *     set only primes (it copies the branch currents and u^{n-1} at the ABC and source nodes) and accounts nothing.  Every later add needs
+ *     n == last + 1 -- a gap means the step's old branch currents are gone: PF_ERR_STATE, the message names both numbers -- and puts step n - 1's
+ *     three quantities into `bin`.  One streaming pass over the node lists on the main stream, not waited for; the next step is ordered behind it.
+ *   - Arithmetic: double throughout, sums over a node's branches in ascending order, no fused multiply-add, NO floating-point atomics.  The sums
+ *     per material have an order fixed by the node order and the node count alone: the same run gives the same bits, and a run resumed from a
+ *     checkpoint (get, pf_engine_save_state; pf_engine_load_state, set) the bits of the one-piece run.
+ *   - get: nodes[Nbl] in the order of sd->bnl_ixyz, mats[nbin][Nm], abc[nbin], in[nbin]; a NULL array is skipped, nothing is reset.  set replaces the
+ *     sums (NULL: zeros) and the count; the next add primes.  pf_absorb_count: the steps accounted so far, or the count given to set.
+ *   - add, get and set are valid between runs only (PF_ERR_STATE inside a split-phase step or pass).  PF_ERR_ARG, with a message that names the
+ *     field, for a null E, nbin < 1, bin outside 0 .. nbin - 1, n outside 1 .. Nt, a negative count, a handle of another engine, chain or kind.
+ *     Scenes without frequency-dependent nodes (Nbl == 0) or without ABC nodes are fine: those rows stay zero.
+ *   - Device memory, all of it the engine's: a copy of the branch currents (round_up(Nbl, 64) * 12 Reals), Nbl + nbin * (Nm + 2) doubles, one Real per
+ *     ABC node and source, and the partial sums of one sample (Nm doubles per 256 nodes).
+ *   - A chain: one per slab on its own device; a slab accounts the nodes of the planes it owns, so every node, ABC node and source is counted once.
+ *     nodes are the slabs' rows put together (bit-equal to a single engine's), the bins the slabs' bins added in slab order on the host.  set gives
+ *     the bins to slab 0: a chain resumed mid-bin sums that bin in another order than the chain in one piece, so its bins agree to rounding
+ *     (Nbl * 2^-52 relative) while its nodes stay bit-equal; only a single engine resumes bit for bit.  add is all or nothing as
+ *     pf_multi_accum_add: create the chain with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES. */
+typedef struct pf_absorb pf_absorb;
+int     pf_engine_absorb_create (pf_engine *e, const double *E /*[Nm*PF_MMB]*/, double wall_scale, double abc_scale, double in_scale, int32_t nbin, pf_absorb **out);
+int     pf_engine_absorb_add    (pf_engine *e, pf_absorb *a, int64_t n, int64_t bin);
+int     pf_engine_absorb_get    (pf_engine *e, pf_absorb *a, double *nodes /*[Nbl], FILE order*/, double *mats /*[nbin*Nm]*/, double *abc /*[nbin]*/, double *in /*[nbin]*/);
+int     pf_engine_absorb_set    (pf_engine *e, pf_absorb *a, const double *nodes, const double *mats, const double *abc, const double *in, int64_t count); /* null = zero; the next add primes */
+int64_t pf_absorb_count         (const pf_absorb *a);   /* steps accounted */
+int     pf_engine_absorb_destroy(pf_engine *e, pf_absorb *a);
+int     pf_multi_absorb_create  (pf_multi *m, const double *E, double wall_scale, double abc_scale, double in_scale, int32_t nbin, pf_absorb **out);
+int     pf_multi_absorb_add     (pf_multi *m, pf_absorb *a, int64_t n, int64_t bin);
+int     pf_multi_absorb_get     (pf_multi *m, pf_absorb *a, double *nodes, double *mats, double *abc, double *in);
+int     pf_multi_absorb_set     (pf_multi *m, pf_absorb *a, const double *nodes, const double *mats, const double *abc, const double *in, int64_t count);
+int     pf_multi_absorb_destroy (pf_multi *m, pf_absorb *a);
 int  pf_engine_timing(pf_engine *e, pf_timing *t, int32_t reset);
 /* switch the per-launch HIP events of pf_opts.timing on / off between runs (a host times its headline region without them
  * and collects kernel durations in a region of its own) */

@@ -24,11 +24,11 @@ int pf__engine_get_region_x(pf_engine *e, int32_t which, const pf_region *r, voi
 // The region observers: field accumulators, band accumulators, vector band accumulators, decimating recorders and vector decimating recorders.  Their
 // kinds (an engine's object and a handle are their kind's alone) and what a message calls their handle types and their chain functions (pf_multi_<name>_*).
 namespace pfeng {
-enum : int { OBS_ACCUM, OBS_BAND, OBS_VBAND, OBS_DECIM, OBS_VDECIM };
-static const char *const obs_type[5] = {"pf_accum", "pf_bandacc", "pf_vbandacc", "pf_decim", "pf_vdecim"};
-static const char *const obs_name[5] = {"accum", "bandacc", "vband", "decim", "vdecim"};
+enum : int { OBS_ACCUM, OBS_BAND, OBS_VBAND, OBS_DECIM, OBS_VDECIM, OBS_ABSORB };
+static const char *const obs_type[6] = {"pf_accum", "pf_bandacc", "pf_vbandacc", "pf_decim", "pf_vdecim", "pf_absorb"};
+static const char *const obs_name[6] = {"accum", "bandacc", "vband", "decim", "vdecim", "absorb"};
 }
-// What the five handle types of pffdtd_hip.h share.  An engine's handle: `eng` and the engine's own object `impl`.  A chain's: `chain` and, in the
+// What the handle types of pffdtd_hip.h share.  An engine's handle: `eng` and the engine's own object `impl`.  A chain's: `chain` and, in the
 // derived type's `part`, one engine handle per slab, null where the region misses the slab -- part[g] observes region_part(...).local of slab g; its
 // rows land in the caller's arrays at out_off, the region's rows out_pitch and the device rows `cells` (of the whole region) apart.  `count` is kept
 // here, by the C ABI; an engine's recorder keeps its own (pf_decim_count asks it).
@@ -67,6 +67,15 @@ struct pf_vdecim : pf_observer { // frames are [ncomp][cells], acc [ncomp][P][ce
    static constexpr int kind = pfeng::OBS_VDECIM;
    std::vector<pf_vdecim *> part;
    int64_t factor = 1, cap = 0, rd = 0;
+};
+// The wall absorption maps (pf_engine_absorb.inc) observe no region: the lossy nodes, the ABC nodes and the sources of the engine.  A chain's: one part
+// per slab, every slab (part[g] never null); the chain keeps `primed`, `last` and `count` itself, so a gap in n is refused before any slab is asked.
+struct pf_absorb : pf_observer {
+   static constexpr int kind = pfeng::OBS_ABSORB;
+   std::vector<pf_absorb *> part;
+   int32_t nbin = 0;
+   bool primed = false;
+   int64_t last = -1;
 };
 // pf_engine_*_get / _set / _read / _get_state / _set_state with the caller's region rows `pitch` and channel / sum / state / frame / acc rows `rowstride`
 // doubles apart (0: dense) -- a slab's cells of a chain's arrays; count: as given.  The band accumulators': `a` is a pf_bandacc (scalar) or a pf_vbandacc; the

@@ -332,6 +332,40 @@ int64_t pf_vdecim_count(const pf_vdecim *a) { int64_t c, p; rec_numbers(a, &c, &
 int64_t pf_vdecim_pending(const pf_vdecim *a) { int64_t c, p; rec_numbers(a, &c, &p); return p; }
 int pf_engine_vdecim_destroy(pf_engine *e, pf_vdecim *a) { return destroy(e, a, pfeng::OBS_VDECIM, "pf_engine_vdecim_destroy"); }
 
+// the wall absorption maps observe no region; the engine's object keeps the count (a priming add accounts nothing)
+int pf_engine_absorb_create(pf_engine *e, const double *E, double wall_scale, double abc_scale, double in_scale, int32_t nbin, pf_absorb **out) {
+   const char *what = "pf_engine_absorb_create";
+   if (!e || !e->impl) return set_err(PF_ERR_ARG, "%s: null engine", what);
+   if (!out) return set_err(PF_ERR_ARG, "%s: null out", what);
+   *out = nullptr;
+   void *impl = nullptr;
+   const int rc = e->impl->absorb_create(E, wall_scale, abc_scale, in_scale, nbin, &impl);
+   if (rc) return rc;
+   pf_absorb *a = new pf_absorb();
+   a->eng = e; a->impl = impl; a->nbin = nbin;
+   e->observers.push_back(a);
+   *out = a;
+   return PF_OK;
+}
+int pf_engine_absorb_add(pf_engine *e, pf_absorb *a, int64_t n, int64_t bin) {
+   const int rc = mine(e, a, pfeng::OBS_ABSORB, "pf_engine_absorb_add");
+   return rc ? rc : e->impl->absorb_add(a->impl, n, bin);
+}
+int pf_engine_absorb_get(pf_engine *e, pf_absorb *a, double *nodes, double *mats, double *abc, double *in) {
+   const int rc = mine(e, a, pfeng::OBS_ABSORB, "pf_engine_absorb_get");
+   return rc ? rc : e->impl->absorb_get(a->impl, nodes, mats, abc, in);
+}
+int pf_engine_absorb_set(pf_engine *e, pf_absorb *a, const double *nodes, const double *mats, const double *abc, const double *in, int64_t count) {
+   const int rc = mine(e, a, pfeng::OBS_ABSORB, "pf_engine_absorb_set");
+   return rc ? rc : e->impl->absorb_set(a->impl, nodes, mats, abc, in, count);
+}
+int64_t pf_absorb_count(const pf_absorb *a) {
+   if (!a) return -1;
+   if (a->chain) return a->count;
+   return a->eng && a->eng->impl ? a->eng->impl->absorb_count(a->impl) : -1;
+}
+int pf_engine_absorb_destroy(pf_engine *e, pf_absorb *a) { return destroy(e, a, pfeng::OBS_ABSORB, "pf_engine_absorb_destroy"); }
+
 #define PF_NEED(e) if (!(e) || !(e)->impl) return set_err(PF_ERR_ARG, "null engine")
 
 int pf_engine_run(pf_engine *e, int64_t n0, int64_t nsteps) { PF_NEED(e); return e->impl->run(n0, nsteps); }

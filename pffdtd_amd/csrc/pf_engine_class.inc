@@ -33,6 +33,7 @@
 #include "pf_band.h"
 #include "pf_vband.h"
 #include "pf_vdecim.h"
+#include "pf_absorb.h"
 
 // shared between the two units (defined in pf_engine.hip)
 extern "C" void pf__set_error(const char *msg);
@@ -76,7 +77,13 @@ struct EngineBase {
    virtual int vdecim_get_state(const char *what, bool scalar, void *a, double *acc, double *state, int64_t pitch, int64_t rowstride) = 0;
    virtual int vdecim_set_state(const char *what, bool scalar, void *a, const double *acc, const double *state, int64_t pitch, int64_t rowstride, int64_t count) = 0;
    virtual int vdecim_info(bool scalar, void *a, int64_t *count, int64_t *pending) const = 0;
-   virtual int observer_destroy(const char *what, int kind, void *a) = 0; // any of the five kinds (pf_engine_observe.inc); kind: OBS_*
+   // the wall absorption maps (pf_engine_absorb.inc): the handle is a pf_absorb
+   virtual int absorb_create(const double *E, double wall_scale, double abc_scale, double in_scale, int nbin, void **out) = 0;
+   virtual int absorb_add(void *a, int64_t n, int64_t bin) = 0;
+   virtual int absorb_get(void *a, double *nodes, double *mats, double *abc, double *in) = 0;
+   virtual int absorb_set(void *a, const double *nodes, const double *mats, const double *abc, const double *in, int64_t count) = 0;
+   virtual int64_t absorb_count(void *a) const = 0;
+   virtual int observer_destroy(const char *what, int kind, void *a) = 0; // any of the kinds (pf_engine_observe.inc); kind: OBS_*
    virtual bool between_runs() const = 0; // not inside a split-phase step or pass
    virtual int save_state(pf_state *st) = 0;
    virtual int load_state(const pf_state *st) = 0;
@@ -1106,6 +1113,7 @@ template <typename Real> struct Engine : EngineBase {
 #include "pf_engine_accum.inc"
 #include "pf_engine_vband.inc"
 #include "pf_engine_vdecim.inc"
+#include "pf_engine_absorb.inc"
    void *stream(int which) override { return which == 1 ? (void *)s_edge : (void *)s_main; }
 };
 

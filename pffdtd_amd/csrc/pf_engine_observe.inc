@@ -59,12 +59,16 @@
       if (!(*a = observer_of<A>(h, kind))) return set_err(PF_ERR_ARG, "%s: the %s belongs to another engine", what, pfeng::obs_type[kind]);
       return PF_OK;
    }
-   template <typename A> int observer_enter(const char *what, void *h, int kind, A **a) {
+   template <typename A> int observer_stand(const char *what, void *h, int kind, A **a) { // (all but the drain: the absorption maps' add, pf_engine_absorb.inc)
       const int rc = observer_mine(what, h, kind, a);
       if (rc) return rc;
       if (in_step || in_pass()) return set_err(PF_ERR_STATE, "%s inside a split-phase step or pass (u^{n+1} is not complete in memory): valid between runs only", what);
       HIPCHK(hipSetDevice(op.device));
-      return sync();
+      return PF_OK;
+   }
+   template <typename A> int observer_enter(const char *what, void *h, int kind, A **a) {
+      const int rc = observer_stand(what, h, kind, a);
+      return rc ? rc : sync();
    }
    int observer_destroy(const char *what, int kind, void *h) override { // (pending samples are dropped)
       Observer *a;

@@ -122,6 +122,11 @@ int pf_h5_read(const char *path, const char *name, int code, void *out, int64_t 
    return 0;
 }
 
+/* pf_h5_write stores HDF5's modification time (seconds) in every dataset's header unless this is switched off: a file whose BYTES are to be the
+ * same whenever its contents are (pffdtd_amd/absorption.py) is written without them.  Default: on, as ever. */
+static int g_track_times = 1;
+void pf_h5_track_times(int on) { g_track_times = on ? 1 : 0; }
+
 /* mode 0: create/truncate the file; 1: open existing (create if missing) and replace/add the dataset */
 int pf_h5_write(const char *path, const char *name, int code, int ndims, const int64_t *dims,
                 const void *data, int mode, int gzip) {
@@ -150,6 +155,7 @@ int pf_h5_write(const char *path, const char *name, int code, int ndims, const i
       own_ft = 1;
    }
    hid_t pl = H5Pcreate(H5P_DATASET_CREATE);
+   if (!g_track_times) H5Pset_obj_track_times(pl, 0);
    if (gzip > 0 && ndims > 0 && total > 0) {
       hsize_t ch[8];
       int64_t per = 1;

@@ -54,6 +54,7 @@
 #include "pf_debug.h" // pf_opts_x: the public options + the development / test switches
 #include "pf_slab_cut.h" // Slab, partition, cut_slab: the cut itself, host code that needs no device
 #include "pf_state_cut.h" // scatter_state, gather_state: the canonical state cut to the slabs and put together again
+#include "pf_absorb_cut.h" // gather_rows, scatter_rows, add_bins: the wall absorption maps of the slabs put together
 #include "pf_region_cut.h" // region_check, region_part: a region of the field cut to the slabs
 
 extern "C" void pf__set_error(const char *msg); // pf_engine.hip (feeds pf_last_error)
@@ -1153,7 +1154,8 @@ int scene_face_check(const char *what, const pf_simdata *sd, const pf_region *r,
 
 // pre(): the kind's refusals that need no engine (the bin range, null weights); late(): the recorders' cap refusal, after the slabs were asked;
 // add(engine, part): the engine's add call, its arguments held by value (a slab thread calls it)
-template <typename H, typename Pre, typename Late, typename Add> int chain_add(pf_multi *m, H *a, const char *what, Pre pre, Late late, Add add) {
+// counts: the sample adds one to the chain's count (the absorption maps' priming sample accounts nothing)
+template <typename H, typename Pre, typename Late, typename Add> int chain_add(pf_multi *m, H *a, const char *what, Pre pre, Late late, Add add, bool counts = true) {
    Shared &S = m->S;
    if (chain_mine(m, a, what)) return PF_ERR_ARG;
    if (const int rc = pre()) return rc;
@@ -1173,7 +1175,7 @@ template <typename H, typename Pre, typename Late, typename Add> int chain_add(p
       if (m->broken && !S.err.load()) S.set_error(PF_ERR_HIP, "slab chain hung: a slab's host thread never came back");
    }
    const int rc = accum_status(S);
-   if (rc == PF_OK) a->count++;
+   if (rc == PF_OK && counts) a->count++;
    return rc;
 }
 
@@ -1451,6 +1453,101 @@ int pf_multi_vdecim_destroy(pf_multi *m, pf_vdecim *a) {
    if (!m) return fail("%s: null object", what);
    if (m->S.G == 1) return pf_engine_vdecim_destroy(m->S.eng[0], a);
    return chain_destroy(m, a, what, pf_engine_vdecim_destroy);
+}
+
+// ---- wall absorption maps of a chain (pf_absorb_cut.h): one per slab on its own device, EVERY slab (they observe no region); the chain keeps primed / last / count,
+// so a gap in n is refused before any slab is asked.  get and set walk the slabs on the caller's thread; add is the slab threads' sample command.
+int pf_multi_absorb_create(pf_multi *m, const double *E, double wall_scale, double abc_scale, double in_scale, int32_t nbin, pf_absorb **out) {
+   const char *what = "pf_multi_absorb_create";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_absorb_create(S.eng[0], E, wall_scale, abc_scale, in_scale, nbin, out);
+   if (!out) return fail("%s: null out", what);
+   *out = nullptr;
+   if (S.err.load()) return raised(S);
+   std::unique_ptr<pf_absorb> a(new pf_absorb());
+   a->chain = m; a->nbin = nbin;
+   a->part.assign((size_t)S.G, nullptr);
+   for (int g = 0; g < S.G; g++) {
+      const int rc = pf_engine_absorb_create(S.eng[g], E, wall_scale, abc_scale, in_scale, nbin, &a->part[g]);
+      if (rc) {
+         const std::string keep = pf_last_error();
+         for (int h = 0; h < g; h++) pf_engine_absorb_destroy(S.eng[h], a->part[h]);
+         pf__set_error(keep.c_str());
+         return rc;
+      }
+   }
+   m->observers.push_back(a.get());
+   *out = a.release();
+   return PF_OK;
+}
+int pf_multi_absorb_add(pf_multi *m, pf_absorb *a, int64_t n, int64_t bin) {
+   const char *what = "pf_multi_absorb_add";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_absorb_add(S.eng[0], a, n, bin);
+   if (chain_mine(m, a, what)) return PF_ERR_ARG;
+   const bool accounts = a->primed;
+   const int rc = chain_add(m, a, what, [&] {
+      if (bin < 0 || bin >= a->nbin) return failv(PF_ERR_ARG, "%s: bin = %ld outside 0 .. %d", what, (long)bin, a->nbin - 1);
+      if (a->primed && n != a->last + 1)
+         return failv(PF_ERR_STATE, "%s: n = %ld after n = %ld: a step between two samples was not seen (its branch currents are gone); sample before every step, or set and "
+                                    "start again", what, (long)n, (long)a->last);
+      return (int)PF_OK;
+   }, none, [=](pf_engine *e, pf_absorb *part) { return pf_engine_absorb_add(e, part, n, bin); }, accounts);
+   if (rc) return rc;
+   a->primed = true;
+   a->last = n;
+   return PF_OK;
+}
+int pf_multi_absorb_get(pf_multi *m, pf_absorb *a, double *nodes, double *mats, double *abc, double *in) {
+   const char *what = "pf_multi_absorb_get";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_absorb_get(S.eng[0], a, nodes, mats, abc, in);
+   if (chain_mine(m, a, what)) return PF_ERR_ARG;
+   if (S.err.load()) return raised(S);
+   const int64_t Nm = m->sd->Nm, nb = a->nbin;
+   std::vector<double> ln, lm((size_t)(nb * Nm)), la((size_t)nb), li((size_t)nb);
+   if (mats) std::fill(mats, mats + nb * Nm, 0.0);
+   if (abc) std::fill(abc, abc + nb, 0.0);
+   if (in) std::fill(in, in + nb, 0.0);
+   for (int g = 0; g < S.G; g++) { // (slab order: the bins' sums are the same bits every time)
+      const pf_cut::Slab &sl = S.slabs[g];
+      ln.resize(sl.bnl_rows.size());
+      const int rc = pf_engine_absorb_get(S.eng[g], a->part[g], nodes ? ln.data() : nullptr, lm.data(), la.data(), li.data());
+      if (rc) return rc;
+      if (nodes) pf_cut::gather_rows(sl, ln.data(), nodes);
+      if (mats) pf_cut::add_bins(mats, lm.data(), nb * Nm);
+      if (abc) pf_cut::add_bins(abc, la.data(), nb);
+      if (in) pf_cut::add_bins(in, li.data(), nb);
+   }
+   return PF_OK;
+}
+int pf_multi_absorb_set(pf_multi *m, pf_absorb *a, const double *nodes, const double *mats, const double *abc, const double *in, int64_t count) {
+   const char *what = "pf_multi_absorb_set";
+   PF_ACCUM_ENTER(what)
+   if (S.G == 1) return pf_engine_absorb_set(S.eng[0], a, nodes, mats, abc, in, count);
+   if (chain_mine(m, a, what)) return PF_ERR_ARG;
+   if (count < 0) return fail("%s: count < 0", what);
+   if (S.err.load()) return raised(S);
+   for (int g = 0; g < S.G; g++)
+      if (!pf__engine_between_runs(S.eng[g])) return failv(PF_ERR_STATE, "%s: a slab is inside a pair or triple: valid between passes only", what);
+   std::vector<double> ln;
+   for (int g = 0; g < S.G; g++) { // the scene's bins to slab 0, zeros to the others
+      const pf_cut::Slab &sl = S.slabs[g];
+      ln.resize(sl.bnl_rows.size());
+      if (nodes) pf_cut::scatter_rows(sl, nodes, ln.data());
+      const int rc = pf_engine_absorb_set(S.eng[g], a->part[g], nodes ? ln.data() : nullptr, g ? nullptr : mats, g ? nullptr : abc, g ? nullptr : in, count);
+      if (rc) return rc;
+   }
+   a->count = count;
+   a->primed = false;
+   a->last = -1;
+   return PF_OK;
+}
+int pf_multi_absorb_destroy(pf_multi *m, pf_absorb *a) {
+   const char *what = "pf_multi_absorb_destroy";
+   if (!m) return fail("%s: null object", what);
+   if (m->S.G == 1) return pf_engine_absorb_destroy(m->S.eng[0], a);
+   return chain_destroy(m, a, what, pf_engine_absorb_destroy);
 }
 
 int pf_multi_get_info(pf_multi *m, pf_multi_info *info) {

@@ -108,6 +108,8 @@ EXPORTS = ["pf_last_error", "pf_version", "pf_device_count", "pf_grid_bytes", "p
            "pf_engine_vdecim_create", "pf_engine_vdecim_add", "pf_engine_vdecim_read", "pf_engine_vdecim_get_state", "pf_engine_vdecim_set_state", "pf_engine_vdecim_destroy",
            "pf_vdecim_count", "pf_vdecim_pending",
            "pf_multi_vdecim_create", "pf_multi_vdecim_add", "pf_multi_vdecim_read", "pf_multi_vdecim_get_state", "pf_multi_vdecim_set_state", "pf_multi_vdecim_destroy",
+           "pf_engine_absorb_create", "pf_engine_absorb_add", "pf_engine_absorb_get", "pf_engine_absorb_set", "pf_engine_absorb_destroy", "pf_absorb_count",
+           "pf_multi_absorb_create", "pf_multi_absorb_add", "pf_multi_absorb_get", "pf_multi_absorb_set", "pf_multi_absorb_destroy",
            "pf_engine_energy_cfg", "pf_engine_run_energy", "pf_run_sim_devices", "pf_slab_partition", "pf_slab_partition_w", "pf_slab_partition_axis", "pf_slab_wall_scale",
            "pf_multi_create", "pf_multi_run", "pf_multi_get_info", "pf_multi_get_slab", "pf_multi_destroy",
            "pf_rccl_unique_id", "pf_rccl_comm_create", "pf_rccl_exchange", "pf_rccl_comm_destroy"]
@@ -223,6 +225,13 @@ def lib():
             getattr(L, pre + "_vdecim_get_state").argtypes = [vp, vp, vp, vp]
             getattr(L, pre + "_vdecim_set_state").argtypes = [vp, vp, vp, vp, i64]
             getattr(L, pre + "_vdecim_destroy").argtypes = [vp, vp]
+            getattr(L, pre + "_absorb_create").argtypes = [vp, vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, ctypes.POINTER(vp)]
+            getattr(L, pre + "_absorb_add").argtypes = [vp, vp, i64, i64]
+            getattr(L, pre + "_absorb_get").argtypes = [vp, vp, vp, vp, vp, vp]
+            getattr(L, pre + "_absorb_set").argtypes = [vp, vp, vp, vp, vp, vp, i64]
+            getattr(L, pre + "_absorb_destroy").argtypes = [vp, vp]
+        L.pf_absorb_count.restype = i64
+        L.pf_absorb_count.argtypes = [vp]
         L.pf_accum_count.restype = i64
         L.pf_accum_count.argtypes = [vp]
         L.pf_bandacc_count.restype = i64
@@ -540,6 +549,40 @@ class VectorDecimatingRecorder(DecimatingRecorder):
         self._make(what, owner, prefix, r, _pre3(what, pre_sos, self.ncomp), taps, factor, cap, depth, comp=(self.ncomp, _ptr(comp)), lead=(self.ncomp,))
 
 
+class Absorption(_Observer):
+    """The energy every step takes out of the room, on the device (pf_engine_absorb_* / pf_multi_absorb_*): per frequency-dependent node, per material
+    and time bin, with the open boundary's loss and the sources' input.  E: the materials' loss coefficients [Nm, 12] (DEF[..., 1], zero padded).
+    add(n, bin) before step n; the first add after creation or set only primes.  Broadband: see include/pffdtd_hip.h.
+    Made by HipEngine.absorption / HipMulti.absorption; it lives no longer than the object that made it."""
+    _kind, _handle, _noun = "absorb", "absorb", "absorption map"
+
+    def __init__(self, owner, prefix, E, wall_scale, abc_scale, in_scale, nbin):
+        sd = owner.sd
+        self.Nm, self.Nbl, self.nbin = int(sd.Nm), int(sd.Nbl), int(nbin)
+        E = np.ascontiguousarray(E, dtype=np.float64)
+        if E.size != self.Nm * PF_MMB:
+            raise PfError(f"absorption: E has {E.size} elements, the scene's {self.Nm} materials need [Nm, {PF_MMB}]")
+        self._bind(owner, prefix, ("create", "add", "get", "set", "destroy"))
+        _check(self._f["create"](owner._h, E.ctypes.data_as(ctypes.c_void_p), float(wall_scale), float(abc_scale), float(in_scale), self.nbin, ctypes.byref(self._a)))
+        self._shapes = (("nodes", (self.Nbl,)), ("materials", (self.nbin, self.Nm)), ("open_boundary", (self.nbin,)), ("input", (self.nbin,)))
+
+    def add(self, n, bin):
+        """before step n (the state is u^{n-1}, u^n): step n - 1's losses and input go into time bin `bin`; PfError (code 4) for a gap in n"""
+        _check(self._f["add"](self._owner._h, self._a, int(n), int(bin)))
+
+    def get(self):
+        """-> dict of float64 arrays: nodes [Nbl] in the order of sd.bnl_ixyz, materials [nbin, Nm], open_boundary [nbin], input [nbin]; nothing reset"""
+        out = {k: np.zeros(shape, dtype=np.float64) for k, shape in self._shapes}
+        _check(self._f["get"](self._owner._h, self._a, *(out[k].ctypes.data_as(ctypes.c_void_p) for k, _ in self._shapes)))
+        return out
+
+    def set(self, sums, count):
+        """replace the sums (a dict as get()'s; None, or a missing key: zeros) and the count; the next add primes -- how a resumed run continues"""
+        sums = sums or {}
+        arrs = _float64_or_none("Absorption.set", "absorption map", tuple((k, sums.get(k), shape) for k, shape in self._shapes))
+        _check(self._f["set"](self._owner._h, self._a, *map(_ptr, arrs), int(count)))
+
+
 def device_count():
     return int(lib().pf_device_count())
 
@@ -653,6 +696,11 @@ class HipMulti:
         """Low-pass filtered, decimated frames of up to four components of a region of the whole scene (pf_multi_vdecim_create): every slab keeps the
         part it owns, a difference across a cut reads the slab's ghost plane.  add raises PfError (code 4) where a slab stands inside a pair or triple."""
         return VectorDecimatingRecorder(self, "pf_multi", lo, hi, stride, comp, pre_sos, taps, factor, cap, depth)
+
+    def absorption(self, E, wall_scale, abc_scale, in_scale, nbin=1):
+        """The wall absorption maps of the whole scene (pf_multi_absorb_create): every slab accounts the nodes of the planes it owns.  add raises
+        PfError with code 4, and changes nothing, while any slab is inside a blocked pass."""
+        return Absorption(self, "pf_multi", E, wall_scale, abc_scale, in_scale, nbin)
 
     def slab(self, g):
         """-> dict(x0, x1, device, paired, steps_per_pass, engine): engine = a non-owning HipEngine view of slab g's engine (state_grids, timing)"""
@@ -827,6 +875,11 @@ class HipEngine:
         """Per cell of the region, on the device (pf_engine_vdecim_create): the components comp (as vector_band_accumulator's) through their own sections
         pre_sos [ncomp, npre, 6] and each through the FIR `taps`, every factor-th output kept as a frame [ncomp, c0, c1, c2] -- a VectorDecimatingRecorder."""
         return VectorDecimatingRecorder(self, "pf_engine", lo, hi, stride, comp, pre_sos, taps, factor, cap, depth)
+
+    def absorption(self, E, wall_scale, abc_scale, in_scale, nbin=1):
+        """The energy every step takes out of the room per wall node, per material and time bin, on the device (pf_engine_absorb_create): an
+        Absorption whose add(n, bin) is called before step n.  E [Nm, 12]: the materials' loss coefficients; the scales: include/pffdtd_hip.h."""
+        return Absorption(self, "pf_engine", E, wall_scale, abc_scale, in_scale, nbin)
 
     def set_grid(self, which, a):
         a = np.ascontiguousarray(a, dtype=self.dtype)

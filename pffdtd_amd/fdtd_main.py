@@ -69,6 +69,14 @@ response instead: channel 0 is W, the pressure, and one channel per axis is the 
 difference `--rec-stencil axis|lattice` names (the rules of `--dir-stencil`; regions one cell clear of the faces the difference reads); frames are
 [F, 1 + A, c0, c1, c2], and recordings.virtual_microphone points a first-order microphone anywhere at every cell.  Without `--rec-axes` the file is
 the pressure's, as before.
+
+Wall absorption maps (pffdtd_amd/absorption.py): `--absorption` sums ON THE DEVICE, at EVERY step from `--absorption-first N` (default 0) on, the energy the
+step loses per frequency-dependent wall node, per material and at the open boundary, and the energy the sources put in, into time bins of
+`--absorption-bin-ms 5` milliseconds, and writes them to sim_absorption.h5 beside sim_outs.h5 at every checkpoint and at the end: which surface takes
+the energy out of the room.  It names no regions -- it reads the walls -- and is broadband.  Everything else as the decay arguments: the run is cut at
+every step from N on, a chain is created with PF_MULTI_NO_PAIRS | PF_MULTI_NO_TRIPLES (one line says so), `--resume` restores the sums from the file and,
+on one domain, gives the file of a run in one piece byte for byte (a chain of slabs: the node sums bit for bit, the bins to rounding -- the file keeps
+the scene's bins, not each slab's), and without these arguments nothing about a run changes.
 """
 import argparse
 import os
@@ -78,6 +86,7 @@ from types import ModuleType
 from typing import Callable, NamedTuple
 
 from . import checkpoint, engine, fields, sim_data, spectra
+from . import absorption as absorb_mod
 from . import decay as decay_mod
 from . import directional as dir_mod
 from . import recordings as rec_mod
@@ -134,7 +143,7 @@ def _run_chain(a, sd, m):
     """all Nt steps of a chain object, in one go or in chunks with progress reports; returns (seconds, timing of the busiest slab).
     With --resume / --checkpoint / --stop-after: from the resumed step, to the step the run stops after (a.stopped_at: less than Nt then)."""
     live = range(m.nslabs)
-    if a.resume or a.checkpoint or a.field_every or any(getattr(a, kind.flag) for kind in KINDS):
+    if a.resume or a.checkpoint or a.field_every or any(getattr(a, kind.flag, False) for kind in KINDS):
         return _run_chain_checkpointed(a, sd, m)
     t0 = time.perf_counter()
     if not a.progress:
@@ -186,6 +195,10 @@ class _Kind(NamedTuple):
     attach_names_regions: bool  # a PfError of attach is a refusal of the regions: it exits as "--<prefix>-planes / --<prefix>-box: ..."
     sampled: str  # why its chain takes single steps (_chain_flags)
     done: Callable  # the output -> the end-of-run line between "--field " and ": <path>"
+    asked_by: str = ""  # the arguments that ask for it, in refusals (default: --<prefix>-planes / --<prefix>-box)
+
+    def names(self):
+        return self.asked_by or f"--{self.prefix}-planes / --{self.prefix}-box"
 
 
 def _stencil_words(prefix):
@@ -212,6 +225,9 @@ KINDS = (  # in the order they are built, sampled within a step, written and rep
           (("--dir-", "--rec-"),) + _stencil_words("rec"), True, "every step is sampled",  # (attach: a factor or a tap count the engine refuses, a region on a face along a recorded axis)
           lambda o: f"recording of {o.count} samples, {o.frames} frames at every {o.factor}th step through {o.taps.size} taps"
                     + ("" if o.axes is None else f", channels W {' '.join('XYZ'[k - 1] for k in o.axes.tolist())} ({o.stencil} differences)")),
+    _Kind("absorption", "absorption", "absorption", absorb_mod, "sim_absorption.h5",  # (no regions: it reads the walls)
+          lambda a, sd, regions, path, resume_at: absorb_mod.WallAbsorption(path, sd, a.absorption_bin_ms, a.absorption_first, resume_at=resume_at),
+          (), False, "every step is sampled", lambda o: f"wall absorption of {o.count} steps, {int(o.Nm)} materials, bins of {o.bin_steps} steps", "--absorption"),
 )
 
 
@@ -219,8 +235,9 @@ def _field_output(kind, a, sd, m, resume_at):
     """the output of `kind` on chain m, attached; a resumed run's state is restored from its file"""
     N = (sd.Nx, sd.Ny, sd.Nz)
     try:
-        regions = [r for spec in getattr(a, kind.prefix + "_planes") for r in fields.parse_planes(spec, N)] + [fields.parse_box(spec, N) for spec in getattr(a, kind.prefix + "_box")]
-        path = getattr(a, kind.prefix + "_file") or Path(a.data_dir) / kind.file
+        regions = ([r for spec in getattr(a, kind.prefix + "_planes", ()) for r in fields.parse_planes(spec, N)]
+                   + [fields.parse_box(spec, N) for spec in getattr(a, kind.prefix + "_box", ())])
+        path = getattr(a, kind.prefix + "_file", "") or Path(a.data_dir) / kind.file
         out = kind.build(a, sd, regions, path, resume_at)
     except ValueError as e:
         text = str(e).replace("--field-", f"--{kind.prefix}-")
@@ -232,14 +249,14 @@ def _field_output(kind, a, sd, m, resume_at):
     except engine.PfError as e:
         if not kind.attach_names_regions:
             raise
-        raise SystemExit(f"--{kind.prefix}-planes / --{kind.prefix}-box: {e}")
+        raise SystemExit(f"{kind.names()}: {e}")
     return out
 
 
 def _chain_flags(a, nslabs):
     """multi_flags of the chain: sampled by a field output of KINDS, no slab steps in pairs or triples (a sample is never shifted, and no slab
     answers inside a pass)"""
-    asked = [kind for kind in KINDS if getattr(a, kind.flag)]
+    asked = [kind for kind in KINDS if getattr(a, kind.flag, False)]
     if not asked or nslabs < 2:
         return 0
     for kind in reversed(asked):
@@ -260,7 +277,7 @@ def _run_chain_checkpointed(a, sd, m):
         m.load_state(state)
         print(f"--resumed at step {n} of {sd.Nt}: {a.resume}", flush=True)
     fw = _field_writer(a, sd, n if a.resume else None)
-    outs = [(kind, _field_output(kind, a, sd, m, n if a.resume else None)) for kind in KINDS if getattr(a, kind.flag)]
+    outs = [(kind, _field_output(kind, a, sd, m, n if a.resume else None)) for kind in KINDS if getattr(a, kind.flag, False)]
     cuts = ([fw] if fw else []) + [out for _, out in outs]  # the run is cut at the next step of each of these
     end = sd.Nt if a.stop_after is None else min(max(a.stop_after, n), sd.Nt)
     every = a.checkpoint_every if a.checkpoint else 0
@@ -292,6 +309,7 @@ def _run_chain_checkpointed(a, sd, m):
             n = _save_checkpoint(a, sd, m, n)
             end = max(end, n)
             for _, out in outs:
+                out.settle(m, n)
                 out.write()  # (the output of the sample steps below n: what --resume of this checkpoint continues)
         for _, out in outs:
             if out.due(n) and n < end:
@@ -308,6 +326,7 @@ def _run_chain_checkpointed(a, sd, m):
             _progress(sd, n, sd.Nt, now - t0, now - tc, k, air_all, air, max(step_all - air_all, 1e-12), max(step - air, 1e-12), m.nslabs)
     a.stopped_at = n
     for kind, out in outs:
+        out.settle(m, n)
         out.write()
         print(f"--field {kind.done(out)}: {out.path}", flush=True)
         out.close()
@@ -455,7 +474,7 @@ def main():
         p.error("--checkpoint-every / --stop-after: not negative")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     fixed = [("--checkpoint / --resume", a.checkpoint or a.resume), ("--field-planes / --field-box", a.field_every)]
-    for names, asked in fixed + [(f"--{kind.prefix}-planes / --{kind.prefix}-box", getattr(a, kind.flag)) for kind in KINDS]:
+    for names, asked in fixed + [(kind.names(), getattr(a, kind.flag, False)) for kind in KINDS]:
         if world > 1 and asked and not a.devices:
             raise SystemExit(f"{names}: not under a one-process-per-GPU launcher (WORLD_SIZE > 1); run one process with --gpus N or --devices")
     if a.devices:

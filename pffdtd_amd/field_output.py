@@ -5,8 +5,9 @@
     class FieldDirectional(FieldOutput)   directional.py    one engine.VectorBandAccumulator
     class FieldRecording(FieldOutput)     recordings.py     one engine.DecimatingRecorder or engine.VectorDecimatingRecorder
     class FieldWriter(Schedule)           fields.py         no observer: frames through the host
+    class WallAbsorption(FieldOutput)     absorption.py     one engine.Absorption, no regions: it reads the walls
 
-The rules, for all four device-side kinds:
+The rules, for all device-side kinds:
   * Samples are due at the steps first, first + every, ... below Nt (Schedule); `every` is 1 for every kind but the spectrum -- a recursive filter
     over skipped samples is another filter.  The sample of step n is u^n, the field the receivers of step n sample.
   * `take(obj, n)` takes the sample of step n and of no other: a sample is NEVER shifted.  A chain answers only while no slab is inside a pair or
@@ -69,11 +70,18 @@ class FieldOutput(Schedule):
         """one observer per region on obj (a HipEngine or a HipMulti); a resumed run's state goes into them"""
         if self.observers is not None:
             return
-        self.observers = [self._observer(obj, lo, hi, st) for lo, hi, st in self.regions]
+        self.observers = self._observers(obj)
         if self._restore is not None:
             for i, o in enumerate(self.observers):
                 self._restore_observer(o, i, *self._restore)
             self._restore = None
+
+    def _observers(self, obj):
+        """one per region; a kind without regions (absorption.py) makes its own"""
+        return [self._observer(obj, lo, hi, st) for lo, hi, st in self.regions]
+
+    def settle(self, obj, n):
+        """before a write with obj standing before step n: nothing to do for a kind whose sample of step n belongs to step n (absorption.py closes step n - 1)"""
 
     @property
     def count(self):

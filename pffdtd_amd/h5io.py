@@ -34,6 +34,8 @@ def _lib():
         L.pf_h5_write.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
                                   ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
         L.pf_h5_list.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int64]
+        L.pf_h5_track_times.argtypes = [ctypes.c_int]
+        L.pf_h5_track_times.restype = None
         _LIB = L
     return _LIB
 
@@ -93,8 +95,9 @@ def read(path, name, dtype=None):
     return arr[()] if arr.ndim == 0 else arr
 
 
-def write(path, name, data, code=None, append=True, gzip=0):
-    """Write `data` as dataset `name`. bool arrays are stored as h5py-compatible enums."""
+def write(path, name, data, code=None, append=True, gzip=0, times=True):
+    """Write `data` as dataset `name`. bool arrays are stored as h5py-compatible enums.  times=False: without HDF5's modification time in the
+    dataset's header, for files whose bytes are to depend on their contents alone."""
     a = np.asarray(data)
     if code is None:
         if a.dtype == np.bool_:
@@ -120,6 +123,13 @@ def write(path, name, data, code=None, append=True, gzip=0):
     shape = a.shape  # np.ascontiguousarray would promote rank-0 to rank-1; the reference needs rank-0 scalars
     a = np.ascontiguousarray(a, dtype=_CODE_TO_NP[code]).reshape(shape)
     dims = (ctypes.c_int64 * 8)(*shape)
-    if _lib().pf_h5_write(os.fsencode(str(path)), name.encode(), code, a.ndim, dims,
-                          a.ctypes.data_as(ctypes.c_void_p), 1 if append else 0, int(gzip)) != 0:
+    L = _lib()
+    if not times:
+        L.pf_h5_track_times(0)
+    try:
+        rc = L.pf_h5_write(os.fsencode(str(path)), name.encode(), code, a.ndim, dims, a.ctypes.data_as(ctypes.c_void_p), 1 if append else 0, int(gzip))
+    finally:
+        if not times:
+            L.pf_h5_track_times(1)
+    if rc != 0:
         raise IOError(_err())
